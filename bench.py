@@ -14,9 +14,19 @@ work per step is fixed.  Inputs are resident in HBM before the timed region.  Wi
 own 4096 trajectories (no data-path collective) and the run ends with the one exchange the north star names: an RCCL
 all-gather of the (K, k) gain stacks, inside the timed region.
 
-Rank 0 prints ONE JSON line: throughput, the roofline of the dominant kernel (the sweep; HIP-event durations measured
-inside the timed region) and, at N = 1, the CPU baseline (the oracle's reference-style fp64 finite-difference iLQR,
-`oracle/ilqr.py`, on a bounded sample, fanned out over the host cores like the reference's own data collection).
+Rank 0 prints ONE JSON line: throughput, per-kernel durations (HIP events inside the timed region) and the roofline of the
+dominant kernel (the sweep) as far as it needs no run of its own.  A plain run does nothing else: set-up, clock settle,
+warm-up, the timed steps, the line.
+
+    --full               also everything beside the headline: the un-settled rate (a second run), the sweep's lone-wave
+                         chain floor (a run of its own), at N = 1 the CPU baseline (the oracle's reference-style fp64
+                         finite-difference iLQR, `oracle/ilqr.py`, on a bounded sample, fanned out over the host cores like
+                         the reference's own data collection) and the `extras` block (other workloads, precisions, sizes and
+                         the product paths).  --no-cpu-baseline / --no-extras drop parts of it.
+    --dump-outputs DIR   after the timed steps, rank 0 writes what the timed path handed back in its last step as
+                         DIR/<name>.npy (float32 / float64; integer arrays as float64): x, u, cost, K, k, alpha_idx, status.
+                         The inputs are seeded, so two builds can be compared output for output.  Above 64 MB in all, a
+                         fixed, seeded sample of trajectories is written, their batch indices in DIR/trajectory_index.npy.
 """
 import argparse
 import json
@@ -544,6 +554,33 @@ def latest_mfma_busy(kernel_prefix, pattern="*_pmc_sq_hybrid.json"):
     return None, None
 
 
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir, solver):
+    """--dump-outputs: the arrays a caller of the timed iteration receives (state, controls, cost, gains, line-search
+    result, status) as DIR/<name>.npy, all with the batch as their first axis; a seeded sample of trajectories above the
+    budget.  -> {name: shape}."""
+    arrays = {"x": solver.x, "u": solver.u, "cost": solver.cost, "K": solver.K, "k": solver.k,
+              "alpha_idx": solver.alpha_idx, "status": solver.status}
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[name] = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+    B = host["x"].shape[0]
+    rows = np.arange(B)
+    per_row = 8 + sum(a.nbytes for a in host.values()) // B             # (+ the index array itself)
+    if per_row * B > DUMP_BUDGET_BYTES:
+        keep = max(1, DUMP_BUDGET_BYTES // per_row)
+        rows = np.sort(np.random.default_rng(0).choice(B, size=keep, replace=False))
+        host = {name: a[rows] for name, a in host.items()}
+    host["trajectory_index"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {name: list(a.shape) for name, a in host.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -552,14 +589,19 @@ def main():
     ap.add_argument("--clock-settle-ms", type=float, default=60.0,
                     help="untimed run of the workload before the warm-up steps (GPU clock ramp); 0 disables")
     ap.add_argument("--batch", type=int, default=BATCH_PER_GPU, help="trajectories per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline workload only (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: un-settled rate, lone-wave chain floor, CPU baseline, "
+                         "extras (other workloads, precisions, sizes, product paths)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no extras block")
     ap.add_argument("--no-fused-sweep", action="store_true",
                     help="A/B: linearise in a kernel of its own (TILE16C records) instead of inside the sweep")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--workload", choices=("pure", "hybrid", "cartpole"), default="pure",
                     help="pure = BASELINE configs[2]/[3] (the metric's config); hybrid = configs[4], transformer-predicted "
-                         "gains; cartpole = configs[1].  The default run reports the other two under `extras`.")
+                         "gains; cartpole = configs[1].  A --full run of pure reports the other two under `extras`.")
     args = ap.parse_args()
 
     if args.cpu_baseline_only:
@@ -584,7 +626,7 @@ def main():
         raise SystemExit(f"rank {rank}: failing on request (QT_BENCH_TEST_FAIL_RANK)")
 
     cpu = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         # In a child process of its own, before this process touches the GPU.  Measured: when the worker pool is
         # forked from THIS process, every later step of the GPU leg idles ~0.7 ms between the sweep and the line search
         # (host calls stay ~15 us, kernel durations in rocprofv3 are unchanged) — 2.3e8 instead of 1.08e9 steps/s.
@@ -687,6 +729,7 @@ def main():
             roof["traffic"], roof["traffic_source"] = traffic, src
             if traffic is not None:
                 roof["traffic_frac"] = traffic / sweep_s / 1e9 / HBM_PEAK_GBS
+        if kind == "pure" and B == BATCH_PER_GPU and args.full:
             # What the kernel IS bound by: (1) the dependency chain — a lone wave's time for one sweep (measured here, B = 2: one
             # workgroup on an empty chip) x the residency rounds of the batch (B waves on 1024 SIMDs x 4 waves); (2) instruction
             # issue with every SIMD carrying 4 such waves — VALU-port and matrix-pipe busy fractions from the SQ counter pass
@@ -774,9 +817,10 @@ def main():
 
     kind = args.workload
     B = args.batch
-    # first the driver's command as it stands (W warm-up steps in a fresh process, no settle phase), then the settled rate
+    # --full: first the driver's command as it stands (W warm-up steps in a fresh process, no settle phase); then the settled
+    # rate, the headline
     no_settle = None
-    if args.clock_settle_ms > 0:
+    if args.full and args.clock_settle_ms > 0:
         _, el_ns, _, comm_ns = run(kind, B, args.steps, args.warmup, world > 1, settle_ms=0.0)
         no_settle = {"value_no_settle": world * B * HORIZON * args.steps / el_ns,
                      "ms_per_step_no_settle": 1e3 * el_ns / args.steps}
@@ -784,13 +828,14 @@ def main():
             no_settle["gather_ms_no_settle"] = comm_ns["gather_ms"]
     wl, elapsed, host_issue, comm = run(kind, B, args.steps, args.warmup, world > 1)
     solver = wl.solver
+    dumped = dump_outputs(args.dump_outputs, solver) if args.dump_outputs and rank == 0 else None
     kern_ms = wl.kernel_ms()
     accepted = float((solver.alpha_idx >= 0).float().mean().item())
     bad = int((solver.status != 0).sum().item())
 
     # ------------------------------------------------------------------------------------------ extras (rank 0, N = 1)
     extras = {}
-    if rank == 0 and world == 1 and not args.no_extras and kind == "pure":
+    if args.full and rank == 0 and world == 1 and not args.no_extras and kind == "pure":
         def product_iterate(sv_kind, B_, steps=20):
             """The product's own iteration — QuattroILQR.iterate(): pure mode = ONE C call (quattro_ilqr_iterate_f32:
             linearise + sweep + line search), no simulate (an accepted forward pass IS the next nominal) — from the same
@@ -1183,6 +1228,8 @@ def main():
             out["speedup_vs_cpu_all_cores"] = out["value"] / base["value"]
         if extras:
             out["extras"] = extras
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

@@ -17,9 +17,9 @@ if [ "$1" == "build" ]; then
 else
   show='import sys,json; d=json.loads(sys.stdin.readline()); print("sweep %.1f us, lone wave %.1f us" % (1e3*d["kernel_ms"]["sweep"], 1e3*d["roofline"]["lone_wave_sweep_ms"]))'
   for rep in 1 2; do
-    echo -n "[shipped] "; python bench.py --no-cpu-baseline --no-extras --steps 100 --warmup 20 2>/dev/null | python3 -c "$show"
+    echo -n "[shipped] "; python bench.py --full --no-cpu-baseline --no-extras --steps 100 --warmup 20 2>/dev/null | python3 -c "$show"
     for n in 1 2 3 4 5; do
-      echo -n "[without segment $n] "; QUATTRO_HIP_LIB=$(realpath build_ab/lib_abl$n.so) python bench.py --no-cpu-baseline --no-extras --steps 100 --warmup 20 2>/dev/null | python3 -c "$show"
+      echo -n "[without segment $n] "; QUATTRO_HIP_LIB=$(realpath build_ab/lib_abl$n.so) python bench.py --full --no-cpu-baseline --no-extras --steps 100 --warmup 20 2>/dev/null | python3 -c "$show"
     done
   done
 fi

@@ -9,7 +9,8 @@ timeout -k 10 900 python -m pytest tests -m gpu -q -x > gpurun_out/pytest_$tag.l
 rc=$?
 tail -5 gpurun_out/pytest_$tag.log
 if [ $rc -ne 0 ]; then echo "pytest failed rc=$rc: stopping"; exit 1; fi
-timeout -k 10 600 python bench.py > gpurun_out/bench_$tag.json 2> gpurun_out/bench_$tag.err || { echo "bench failed"; tail -20 gpurun_out/bench_$tag.err; exit 1; }
+mkdir -p bench_out
+timeout -k 10 600 python bench.py --full > bench_out/bench_$tag.json 2> bench_out/bench_$tag.err || { echo "bench failed"; tail -20 bench_out/bench_$tag.err; exit 1; }
 echo "bench done"
 export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_$tag -o bench -- python3 bench.py --no-cpu-baseline --no-extras --steps 20 > gpurun_out/prof_$tag.log 2>&1 || { echo "rocprof failed"; tail -20 gpurun_out/prof_$tag.log; exit 1; }

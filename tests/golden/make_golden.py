@@ -28,8 +28,10 @@ Fixture families:
                                    (quattro_ilqr_tf.py:66-84): a planar two-rotor vehicle with a non-diagonal, non-quadratic cost,
                                    Euler and RK4 — optimize() logs for several starts; pins the user-compiled models of
                                    quattro_ilqr_amd.compile_model (tests/test_user_model_gpu.py holds the same problem as C++ bodies)
+  G14    mpc_objects_<model>.npz   the reference's QuadrotorMPC / CartPoleMPC as data: the attributes the drop-in recognises them
+                                   by and their callables' outputs at the drop-in's probe points (tests/test_host_cpu.py)
 
-`--only dataset` regenerates G10 alone, `--only lqr` G11, `--only user_planar` G13.
+`--only dataset` regenerates G10 alone, `--only lqr` G11, `--only user_planar` G13, `--only mpc_objects` G14.
 """
 import os
 import sys
@@ -491,9 +493,47 @@ def gen_user_planar(n_states=4, N=30, max_iter=40):
     save("user_planar.npz", **out)
 
 
+# ------------------------------------------------------------------ G14
+PROBE_SEED, PROBE_POINTS = 20240607, 6          # quattro_ilqr_amd.solver.probe_callables: seed and number of probe points
+
+
+def probe_points(x_ref, m):
+    """The points quattro_ilqr_amd.solver.probe_callables evaluates a problem object's callables at."""
+    rng = np.random.default_rng(PROBE_SEED)
+    xs = np.asarray(x_ref, dtype=np.float64) + 0.3 * rng.standard_normal((PROBE_POINTS, len(x_ref)))
+    us = rng.uniform(-0.5, 3.0, (PROBE_POINTS, m))
+    return xs.astype(np.float32).astype(np.float64), us.astype(np.float32).astype(np.float64)
+
+
+def gen_mpc_objects(model):
+    """The reference's own problem objects (QuadrotorMPC / CartPoleMPC, ilqr_only, horizon 20, dt 0.01, Euler) as data: the
+    attributes the drop-in recognises them by, the arguments they hand to iLQR_TF, and what their bound discrete_dynamics /
+    running_cost / final_cost return at the probe points, in the three states tests/test_host_cpu.py walks them through
+    (Euler; RK4; RK4 with Qf doubled)."""
+    mpc = make_mpc(model, 20, "euler")
+    m = np.asarray(mpc.R).shape[0]
+    xs, us = probe_points(mpc.x_ref, m)
+    dyn_names = sorted(k for k, v in vars(mpc.dynamics).items() if isinstance(v, (int, float)) and not isinstance(v, bool))
+    arrays = dict(Q=mpc.Q, R=mpc.R, Qf=mpc.Qf, x_ref=mpc.x_ref, dt=float(mpc.dt), horizon=len(mpc.ilqr.u),
+                  u_init=np.array([np.asarray(u, dtype=np.float64).reshape(-1) for u in mpc.ilqr.u]), tol=float(mpc.ilqr.tol),
+                  dyn_names=np.array(dyn_names), dyn_values=np.array([float(getattr(mpc.dynamics, k)) for k in dyn_names]),
+                  probe_x=xs, probe_u=us)
+    if model == "quadrotor":
+        arrays.update(alpha=float(mpc.alpha), beta=float(mpc.beta))
+    for tag, method, qf_scale in (("euler", "euler", 1.0), ("rk4", "rk4", 1.0), ("rk4_qf2", "rk4", 2.0)):
+        mpc.integration_method, mpc.Qf = method, qf_scale * arrays["Qf"]
+        arrays[f"f_{tag}"] = np.array([mpc.discrete_dynamics(x.copy(), u.copy()) for x, u in zip(xs, us)], dtype=np.float64)
+        arrays[f"L_{tag}"] = np.array([float(mpc.running_cost(x.copy(), u.copy())) for x, u in zip(xs, us)])
+        arrays[f"Lf_{tag}"] = np.array([float(mpc.final_cost(x.copy())) for x in xs])
+    save(f"mpc_objects_{model}.npz", **arrays)
+
+
 if __name__ == "__main__":
     torch.manual_seed(0)
     torch.set_num_threads(1)
+    if sys.argv[1:] == ["--only", "mpc_objects"]:
+        gen_mpc_objects("quadrotor"); gen_mpc_objects("cartpole")
+        sys.exit(0)
     if sys.argv[1:] == ["--only", "int8"]:
         gen_int8("cartpole"); gen_int8("quadrotor")
         sys.exit(0)
@@ -530,3 +570,4 @@ if __name__ == "__main__":
     gen_lqr()
     gen_int8("cartpole"); gen_int8("quadrotor")
     gen_user_planar()
+    gen_mpc_objects("quadrotor"); gen_mpc_objects("cartpole")

@@ -3,6 +3,7 @@ import ctypes
 import os
 import subprocess
 import sys
+import types
 
 import numpy as np
 import pytest
@@ -319,9 +320,6 @@ def test_user_model_library_builds_and_exports_the_whole_abi():
 
 
 # ------------------------------------------------------------------------------------------------ reference problem objects
-REFERENCE = "/root/reference"
-
-
 def _oracle_device_eval(md, xs, us, device):
     """Stand-in for solver._device_eval where there is no GPU (the build container): the fp64 oracle of the same model."""
     from oracle import models as o_models
@@ -334,25 +332,59 @@ def _oracle_device_eval(md, xs, us, device):
     return f, np.array([spec.L(x, u) for x, u in zip(xs, us)]), np.array([spec.Lf(x) for x in xs])
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="needs the reference checkout (build container only)")
+class _RecordedProblem:
+    """The reference's QuadrotorMPC / CartPoleMPC (examples/*/…_mpc.py) as the drop-in meets them, from the G14 fixture
+    (tests/golden/mpc_objects_<model>.npz, captured from the reference itself by make_golden.py): the attributes it recognises
+    them by, and bound discrete_dynamics / running_cost / final_cost that answer with the reference's own outputs at the
+    points they were captured at (the drop-in's probe points), in each captured state: Euler, RK4, RK4 with Qf doubled.
+    Anywhere else they raise: nothing here computes a model of its own."""
+
+    def __init__(self, g):
+        self._g = g
+        self.Q, self.R, self.Qf, self.x_ref = (np.array(g[k]) for k in ("Q", "R", "Qf", "x_ref"))
+        self.dt, self.integration_method = float(g["dt"]), "euler"
+        self.dynamics = types.SimpleNamespace(**{str(k): float(v) for k, v in zip(g["dyn_names"], g["dyn_values"])})
+        if "alpha" in g.files:
+            self.alpha, self.beta = float(g["alpha"]), float(g["beta"])
+
+    def _recorded(self, what, x, u=None):
+        g = self._g
+        qf = {1.0: "", 2.0: "_qf2"}[next(s for s in (1.0, 2.0) if np.array_equal(self.Qf, s * g["Qf"]))]
+        hit = np.all(g["probe_x"] == np.asarray(x, dtype=np.float64), axis=1)
+        if u is not None:
+            hit &= np.all(g["probe_u"] == np.asarray(u, dtype=np.float64).reshape(-1), axis=1)
+        i = int(np.flatnonzero(hit)[0])
+        return g[f"{what}_{self.integration_method}{qf}"][i]
+
+    def discrete_dynamics(self, x, u):
+        return self._recorded("f", x, u).copy()
+
+    def running_cost(self, x, u):
+        return float(self._recorded("L", x, u))
+
+    def final_cost(self, x):
+        return float(self._recorded("Lf", x))
+
+
 @pytest.mark.parametrize("which", ["quadrotor", "cartpole"])
 def test_the_references_own_mpc_objects_bind_to_the_dropin(which, monkeypatch):
-    """SURVEY 8(b) 'never an error': the reference's QuadrotorMPC / CartPoleMPC (examples/*/…_mpc.py), constructed UNCHANGED
-    with this package's iLQR_TF in place of theirs, bind — their bound methods are recognised by the owner's attribute set and
-    verified by probing the three callables against the device model (here evaluated by the oracle: no GPU in this container).
-    A tampered cost (attributes say one thing, the callable computes another) must be refused."""
+    """SURVEY 8(b) 'never an error': the reference's QuadrotorMPC / CartPoleMPC hand their bound methods to iLQR_TF; with this
+    package's iLQR_TF in its place they bind — recognised by the owner's attribute set and verified by probing the three
+    callables against the device model (here evaluated by the oracle: no GPU in this container).  The reference objects are
+    replayed from what they returned (_RecordedProblem, G14).  A tampered cost (attributes say one thing, the callable
+    computes another) must be refused."""
     pytest.importorskip("torch")
-    import importlib
     from quattro_ilqr_amd import solver
-    for p in (REFERENCE, os.path.join(REFERENCE, "examples", which)):
-        monkeypatch.syspath_prepend(p)
-    monkeypatch.setattr(sys, "dont_write_bytecode", True)
     monkeypatch.setattr(solver, "_device_eval", _oracle_device_eval)
-    ref_mod = importlib.import_module(f"{which}_mpc")
-    monkeypatch.setattr(ref_mod, "iLQR_TF", solver.iLQR_TF)            # the drop-in: same constructor call, our class
-    cls = ref_mod.QuadrotorMPC if which == "quadrotor" else ref_mod.CartPoleMPC
-    kw = dict(horizon=20, dt=0.01, integration_method="euler")
-    mpc = cls(**kw) if which == "quadrotor" else cls(ilqr_only=True, **kw)
+    g = load_golden(f"mpc_objects_{which}.npz")
+    mpc = _RecordedProblem(g)
+    # the iLQR_TF call of the reference's constructors (quadrotor_mpc.py:55-66, cartpole_mpc.py:207-216, ilqr_only)
+    mpc.ilqr = solver.iLQR_TF(dynamics=mpc.discrete_dynamics, cost=mpc.running_cost, cost_final=mpc.final_cost, x0=mpc.x_ref,
+                              u_init=[u.copy() for u in g["u_init"]], horizon=int(g["horizon"]), tf=None, tol=float(g["tol"]))
+    if which == "quadrotor":
+        offset = mpc.ilqr.get_state_offset()
+        offset[2] = 0.5
+        mpc.ilqr.set_state_offset(offset)
     assert isinstance(mpc.ilqr, solver.iLQR_TF)
     md = mpc.ilqr._model()
     import quattro_ilqr_amd as q
@@ -370,8 +402,7 @@ def test_the_references_own_mpc_objects_bind_to_the_dropin(which, monkeypatch):
     assert mpc.ilqr._model().integrator == "rk4"
     # a callable that does not compute what the attributes claim is refused, with the way out in the message
     mpc.Q = mpc.Q * 1.0
-    import types
-    real = cls.running_cost
+    real = _RecordedProblem.running_cost
     mpc.ilqr.L = types.MethodType(lambda self, x, u: 1.01 * real(self, x, u), mpc)     # still bound to the same object
     mpc.Qf = 2.0 * mpc.Qf                                               # (forces a new probe)
     with pytest.raises(NotImplementedError, match="compile_model"):

@@ -703,7 +703,8 @@ def test_bench_self_launch_two_ranks_share_the_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(QT_BENCH_REHEARSAL="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-                        "--batch", "512", "--clock-settle-ms", "5", "--no-extras"], env=env, capture_output=True, text=True,
+                        "--batch", "512", "--clock-settle-ms", "5", "--full", "--no-extras"], env=env, capture_output=True,
+                       text=True,
                        timeout=600)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
