@@ -1,5 +1,5 @@
 // extern "C" surface of libquattro_hip.so: argument checks + dispatch to the kernels.  See include/quattro_hip.h.
-#include "quattro_device.h"
+#include "solve_loop.h"
 
 int quattro_launch_sweep_generic(const float*, const float*, const float*, int, int, int, int, float, float*, float*,
                                  int32_t*, const int32_t*, hipStream_t);
@@ -26,13 +26,9 @@ int quattro_launch_rollout(const quattro_model_params&, const float*, const floa
 int quattro_launch_linesearch(const quattro_model_params&, float*, float*, const float*, const float*, const float*,
                               int, int, int, double, double*, int32_t*, int32_t*, int32_t*, float*, hipStream_t);
 size_t quattro_linesearch_scratch_bytes_impl(int, int, int, int);
-int quattro_launch_solve_cartpole(const quattro_model_params&, const float*, float*, float*, int, int, float, const float*, int,
-                                  double, int, int, float*, float*, double*, int32_t*, int32_t*, int32_t*, int32_t*, float*, int,
-                                  float*, float*, float*, int32_t*, const float*, const quattro_solve_log*, hipStream_t);
-int quattro_launch_solve_quad(const quattro_model_params&, const float*, float*, float*, int, int, float, const float*, int,
-                              double, int, int, float*, float*, double*, int32_t*, int32_t*, int32_t*, int32_t*, float*, float*,
-                              int, float*, float*, float*, int32_t*, const float*, unsigned long long*, int,
-                              const quattro_solve_log*, hipStream_t);
+int quattro_launch_solve_cartpole(const quattro_model_params& p, const SolveLoop& loop, hipStream_t stream);
+int quattro_launch_solve_quad(const quattro_model_params& p, const SolveLoop& loop, float* coef, unsigned long long* stamps,
+                              int stamp_rows, hipStream_t stream);
 size_t quattro_solve_log_record_bytes_impl(int, int, int, int);
 size_t quattro_solve_log_offset_impl(int, int, int, int, int);
 int quattro_launch_solve_log_record(const quattro_solve_log&, int, const float*, const float*, const float*, const float*,
@@ -41,10 +37,8 @@ int quattro_launch_solve_log_record(const quattro_solve_log&, int, const float*,
 #ifdef QT_USER_MODEL_HEADER
 int quattro_launch_sweep_rowpad_user(const float*, const float*, const float*, int, int, int, int, float, float*, float*, int32_t*,
                                      const int32_t*, hipStream_t);
-int quattro_launch_solve_user(const quattro_model_params&, const float*, float*, float*, int, int, float, const float*, int,
-                              double, int, int, float*, float*, double*, int32_t*, int32_t*, int32_t*, int32_t*, float*, float*,
-                              float*, float*, int, float*, float*, float*, int32_t*, const float*, const quattro_solve_log*,
-                              hipStream_t);
+int quattro_launch_solve_user(const quattro_model_params& p, const SolveLoop& loop, float* rec, float* VxN, float* VxxN,
+                              hipStream_t stream);
 #endif
 int quattro_launch_tf_stream(const quattro_tf_weights&, const float*, const float*, int, float*, float*, float*,
                              const int32_t*, int, int, int, hipStream_t);
@@ -265,6 +259,22 @@ WorkspacePlan plan_workspace(int n, int m, int B, int N, int layout) {
   w.total = w.scratch + ws_round(w.scratch_bytes);
   return w;
 }
+
+// The checks the iterate, solve and MPC entries share, in their order: the model, the arrays every iteration reads or
+// writes, the step sizes, then `entry_rc` (the entry's verdict on its own arguments), then the workspace, planned into *w.
+int check_solve_args(const quattro_model_params* p, const float* x_nom, const float* u_nom, int B, int N, const float* alphas,
+                     int n_alpha, const float* K, const float* k, const double* cost, const int32_t* alpha_idx,
+                     const int32_t* active, int entry_rc, const void* workspace, size_t workspace_bytes, WorkspacePlan* w) {
+  if (!model_ok(p)) return p ? QUATTRO_ERR_UNSUPPORTED : QUATTRO_ERR_BAD_ARG;
+  if (!x_nom || !u_nom || !K || !k || !alphas || !cost || !alpha_idx || !active || B <= 0 || N <= 0)
+    return QUATTRO_ERR_BAD_ARG;
+  if (n_alpha <= 0 || n_alpha > QUATTRO_MAX_ALPHAS) return QUATTRO_ERR_BAD_ARG;
+  if (entry_rc != QUATTRO_OK) return entry_rc;
+  *w = plan_workspace(p->n, p->m, B, N, quattro_model_layout(p));
+  if (!workspace || ((uintptr_t)workspace & (WS_ALIGN - 1)) != 0 || workspace_bytes < w->total)
+    return QUATTRO_ERR_WORKSPACE;
+  return QUATTRO_OK;
+}
 }  // namespace
 
 size_t quattro_workspace_bytes(int n, int m, int B, int N) {
@@ -282,19 +292,15 @@ static int quattro_ilqr_iterate_logged(const quattro_model_params* p, float* x_n
                                        const float* alphas, int n_alpha, double tol, float* K, float* k, double* cost,
                                        int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status, void* workspace,
                                        size_t workspace_bytes, const quattro_solve_log* log, int force, void* stream) {
-  if (!model_ok(p)) return p ? QUATTRO_ERR_UNSUPPORTED : QUATTRO_ERR_BAD_ARG;
-  if (!x_nom || !u_nom || !K || !k || !alphas || !cost || !alpha_idx || !active || B <= 0 || N <= 0)
-    return QUATTRO_ERR_BAD_ARG;
-  if (n_alpha <= 0 || n_alpha > QUATTRO_MAX_ALPHAS) return QUATTRO_ERR_BAD_ARG;
+  WorkspacePlan w;
+  int rc = check_solve_args(p, x_nom, u_nom, B, N, alphas, n_alpha, K, k, cost, alpha_idx, active, QUATTRO_OK, workspace,
+                            workspace_bytes, &w);
+  if (rc != QUATTRO_OK) return rc;
   const int layout = quattro_model_layout(p);
-  const WorkspacePlan w = plan_workspace(p->n, p->m, B, N, layout);
-  if (!workspace || ((uintptr_t)workspace & (WS_ALIGN - 1)) != 0 || workspace_bytes < w.total)
-    return QUATTRO_ERR_WORKSPACE;
   char* base = (char*)workspace;
   float* rec = (float*)(base + w.rec);
   float* VxN = (float*)(base + w.vx);
   float* VxxN = (float*)(base + w.vxx);
-  int rc;
   if (quattro_model_fuses_sweep(p) == 1) {
     // (RK4 quadrotor: the record area of the workspace doubles as the sweep's coefficient scratch — 528 of its 624 B per step)
     rc = quattro_linearize_sweep_f32(p, x_nom, u_nom, B, N, 0, reg, K, k, status, active, rec,
@@ -377,46 +383,67 @@ int quattro_solve_log_record_f32(const quattro_solve_log* log, int phase, const 
                                          (hipStream_t)stream);
 }
 
+namespace {
+// The loop block of a device-resident run, from the C entry's arguments (same names, same order as
+// quattro_ilqr_solve_logged_f32); an MPC run adds its own block and keeps no log
+SolveLoop solve_loop(const quattro_model_params& p, const float* x0, float* x_nom, float* u_nom, int B, int N, float reg,
+                     const float* alphas, int n_alpha, double tol, int max_iter, int flags, float* K, float* k, double* cost,
+                     int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status, const quattro_solve_log* log) {
+  SolveLoop c{};
+  c.x0 = x0;
+  c.x = x_nom;
+  c.u = u_nom;
+  c.K = K;
+  c.k = k;
+  c.cost = cost;
+  c.alpha_idx = alpha_idx;
+  c.active = active;
+  c.iters = iters;
+  c.status = status;
+  for (int i = 0; i < QUATTRO_MAX_ALPHAS; ++i) c.al.a[i] = i < n_alpha ? alphas[i] : 0.0f;
+  c.n_alpha = n_alpha;
+  c.B = B;
+  c.N = N;
+  c.max_iter = max_iter;
+  c.flags = flags & (QUATTRO_SOLVE_SIMULATE | QUATTRO_SOLVE_FIXED_ITERS | QUATTRO_SOLVE_RESET);
+  c.reg = reg;
+  c.tol = tol;
+  c.log = make_log_dev(log, p.n, p.m, N);
+  return c;
+}
+
+// the model's persistent kernel on the workspace planned in w
+int launch_device_loop(const quattro_model_params& p, SolveLoop loop, const WorkspacePlan& w, char* base, hipStream_t stream) {
+  loop.scratch = (float*)(base + w.scratch);
+#ifdef QT_USER_MODEL_HEADER
+  if (p.model_id == QUATTRO_MODEL_USER)
+    return quattro_launch_solve_user(p, loop, (float*)(base + w.rec), (float*)(base + w.vx), (float*)(base + w.vxx), stream);
+#endif
+  if (p.model_id == QUATTRO_MODEL_CARTPOLE) return quattro_launch_solve_cartpole(p, loop, stream);
+  return quattro_launch_solve_quad(p, loop, (float*)(base + w.rec), g_solve_stamps, g_solve_stamp_rows, stream);
+}
+}  // namespace
+
 int quattro_ilqr_solve_logged_f32(const quattro_model_params* p, const float* x0, float* x_nom, float* u_nom, int B, int N,
                                   float reg, const float* alphas, int n_alpha, double tol, int max_iter, int flags, float* K,
                                   float* k, double* cost, int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status,
                                   void* workspace, size_t workspace_bytes, const quattro_solve_log* log, void* stream) {
-  if (!model_ok(p)) return p ? QUATTRO_ERR_UNSUPPORTED : QUATTRO_ERR_BAD_ARG;
-  if (!x_nom || !u_nom || !K || !k || !alphas || !cost || !alpha_idx || !active || !iters || B <= 0 || N <= 0 || max_iter < 0)
-    return QUATTRO_ERR_BAD_ARG;
-  if ((flags & QUATTRO_SOLVE_SIMULATE) && !x0) return QUATTRO_ERR_BAD_ARG;
-  if (n_alpha <= 0 || n_alpha > QUATTRO_MAX_ALPHAS) return QUATTRO_ERR_BAD_ARG;
-  if (!log_ok(log)) return QUATTRO_ERR_BAD_ARG;
+  const bool args_ok = iters && max_iter >= 0 && !((flags & QUATTRO_SOLVE_SIMULATE) && !x0) && log_ok(log);
+  WorkspacePlan w;
+  int rc = check_solve_args(p, x_nom, u_nom, B, N, alphas, n_alpha, K, k, cost, alpha_idx, active,
+                            args_ok ? QUATTRO_OK : QUATTRO_ERR_BAD_ARG, workspace, workspace_bytes, &w);
+  if (rc != QUATTRO_OK) return rc;
   if (log != nullptr && log->records == nullptr) log = nullptr;
-  const int layout = quattro_model_layout(p);
-  const WorkspacePlan w = plan_workspace(p->n, p->m, B, N, layout);
-  if (!workspace || ((uintptr_t)workspace & (WS_ALIGN - 1)) != 0 || workspace_bytes < w.total)
-    return QUATTRO_ERR_WORKSPACE;
-  char* base = (char*)workspace;
   // the persistent kernel where it is the model's fastest form (1), or on request where it merely exists (2: a user model's)
   const int loop = quattro_model_has_device_loop(p);
-  const bool persistent = !(flags & QUATTRO_SOLVE_ENQUEUE) && (loop == 1 || (loop == 2 && (flags & QUATTRO_SOLVE_PERSISTENT)));
-  const int kflags = flags & (QUATTRO_SOLVE_SIMULATE | QUATTRO_SOLVE_FIXED_ITERS | QUATTRO_SOLVE_RESET);
-#ifdef QT_USER_MODEL_HEADER
-  if (persistent && p->model_id == QUATTRO_MODEL_USER)
-    return quattro_launch_solve_user(*p, x0, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, kflags, K, k, cost, alpha_idx,
-                                     active, iters, status, (float*)(base + w.rec), (float*)(base + w.vx), (float*)(base + w.vxx),
-                                     (float*)(base + w.scratch), 0, nullptr, nullptr, nullptr, nullptr, nullptr, log,
-                                     (hipStream_t)stream);
-#endif
-  if (persistent && p->model_id == QUATTRO_MODEL_CARTPOLE)
-    return quattro_launch_solve_cartpole(*p, x0, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, kflags, K, k, cost,
-                                         alpha_idx, active, iters, status, (float*)(base + w.scratch), 0, nullptr, nullptr,
-                                         nullptr, nullptr, nullptr, log, (hipStream_t)stream);
-  if (persistent && p->model_id == QUATTRO_MODEL_QUADROTOR)
-    return quattro_launch_solve_quad(*p, x0, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, kflags, K, k, cost,
-                                     alpha_idx, active, iters, status, (float*)(base + w.scratch), (float*)(base + w.rec), 0,
-                                     nullptr, nullptr, nullptr, nullptr, nullptr, g_solve_stamps, g_solve_stamp_rows, log,
-                                     (hipStream_t)stream);
+  if (!(flags & QUATTRO_SOLVE_ENQUEUE) && (loop == 1 || (loop == 2 && (flags & QUATTRO_SOLVE_PERSISTENT))))
+    return launch_device_loop(*p,
+                              solve_loop(*p, x0, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, flags, K, k, cost,
+                                         alpha_idx, active, iters, status, log),
+                              w, (char*)workspace, (hipStream_t)stream);
   // Enqueued form: the same loop as max_iter iterations of quattro_ilqr_iterate_f32.  Still no host round trip — every
   // kernel skips the trajectories whose `active` flag is down, so the iterations after the last stop are (nearly) empty
   // launches — but max_iter x 2-3 launches are issued whatever the solve needs.
-  int rc;
   hipStream_t st = (hipStream_t)stream;
   if (flags & QUATTRO_SOLVE_RESET) {
     if (hipMemsetD32Async((hipDeviceptr_t)active, 1, (size_t)B, st) != hipSuccess ||
@@ -463,32 +490,22 @@ int quattro_mpc_run_f32(const quattro_model_params* p, float* x_cur, float* x_no
                         int32_t* traj_iters, const float* disturbance, float* K, float* k, double* cost, int32_t* alpha_idx,
                         int32_t* active, int32_t* iters, int32_t* status, void* workspace, size_t workspace_bytes,
                         void* stream) {
-  if (!model_ok(p)) return p ? QUATTRO_ERR_UNSUPPORTED : QUATTRO_ERR_BAD_ARG;
-  if (!x_cur || !x_nom || !u_nom || !K || !k || !alphas || !cost || !alpha_idx || !active || !iters || !traj_x || !traj_u ||
-      !traj_iters || B <= 0 || N <= 0 || max_iter < 0 || n_steps <= 0)
-    return QUATTRO_ERR_BAD_ARG;
-  if (n_alpha <= 0 || n_alpha > QUATTRO_MAX_ALPHAS) return QUATTRO_ERR_BAD_ARG;
-  if (!quattro_model_has_device_loop(p)) return QUATTRO_ERR_UNSUPPORTED;
-  const WorkspacePlan w = plan_workspace(p->n, p->m, B, N, quattro_model_layout(p));
-  if (!workspace || ((uintptr_t)workspace & (WS_ALIGN - 1)) != 0 || workspace_bytes < w.total)
-    return QUATTRO_ERR_WORKSPACE;
-#ifdef QT_USER_MODEL_HEADER
-  if (p->model_id == QUATTRO_MODEL_USER) {
-    char* base = (char*)workspace;
-    return quattro_launch_solve_user(*p, x_cur, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, 0, K, k, cost, alpha_idx,
-                                     active, iters, status, (float*)(base + w.rec), (float*)(base + w.vx), (float*)(base + w.vxx),
-                                     (float*)(base + w.scratch), n_steps, x_cur, traj_x, traj_u, traj_iters, disturbance,
-                                     nullptr, (hipStream_t)stream);
-  }
-#endif
-  if (p->model_id == QUATTRO_MODEL_CARTPOLE)
-    return quattro_launch_solve_cartpole(*p, x_cur, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, 0, K, k, cost,
-                                         alpha_idx, active, iters, status, (float*)((char*)workspace + w.scratch), n_steps,
-                                         x_cur, traj_x, traj_u, traj_iters, disturbance, nullptr, (hipStream_t)stream);
-  return quattro_launch_solve_quad(*p, x_cur, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, 0, K, k, cost, alpha_idx,
-                                   active, iters, status, (float*)((char*)workspace + w.scratch), (float*)((char*)workspace + w.rec),
-                                   n_steps, x_cur, traj_x, traj_u, traj_iters, disturbance, g_solve_stamps, g_solve_stamp_rows,
-                                   nullptr, (hipStream_t)stream);
+  const bool args_ok = x_cur && iters && traj_x && traj_u && traj_iters && max_iter >= 0 && n_steps > 0;
+  WorkspacePlan w;
+  const int rc = check_solve_args(p, x_nom, u_nom, B, N, alphas, n_alpha, K, k, cost, alpha_idx, active,
+                                  !args_ok ? QUATTRO_ERR_BAD_ARG
+                                           : (quattro_model_has_device_loop(p) ? QUATTRO_OK : QUATTRO_ERR_UNSUPPORTED),
+                                  workspace, workspace_bytes, &w);
+  if (rc != QUATTRO_OK) return rc;
+  SolveLoop loop = solve_loop(*p, x_cur, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, 0, K, k, cost, alpha_idx,
+                              active, iters, status, nullptr);
+  loop.n_ctrl = n_steps;
+  loop.x_cur = x_cur;
+  loop.traj_x = traj_x;
+  loop.traj_u = traj_u;
+  loop.traj_iters = traj_iters;
+  loop.disturbance = disturbance;
+  return launch_device_loop(*p, loop, w, (char*)workspace, (hipStream_t)stream);
 }
 
 namespace {

@@ -163,6 +163,13 @@ struct Tile16RRec {
   static QT_HD int lu(int a_) { return LZ + 12 + a_; }
 };
 
+// the step sizes of a line search, by value (a kernel argument)
+namespace {
+struct AlphaList {
+  float a[QUATTRO_MAX_ALPHAS];
+};
+}  // namespace
+
 // ----------------------------------------------------------------------------------------------
 // wave helpers
 // ----------------------------------------------------------------------------------------------

@@ -5,10 +5,6 @@
 
 namespace {
 
-struct AlphaList {
-  float a[QUATTRO_MAX_ALPHAS];
-};
-
 template <int N>
 __device__ __forceinline__ void load_vec(const float* __restrict__ p, float* dst) {
   if constexpr (N % 4 == 0) {

@@ -6,10 +6,6 @@
 
 namespace {
 
-struct AlphaList {
-  float a[QUATTRO_MAX_ALPHAS];
-};
-
 constexpr int NX = 12, NU = 4, CS = 16;   // candidate record: x'_{t+1} (12) | u'_t (4)
 
 // Diagnostic build only (-DQT_ABLATE_LS=n, scripts/ablate_linesearch.sh): one segment of a rollout step is left out (wrong numbers

@@ -13,173 +13,63 @@
 // chains and nothing else — no launch, no kernel boundary, no host call.
 #include "cartpole_body.h"
 #include "rollout_body.h"
-#include "solve_log.h"
+#include "solve_loop.h"
 
 namespace {
 
 struct CpSolveArgs {
   quattro_model_params p;
-  const float* x0;      // [B][4]  (MPC: the controllers' current states, == x_cur)
-  float* x;             // [B][N+1][4]
-  float* u;             // [B][N][1]
-  float* K;             // [B][N][1][4]
-  float* k;             // [B][N][1]
-  double* cost;
-  int32_t* alpha_idx;
-  int32_t* active;
-  int32_t* iters;
-  int32_t* status;      // may be NULL
-  float* scratch;
-  AlphaList al;
-  int n_alpha, B, N, max_iter, flags;
-  float reg;
-  double tol;
-  int n_ctrl;
-  float* x_cur;
-  float* traj_x;              // [B][n_ctrl+1][4]
-  float* traj_u;              // [B][n_ctrl][1]
-  int32_t* traj_iters;        // [B][n_ctrl]
-  const float* disturbance;   // [n_ctrl][B][4] or NULL
-  SolveLogDev log;            // per-iteration log ring (rec == nullptr: none); plain solves only (n_ctrl == 0)
+  SolveLoop c;          // x [B][N+1][4], u [B][N][1], K [B][N][1][4], k [B][N][1]
 };
-
-constexpr int CP_FLAG_SIMULATE = 1, CP_FLAG_FIXED = 2, CP_FLAG_RESET = 4;
-
-// every store of this wave has completed before its lanes read what other lanes of the wave wrote (the phases of the loop hand
-// trajectories over through global memory)
-__device__ __forceinline__ void wave_handoff() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 
 template <bool RK4>
 __global__ __launch_bounds__(QT_WAVE) void solve_cartpole_kernel(const CpSolveArgs a) {
   constexpr int MODEL = QUATTRO_MODEL_CARTPOLE, NX = 4;
   __shared__ __attribute__((aligned(16))) float s_stage[4 * cp16::STAGE_FLOATS];
+  const SolveLoop& c = a.c;
   const int lane = threadIdx.x;
   const int sub = lane & 15;
   const int b = blockIdx.x * 4 + (lane >> 4);
-  const bool have = b < a.B;
+  const bool have = b < c.B;
   const size_t bb = have ? b : 0;
-  const bool force = (a.flags & CP_FLAG_FIXED) != 0;
-  const int N = a.N;
+  const bool force = (c.flags & QUATTRO_SOLVE_FIXED_ITERS) != 0;
+  const int N = c.N;
   float* stage = s_stage + (lane >> 4) * cp16::STAGE_FLOATS;
-  const int n_ctrl = a.n_ctrl > 0 ? a.n_ctrl : 1;
+  const int n_ctrl = c.n_ctrl > 0 ? c.n_ctrl : 1;
   for (int cs = 0; cs < n_ctrl; ++cs) {
-    if ((a.flags & (CP_FLAG_SIMULATE | CP_FLAG_RESET)) != 0 || a.n_ctrl > 0) {
-      if (have && sub == 0) {
-        if (a.n_ctrl > 0 && cs == 0) {
-#pragma unroll
-          for (int i = 0; i < NX; ++i) a.traj_x[(bb * (a.n_ctrl + 1)) * NX + i] = a.x0[bb * NX + i];
-        }
-        if (a.n_ctrl > 0 || (a.flags & CP_FLAG_RESET) != 0) {
-          a.iters[bb] = 0;          // per-solve state of this control step (what a host caller resets before a solve)
-          a.active[bb] = 1;
-          a.alpha_idx[bb] = -1;
-          if (a.status != nullptr) a.status[bb] = 0;
-        }
-        if ((a.flags & CP_FLAG_SIMULATE) != 0 || a.n_ctrl > 0) simulate_body<MODEL, RK4>(a.p, a.x0, a.u, N, a.x, a.cost, b);
-      }
-      wave_handoff();
-    }
-    const bool logging = a.log.rec != nullptr && a.n_ctrl == 0;
-    for (int it = 0; it < a.max_iter; ++it) {
-      const bool act = have && (force || a.active[bb] != 0);
+    wave_step_prologue<NX>(c, bb, cs, have && sub == 0,
+                           [&] { simulate_body<MODEL, RK4>(a.p, c.x0, c.u, N, c.x, c.cost, b); });
+    const bool logging = c.log.rec != nullptr && c.n_ctrl == 0;
+    for (int it = 0; it < c.max_iter; ++it) {
+      const bool act = have && (force || c.active[bb] != 0);
       if (!__any(act)) break;
       int log_it = 0;
       if (logging && act) {      // the record of this iteration: nominal, cost, start stamp (the row's 16 lanes)
-        log_it = a.iters[bb];
-        log_begin(a.log, b, log_it, a.x + bb * (N + 1) * NX, a.u + bb * N, a.cost[bb], sub, 16);
+        log_it = c.iters[bb];
+        log_begin(c.log, b, log_it, c.x + bb * (N + 1) * NX, c.u + bb * N, c.cost[bb], sub, 16);
       }
-      sweep16_cartpole_body<RK4>(a.p, a.x, a.u, N, 0, a.reg, a.K, a.k, a.status, b, act, lane, stage);
-      if (logging && act && sub == 0) log_stamp(a.log, b, log_it, 1, 2);
+      sweep16_cartpole_body<RK4>(a.p, c.x, c.u, N, 0, c.reg, c.K, c.k, c.status, b, act, lane, stage);
+      if (logging && act && sub == 0) log_stamp(c.log, b, log_it, 1, 2);
       wave_handoff();
-      linesearch_body<MODEL, RK4, 16>(a.p, a.x, a.u, a.K, a.k, a.al, a.n_alpha, a.B, N, a.tol, a.cost, a.alpha_idx, a.active,
-                                      a.iters, a.scratch, 16 * b + sub, force);
+      linesearch_body<MODEL, RK4, 16>(a.p, c.x, c.u, c.K, c.k, c.al, c.n_alpha, c.B, N, c.tol, c.cost, c.alpha_idx, c.active,
+                                      c.iters, c.scratch, 16 * b + sub, force);
       wave_handoff();
       if (logging && act)        // gains, accepted step, cost after the iteration, end stamp
-        log_end(a.log, b, log_it, a.K + bb * N * NX, a.k + bb * N, a.alpha_idx[bb], a.cost[bb], sub, 16);
+        log_end(c.log, b, log_it, c.K + bb * N * NX, c.k + bb * N, c.alpha_idx[bb], c.cost[bb], sub, 16);
     }
-    if (a.n_ctrl > 0) {
-      // apply u_0 to the plant (the device model itself), record, shift the warm start: CartPoleMPC._ilqr_step after
-      // optimize() (cartpole_mpc.py:331) and the simulator's step around it
-      float u_next[4];
-      const int tot = N - 1;                                   // u <- (u_1 .. u_{N-1}, u_{N-1}); 16 lanes x 4 cover N <= 65
-      for (int base = 0; base < tot || base == 0; base += 64) {     // (at least once: the plant step below rides on the first pass, also when N = 1 and nothing shifts)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int e = base + sub + 16 * q;
-          u_next[q] = (have && e < tot) ? a.u[bb * N + e + 1] : 0.0f;
-        }
-        float u0 = 0.0f;
-        if (base == 0 && have && sub == 0) u0 = a.u[bb * N];
-        wave_handoff();                                        // every element is read before any is written
-        if (base == 0 && have && sub == 0) {
-          float xo[NX], xn[NX];
-#pragma unroll
-          for (int i = 0; i < NX; ++i) xo[i] = a.x_cur[bb * NX + i];
-          const float us[1] = {u0};
-          qt_step<MODEL, RK4>(a.p, xo, us, xn);
-          if (a.disturbance != nullptr) {
-#pragma unroll
-            for (int i = 0; i < NX; ++i) xn[i] += a.disturbance[((size_t)cs * a.B + bb) * NX + i];
-          }
-          a.traj_u[bb * a.n_ctrl + cs] = u0;
-          a.traj_iters[bb * a.n_ctrl + cs] = a.iters[bb];
-#pragma unroll
-          for (int i = 0; i < NX; ++i) {
-            a.x_cur[bb * NX + i] = xn[i];
-            a.traj_x[(bb * (a.n_ctrl + 1) + cs + 1) * NX + i] = xn[i];
-          }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int e = base + sub + 16 * q;
-          if (have && e < tot) a.u[bb * N + e] = u_next[q];
-        }
-      }
-      wave_handoff();
-    }
+    // apply u_0, record, shift the warm start: CartPoleMPC._ilqr_step after optimize() (cartpole_mpc.py:331) and the
+    // simulator's step around it
+    if (c.n_ctrl > 0)
+      wave_mpc_epilogue<NX, 1, 16>(c, bb, cs, sub, have,
+                                   [&](const float* xo, const float* u0, float* xn) { qt_step<MODEL, RK4>(a.p, xo, u0, xn); });
   }
 }
 
 }  // namespace
 
-int quattro_launch_solve_cartpole(const quattro_model_params& p, const float* x0, float* x, float* u, int B, int N, float reg,
-                                  const float* alphas, int n_alpha, double tol, int max_iter, int flags, float* K, float* k,
-                                  double* cost, int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status,
-                                  float* scratch, int n_ctrl, float* x_cur, float* traj_x, float* traj_u, int32_t* traj_iters,
-                                  const float* disturbance, const quattro_solve_log* log, hipStream_t stream) {
-  CpSolveArgs a;
-  a.p = p;
-  a.x0 = n_ctrl > 0 ? x_cur : x0;
-  a.x = x;
-  a.u = u;
-  a.K = K;
-  a.k = k;
-  a.cost = cost;
-  a.alpha_idx = alpha_idx;
-  a.active = active;
-  a.iters = iters;
-  a.status = status;
-  a.scratch = scratch;
-  for (int i = 0; i < QUATTRO_MAX_ALPHAS; ++i) a.al.a[i] = i < n_alpha ? alphas[i] : 0.0f;
-  a.n_alpha = n_alpha;
-  a.B = B;
-  a.N = N;
-  a.max_iter = max_iter;
-  a.flags = flags;
-  a.reg = reg;
-  a.tol = tol;
-  a.n_ctrl = n_ctrl;
-  a.x_cur = x_cur;
-  a.traj_x = traj_x;
-  a.traj_u = traj_u;
-  a.traj_iters = traj_iters;
-  a.disturbance = disturbance;
-  a.log = make_log_dev(n_ctrl > 0 ? nullptr : log, 4, 1, N);
-  const dim3 grid((unsigned)((B + 3) / 4));
+int quattro_launch_solve_cartpole(const quattro_model_params& p, const SolveLoop& c, hipStream_t stream) {
+  const CpSolveArgs a{p, c};
+  const dim3 grid((unsigned)((c.B + 3) / 4));
   if (p.integrator == QUATTRO_INTEGRATOR_EULER)
     hipLaunchKernelGGL((solve_cartpole_kernel<false>), grid, dim3(QT_WAVE), 0, stream, a);
   else if (p.integrator == QUATTRO_INTEGRATOR_RK4)

@@ -1,0 +1,119 @@
+// What the three device-resident solve loops share (solve_quad.hip, solve_cartpole.hip, solve_user.hip): the block of loop
+// arguments every one of them takes, filled on the host by capi.hip from the C entry's arguments, and the wave-private pieces
+// of the control step that the cart-pole and user-model loops run alike.  The quadrotor's two-wave workgroup loop has a lane
+// mapping of its own and keeps its prologue and MPC step in solve_quad.hip.
+#pragma once
+#include "solve_log.h"
+
+// (outside the anonymous namespace: the kernel launchers take it from capi.hip)
+struct SolveLoop {
+  const float* x0;      // [B][n]  states the rollouts start from (MPC: the controllers' current states, == x_cur)
+  float* x;             // [B][N+1][n]  nominal, in/out
+  float* u;             // [B][N][m]
+  float* K;             // [B][N][m][n]
+  float* k;             // [B][N][m]
+  double* cost;         // [B]
+  int32_t* alpha_idx;   // [B]
+  int32_t* active;      // [B]
+  int32_t* iters;       // [B]
+  int32_t* status;      // [B] (may be NULL)
+  float* scratch;       // line-search candidates
+  AlphaList al;
+  int n_alpha, B, N, max_iter, flags;   // flags: QUATTRO_SOLVE_SIMULATE | QUATTRO_SOLVE_FIXED_ITERS | QUATTRO_SOLVE_RESET
+  float reg;
+  double tol;
+  // receding-horizon mode (n_ctrl > 0)
+  int n_ctrl;
+  float* x_cur;               // [B][n]  == x0 (writable)
+  float* traj_x;              // [B][n_ctrl+1][n]
+  float* traj_u;              // [B][n_ctrl][m]
+  int32_t* traj_iters;        // [B][n_ctrl]
+  const float* disturbance;   // [n_ctrl][B][n] or NULL
+  SolveLogDev log;            // per-iteration log ring (rec == nullptr: none); plain solves only (n_ctrl == 0)
+};
+
+namespace {
+
+// every store of this wave has completed before its lanes read what other lanes of the wave wrote (the phases of a
+// wave-private loop hand trajectories over through global memory)
+__device__ __forceinline__ void wave_handoff() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// Top of control step cs of a wave-private loop: the lane that leads trajectory bb (lead) records its start state (MPC),
+// resets the per-solve state (what a host caller resets before a solve; after the last control step it stays as that solve
+// left it) and rolls the nominal out from x0 (simulate(): the model's rollout body, run by that lane alone).
+template <int NX, class Simulate>
+__device__ __forceinline__ void wave_step_prologue(const SolveLoop& c, const size_t bb, const int cs, const bool lead,
+                                                   Simulate simulate) {
+  if ((c.flags & (QUATTRO_SOLVE_SIMULATE | QUATTRO_SOLVE_RESET)) == 0 && c.n_ctrl == 0) return;
+  if (lead) {
+    if (c.n_ctrl > 0 && cs == 0) {
+#pragma unroll
+      for (int i = 0; i < NX; ++i) c.traj_x[(bb * (c.n_ctrl + 1)) * NX + i] = c.x0[bb * NX + i];
+    }
+    if (c.n_ctrl > 0 || (c.flags & QUATTRO_SOLVE_RESET) != 0) {
+      c.iters[bb] = 0;
+      c.active[bb] = 1;
+      c.alpha_idx[bb] = -1;
+      if (c.status != nullptr) c.status[bb] = 0;
+    }
+    if ((c.flags & QUATTRO_SOLVE_SIMULATE) != 0 || c.n_ctrl > 0) simulate();
+  }
+  wave_handoff();
+}
+
+// End of MPC control step cs of a wave-private loop, W lanes per trajectory (l: lane in the group, have: the group has a
+// trajectory): apply u_0 to the plant (step(x, u, x_next): the device model itself), add the disturbance, record, and shift the
+// warm start u <- (u_1 .. u_{N-1}, u_{N-1}) in passes of a wave's worth of elements.  Every element of a pass is read before
+// any is written.
+template <int NX, int NU, int W, class Step>
+__device__ __forceinline__ void wave_mpc_epilogue(const SolveLoop& c, const size_t bb, const int cs, const int l, const bool have,
+                                                  Step step) {
+  constexpr int PER = QT_WAVE / W;                             // elements a lane moves per pass
+  float* ub = c.u + bb * c.N * NU;
+  const int tot = (c.N - 1) * NU;                              // elements that move
+  const bool lead = have && l == 0;
+  for (int base = 0; base < tot || base == 0; base += W * PER) {    // (at least once: the plant step below rides on the first pass, also when N = 1 and nothing shifts)
+    float v[PER];
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+      const int e = base + l + W * q;
+      v[q] = (have && e < tot) ? ub[e + NU] : 0.0f;
+    }
+    float u0[NU] = {};
+    if (base == 0 && lead) {
+#pragma unroll
+      for (int q = 0; q < NU; ++q) u0[q] = ub[q];
+    }
+    wave_handoff();                                            // every element of the pass is read before any is written
+    if (base == 0 && lead) {
+      float xo[NX], xn[NX];
+#pragma unroll
+      for (int i = 0; i < NX; ++i) xo[i] = c.x_cur[bb * NX + i];
+      step(xo, u0, xn);
+      if (c.disturbance != nullptr) {
+#pragma unroll
+        for (int i = 0; i < NX; ++i) xn[i] += c.disturbance[((size_t)cs * c.B + bb) * NX + i];
+      }
+#pragma unroll
+      for (int q = 0; q < NU; ++q) c.traj_u[(bb * c.n_ctrl + cs) * NU + q] = u0[q];
+      c.traj_iters[bb * c.n_ctrl + cs] = c.iters[bb];
+#pragma unroll
+      for (int i = 0; i < NX; ++i) {
+        c.x_cur[bb * NX + i] = xn[i];
+        c.traj_x[(bb * (c.n_ctrl + 1) + cs + 1) * NX + i] = xn[i];
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < PER; ++q) {
+      const int e = base + l + W * q;
+      if (have && e < tot) ub[e] = v[q];
+    }
+  }
+  wave_handoff();
+}
+
+}  // namespace

@@ -25,11 +25,7 @@
 // workgroup a moment ago and come from L2), which keeps the whole loop inside the sweep's 128-register budget: 4 waves
 // per SIMD, i.e. B = 4096 resident at once.
 #include "rollout_quad_body.h"
-#include "solve_log.h"
-
-#ifndef QT_SOLVE_LS_PRIO
-#define QT_SOLVE_LS_PRIO 3
-#endif
+#include "solve_loop.h"
 #include "sweep_tile16_body.h"
 
 namespace {
@@ -37,47 +33,28 @@ namespace {
 struct SolveArgs {
   FusedArgs fa;         // model parameters + nominal (x [B][N+1][12], u [B][N][4], in/out) as the sweep body takes them: kept
                         // inside the kernel-argument block (a private copy with lane-dependent indexing would live in scratch)
-  const float* x0;      // [B][12]  states the rollouts start from (MPC: the controllers' current states, updated in place)
-  float* x;             // == fa.x, writable
-  float* u;             // == fa.u, writable
-  float* K;             // [B][N][4][12]
-  float* k;             // [B][N][4]
-  double* cost;         // [B]
-  int32_t* alpha_idx;   // [B]
-  int32_t* active;      // [B]
-  int32_t* iters;       // [B]
-  int32_t* status;      // [B] (may be NULL)
-  float* scratch;       // line-search candidates
-  AlphaList al;
-  int n_alpha, B, N, max_iter, flags;
-  float reg;
-  double tol;
-  // receding-horizon mode (n_ctrl > 0)
-  int n_ctrl;
-  float* x_cur;               // [B][12]  == x0 (writable)
-  float* traj_x;              // [B][n_ctrl+1][12]
-  float* traj_u;              // [B][n_ctrl][4]
-  int32_t* traj_iters;        // [B][n_ctrl]
-  const float* disturbance;   // [n_ctrl][B][12] or NULL
+  SolveLoop c;          // c.x == fa.x, c.u == fa.u (writable); K [B][N][4][12], k [B][N][4]
   unsigned long long* stamps; // diagnostics (may be NULL): [workgroup][2 * (n_ctrl + 1) + 2] = (s_memrealtime at the start / after
                               // each control step, iterations the workgroup ran in that step; wave 1's exit stamp and loop
                               // passes in the last two slots); 100 MHz ticks
   int stamp_rows;             // workgroups the stamps buffer has rows for (others do not stamp)
-  SolveLogDev log;            // per-iteration log ring (rec == nullptr: none); plain solves only (n_ctrl == 0)
 };
 
-constexpr int FLAG_SIMULATE = 1, FLAG_FIXED = 2, FLAG_RESET = 4;
+// the line-search wave above every phase of the sweeps it shares its SIMD with — other workgroups': it is the one wave of two
+// that works in this phase, and its partner waits for it (91.2 -> 85.5 us per iteration at B = 4096; 1 / 2: 86.3 / 87.3)
+constexpr int LS_PRIO = 3;
 
 // apply u_0 to the plant (the device model itself), record, shift the warm start, reset the per-solve state: what
 // QuadrotorMPC.control_step does after optimize() (quadrotor_mpc.py:121-122) plus the simulator's step around it.
 // Run by wave 0: quad q = lane >> 2 < 2 owns trajectory b0 + q for the plant step; the shift is spread over 32 lanes per
 // trajectory.
 template <bool RK4>
-__device__ __forceinline__ void mpc_advance(const SolveArgs& a, const int b0, const int lane, const int cs) {
+__device__ __forceinline__ void mpc_advance(const SolveArgs& args, const int b0, const int lane, const int cs) {
+  const SolveLoop& a = args.c;
   const int q = lane >> 2, tb = b0 + q;
   const bool live = lane < 8 && tb < a.B;
   const size_t bb = live ? tb : 0;
-  const LaneConst L = lane_const(a.fa.p, lane & 3);
+  const LaneConst L = lane_const(args.fa.p, lane & 3);
   const int N = a.N;
   float xo[4], xn[4];
 #pragma unroll
@@ -138,8 +115,6 @@ __device__ __forceinline__ const SolveArgs& fresh_args(KernArgPtr base) {
   return *(const SolveArgs*)base;
 }
 
-__device__ __forceinline__ bool c_dummy_never(const float* pp) { return pp == nullptr; }
-
 // Workgroup barrier that hands GLOBAL-memory data from one wave to the other.  __syncthreads() alone is not enough here: for
 // a workgroup-scope release on gfx950 (waves of a workgroup share their CU's L1) the compiler emits `s_waitcnt lgkmcnt(0)`
 // only — no vmcnt(0) — on the premise that the CU performs its vector-memory operations in order.  Across two WAVES that
@@ -164,32 +139,26 @@ __global__ __launch_bounds__(128, 4) void solve_quad_kernel(const SolveArgs) {
   constexpr int SWEEP_MODE = RK4 ? MODE_FUSED_RK4 : MODE_FUSED;
   constexpr int LIN_FLOATS = sweep_lin_floats<SWEEP_MODE>();
   __shared__ __attribute__((aligned(16))) float s_lin_all[2 * LIN_FLOATS];
-#ifdef QT_SOLVE_LDS_PAD
-  __shared__ float s_pad[QT_SOLVE_LDS_PAD];          // experiment: caps the workgroups per CU
-  {
-    float* pp = s_pad;
-    asm volatile("" : "+v"(pp));
-    if (c_dummy_never(pp)) pp[threadIdx.x] = 0.0f;
-  }
-#endif
 
-  const SolveArgs& c = *(const SolveArgs*)kap;     // loop control only (a handful of scalars)
+  const SolveArgs& ka = *(const SolveArgs*)kap;    // loop control only (a handful of scalars)
+  const SolveLoop& c = ka.c;
   const bool have = b < c.B;
-  const bool force = (c.flags & FLAG_FIXED) != 0;
+  const bool force = (c.flags & QUATTRO_SOLVE_FIXED_ITERS) != 0;
   const int n_ctrl = c.n_ctrl > 0 ? c.n_ctrl : 1;
-  const bool stamping = c.stamps != nullptr && (int)blockIdx.x < c.stamp_rows;
-  if (stamping && threadIdx.x == 0) c.stamps[(size_t)blockIdx.x * (2 * (n_ctrl + 1) + 2)] = __builtin_amdgcn_s_memrealtime();
+  const bool stamping = ka.stamps != nullptr && (int)blockIdx.x < ka.stamp_rows;
+  if (stamping && threadIdx.x == 0) ka.stamps[(size_t)blockIdx.x * (2 * (n_ctrl + 1) + 2)] = __builtin_amdgcn_s_memrealtime();
   const bool logging = c.log.rec != nullptr && c.n_ctrl == 0;
   int total_passes = 0;
   for (int cs = 0; cs < n_ctrl; ++cs) {
     int wg_iters = 0;
-    if ((c.flags & (FLAG_SIMULATE | FLAG_RESET)) != 0 || c.n_ctrl > 0) {
+    if ((c.flags & (QUATTRO_SOLVE_SIMULATE | QUATTRO_SOLVE_RESET)) != 0 || c.n_ctrl > 0) {
       // nominal rollout + cost from the current state (simulate :127-132, compute_total_cost :138-143): quads 0 and 1 of wave 0
       if (wv == 0) {
-        const SolveArgs& a = fresh_args(kap);
+        const SolveArgs& args = fresh_args(kap);
+        const SolveLoop& a = args.c;
         int ln = lane;
         asm volatile("" : "+v"(ln));
-        if ((a.n_ctrl > 0 || (a.flags & FLAG_RESET) != 0) && ln < 8 && b0 + (ln >> 2) < a.B) {
+        if ((a.n_ctrl > 0 || (a.flags & QUATTRO_SOLVE_RESET) != 0) && ln < 8 && b0 + (ln >> 2) < a.B) {
           const size_t tb = b0 + (ln >> 2);
           if (a.n_ctrl > 0 && cs == 0 && (ln & 3) < 3) {
 #pragma unroll
@@ -203,8 +172,8 @@ __global__ __launch_bounds__(128, 4) void solve_quad_kernel(const SolveArgs) {
             if (a.status != nullptr) a.status[tb] = 0;
           }
         }
-        if ((a.flags & FLAG_SIMULATE) != 0 || a.n_ctrl > 0)
-          simulate_quad_body<RK4>(a.fa.p, a.x0, a.u, a.N, a.x, a.cost, 4 * b0 + ln, ln < 8 && b0 + (ln >> 2) < a.B);
+        if ((a.flags & QUATTRO_SOLVE_SIMULATE) != 0 || a.n_ctrl > 0)
+          simulate_quad_body<RK4>(args.fa.p, a.x0, a.u, a.N, a.x, a.cost, 4 * b0 + ln, ln < 8 && b0 + (ln >> 2) < a.B);
       }
       wg_sync();
     }
@@ -220,35 +189,35 @@ __global__ __launch_bounds__(128, 4) void solve_quad_kernel(const SolveArgs) {
       const bool mine = have && (wv == 0 ? act0 : act1);
       int log_it = 0;
       if (logging && mine) {     // the record of this iteration: nominal, cost, start stamp (this wave's own trajectory)
-        const SolveArgs& a = fresh_args(kap);
+        const SolveLoop& a = fresh_args(kap).c;
         int ln = lane;
         asm volatile("" : "+v"(ln));
         log_it = __hip_atomic_load(a.iters + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         log_begin(a.log, b, log_it, a.x + (size_t)b * (a.N + 1) * NX, a.u + (size_t)b * a.N * NU, a.cost[b], ln, 64);
       }
       if (mine) {
-        const SolveArgs& a = fresh_args(kap);
+        const SolveArgs& args = fresh_args(kap);
+        const SolveLoop& a = args.c;
         int ln = lane;
         asm volatile("" : "+v"(ln));
-        sweep_tile16_body<SWEEP_MODE>(nullptr, nullptr, nullptr, a.N, a.reg, a.K, a.k, a.status, a.fa, b, ln,
+        sweep_tile16_body<SWEEP_MODE>(nullptr, nullptr, nullptr, a.N, a.reg, a.K, a.k, a.status, args.fa, b, ln,
                                       s_t_all + wv * 16 * LD, s_vx_all + wv * 64, s_lin_all + wv * LIN_FLOATS);
       }
-      if (logging && mine && lane == 0) log_stamp(fresh_args(kap).log, b, log_it, 1, 2);
+      if (logging && mine && lane == 0) log_stamp(fresh_args(kap).c.log, b, log_it, 1, 2);
       wg_sync();
       if (wv == 0) {
-        const SolveArgs& a = fresh_args(kap);
+        const SolveArgs& args = fresh_args(kap);
+        const SolveLoop& a = args.c;
         int ln = lane;
         asm volatile("" : "+v"(ln));
-        // (the line-search wave above every phase of the sweeps it shares its SIMD with — other workgroups': it is the one wave of
-        //  two that works in this phase, and its partner waits for it: 91.2 -> 85.5 us per iteration at B = 4096; 1 / 2: 86.3 / 87.3)
-        __builtin_amdgcn_s_setprio(QT_SOLVE_LS_PRIO);
-        linesearch_quad_body<RK4, 2>(a.fa.p, a.x, a.u, a.K, a.k, a.al, a.n_alpha, a.B, a.N, a.tol, a.cost, a.alpha_idx, a.active,
+        __builtin_amdgcn_s_setprio(LS_PRIO);
+        linesearch_quad_body<RK4, 2>(args.fa.p, a.x, a.u, a.K, a.k, a.al, a.n_alpha, a.B, a.N, a.tol, a.cost, a.alpha_idx, a.active,
                                      a.iters, a.scratch, 32 * b0 + ln, force);
         __builtin_amdgcn_s_setprio(0);
       }
       wg_sync();
       if (logging && mine) {     // gains, accepted step, cost after the iteration, end stamp
-        const SolveArgs& a = fresh_args(kap);
+        const SolveLoop& a = fresh_args(kap).c;
         int ln = lane;
         asm volatile("" : "+v"(ln));
         const int ai = __hip_atomic_load(a.alpha_idx + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -262,15 +231,15 @@ __global__ __launch_bounds__(128, 4) void solve_quad_kernel(const SolveArgs) {
       // passes after wave 0 had left the kernel).
       wg_sync();
       if (wv == 0) {
-        const SolveArgs& a = fresh_args(kap);
+        const SolveArgs& args = fresh_args(kap);
         int ln = lane;
         asm volatile("" : "+v"(ln));
-        mpc_advance<RK4>(a, b0, ln, cs);
+        mpc_advance<RK4>(args, b0, ln, cs);
       }
       wg_sync();
     }
     if (stamping && threadIdx.x == 0) {
-      unsigned long long* st = c.stamps + (size_t)blockIdx.x * (2 * (n_ctrl + 1) + 2);
+      unsigned long long* st = ka.stamps + (size_t)blockIdx.x * (2 * (n_ctrl + 1) + 2);
       st[2 * (cs + 1)] = __builtin_amdgcn_s_memrealtime();
       st[2 * (cs + 1) + 1] = (unsigned long long)wg_iters;
     }
@@ -278,7 +247,7 @@ __global__ __launch_bounds__(128, 4) void solve_quad_kernel(const SolveArgs) {
   // slot 1: s_memrealtime at which wave 0 left the kernel; the two extra slots at the end of the row: the same for wave 1 and
   // the total number of loop passes wave 1 made
   if (stamping && lane == 0) {
-    unsigned long long* st = c.stamps + (size_t)blockIdx.x * (2 * (n_ctrl + 1) + 2);
+    unsigned long long* st = ka.stamps + (size_t)blockIdx.x * (2 * (n_ctrl + 1) + 2);
     if (wv == 0) {
       st[1] = __builtin_amdgcn_s_memrealtime();
     } else {
@@ -290,58 +259,28 @@ __global__ __launch_bounds__(128, 4) void solve_quad_kernel(const SolveArgs) {
 
 }  // namespace
 
-// flags: bit 0 = roll the nominal out from x0 first; bit 1 = fixed iteration count (stop flags ignored); bit 2 = reset the
-// per-solve state (active, iters, alpha_idx, status) first
-int quattro_launch_solve_quad(const quattro_model_params& p, const float* x0, float* x, float* u, int B, int N, float reg,
-                              const float* alphas, int n_alpha, double tol, int max_iter, int flags, float* K, float* k,
-                              double* cost, int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status,
-                              float* scratch, float* coef, int n_ctrl, float* x_cur, float* traj_x, float* traj_u,
-                              int32_t* traj_iters, const float* disturbance, unsigned long long* stamps, int stamp_rows,
-                              const quattro_solve_log* log, hipStream_t stream) {
+int quattro_launch_solve_quad(const quattro_model_params& p, const SolveLoop& c, float* coef, unsigned long long* stamps,
+                              int stamp_rows, hipStream_t stream) {
   if (p.integrator != QUATTRO_INTEGRATOR_EULER && p.integrator != QUATTRO_INTEGRATOR_RK4) return QUATTRO_ERR_UNSUPPORTED;
   if (p.integrator == QUATTRO_INTEGRATOR_RK4 && coef == nullptr) return QUATTRO_ERR_WORKSPACE;
   SolveArgs a;
   a.fa.p = p;
-  a.fa.x = x;
-  a.fa.u = u;
-  a.fa.N = N;
+  a.fa.x = c.x;
+  a.fa.u = c.u;
+  a.fa.N = c.N;
   a.fa.t_start = 0;
-  a.fa.B = B;
+  a.fa.B = c.B;
   a.fa.coef = coef;     // RK4: the sweep's coefficient scratch, B * N * 132 floats
   a.fa.k_rows = 0;
   a.fa.rn = 12;
   a.fa.rm = 4;
-  a.x0 = n_ctrl > 0 ? x_cur : x0;
-  a.x = x;
-  a.u = u;
-  a.K = K;
-  a.k = k;
-  a.cost = cost;
-  a.alpha_idx = alpha_idx;
-  a.active = active;
-  a.iters = iters;
-  a.status = status;
-  a.scratch = scratch;
-  for (int i = 0; i < QUATTRO_MAX_ALPHAS; ++i) a.al.a[i] = i < n_alpha ? alphas[i] : 0.0f;
-  a.n_alpha = n_alpha;
-  a.B = B;
-  a.N = N;
-  a.max_iter = max_iter;
-  a.flags = flags;
-  a.reg = reg;
-  a.tol = tol;
-  a.n_ctrl = n_ctrl;
-  a.x_cur = x_cur;
-  a.traj_x = traj_x;
-  a.traj_u = traj_u;
-  a.traj_iters = traj_iters;
-  a.disturbance = disturbance;
+  a.c = c;
   a.stamps = stamps;
   a.stamp_rows = stamp_rows;
-  a.log = make_log_dev(n_ctrl > 0 ? nullptr : log, 12, 4, N);
+  const dim3 grid((unsigned)((c.B + 1) / 2));
   if (p.integrator == QUATTRO_INTEGRATOR_RK4)
-    hipLaunchKernelGGL((solve_quad_kernel<true>), dim3((unsigned)((B + 1) / 2)), dim3(128), 0, stream, a);
+    hipLaunchKernelGGL((solve_quad_kernel<true>), grid, dim3(128), 0, stream, a);
   else
-    hipLaunchKernelGGL((solve_quad_kernel<false>), dim3((unsigned)((B + 1) / 2)), dim3(128), 0, stream, a);
+    hipLaunchKernelGGL((solve_quad_kernel<false>), grid, dim3(128), 0, stream, a);
   return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;
 }

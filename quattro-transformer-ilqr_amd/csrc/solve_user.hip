@@ -17,7 +17,7 @@
 #error "solve_user.hip is part of a user model's library"
 #endif
 #include "rollout_body.h"
-#include "solve_log.h"
+#include "solve_loop.h"
 #include "sweep_generic_body.h"
 #include "sweep_tile16_body.h"
 #include "user_linearize.h"
@@ -26,41 +26,11 @@ namespace {
 
 struct UserSolveArgs {
   quattro_model_params p;
-  const float* x0;      // [B][n]  (MPC: the controllers' current states, == x_cur)
-  float* x;             // [B][N+1][n]
-  float* u;             // [B][N][m]
-  float* K;             // [B][N][m][n]
-  float* k;             // [B][N][m]
-  double* cost;
-  int32_t* alpha_idx;
-  int32_t* active;
-  int32_t* iters;
-  int32_t* status;      // may be NULL
   float* rec;           // [B][N][RowMajorRec stride]
   float* VxN;           // [B][n]
   float* VxxN;          // [B][n][n]
-  float* scratch;       // line-search candidates
-  AlphaList al;
-  int n_alpha, B, N, max_iter, flags;
-  float reg;
-  double tol;
-  int n_ctrl;
-  float* x_cur;
-  float* traj_x;              // [B][n_ctrl+1][n]
-  float* traj_u;              // [B][n_ctrl][m]
-  int32_t* traj_iters;        // [B][n_ctrl]
-  const float* disturbance;   // [n_ctrl][B][n] or NULL
-  SolveLogDev log;            // per-iteration log ring (rec == nullptr: none); plain solves only (n_ctrl == 0)
+  SolveLoop c;          // x [B][N+1][n], u [B][N][m], K [B][N][m][n], k [B][N][m]
 };
-
-constexpr int US_FLAG_SIMULATE = 1, US_FLAG_FIXED = 2, US_FLAG_RESET = 4;
-
-// every store of this wave has completed before its lanes read what other lanes of the wave wrote
-__device__ __forceinline__ void wave_handoff() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 
 // (two waves per SIMD: left to itself the allocator takes 300 registers for the dual-number linearisation next to the tile sweep —
 //  one wave per SIMD — and the loop runs 3x slower than with the 42 spilled registers this bound costs)
@@ -75,40 +45,26 @@ __global__ __launch_bounds__(QT_WAVE, 2) void solve_user_kernel(const UserSolveA
   __shared__ __attribute__((aligned(16))) float s_t[TILE ? 16 * LD : 4];
   __shared__ __attribute__((aligned(16))) float s_vx[64];
   __shared__ __attribute__((aligned(16))) float s_lin[4];
+  const SolveLoop& c = a.c;
   const int lane = threadIdx.x;
   const int b = blockIdx.x;                      // (grid = B exactly)
   const size_t bb = b;
-  const bool force = (a.flags & US_FLAG_FIXED) != 0;
-  const int N = a.N;
-  float* xb = a.x + bb * (N + 1) * NX;
-  float* ub = a.u + bb * N * NU;
+  const bool force = (c.flags & QUATTRO_SOLVE_FIXED_ITERS) != 0;
+  const int N = c.N;
+  float* xb = c.x + bb * (N + 1) * NX;
+  float* ub = c.u + bb * N * NU;
   float* recb = a.rec + bb * N * R::STRIDE;
-  volatile int32_t* act_flag = a.active + b;     // written by this wave's line search: always re-read from memory
-  const int n_ctrl = a.n_ctrl > 0 ? a.n_ctrl : 1;
+  volatile int32_t* act_flag = c.active + b;     // written by this wave's line search: always re-read from memory
+  const int n_ctrl = c.n_ctrl > 0 ? c.n_ctrl : 1;
   for (int cs = 0; cs < n_ctrl; ++cs) {
-    if ((a.flags & (US_FLAG_SIMULATE | US_FLAG_RESET)) != 0 || a.n_ctrl > 0) {
-      if (lane == 0) {
-        if (a.n_ctrl > 0 && cs == 0) {
-#pragma unroll
-          for (int i = 0; i < NX; ++i) a.traj_x[(bb * (a.n_ctrl + 1)) * NX + i] = a.x0[bb * NX + i];
-        }
-        if (a.n_ctrl > 0 || (a.flags & US_FLAG_RESET) != 0) {
-          a.iters[b] = 0;           // per-solve state of this control step (what a host caller resets before a solve)
-          a.active[b] = 1;
-          a.alpha_idx[b] = -1;
-          if (a.status != nullptr) a.status[b] = 0;
-        }
-        if ((a.flags & US_FLAG_SIMULATE) != 0 || a.n_ctrl > 0) simulate_body<MODEL, RK4>(a.p, a.x0, a.u, N, a.x, a.cost, b);
-      }
-      wave_handoff();
-    }
-    const bool logging = a.log.rec != nullptr && a.n_ctrl == 0;
-    for (int it = 0; it < a.max_iter; ++it) {
+    wave_step_prologue<NX>(c, bb, cs, lane == 0, [&] { simulate_body<MODEL, RK4>(a.p, c.x0, c.u, N, c.x, c.cost, b); });
+    const bool logging = c.log.rec != nullptr && c.n_ctrl == 0;
+    for (int it = 0; it < c.max_iter; ++it) {
       if (!(force || *act_flag != 0)) break;       // wave-uniform: one trajectory per wave
       int log_it = 0;
       if (logging) {             // the record of this iteration: nominal, cost, start stamp
-        log_it = *(volatile int32_t*)(a.iters + b);
-        log_begin(a.log, b, log_it, xb, ub, *(volatile double*)(a.cost + b), lane, QT_WAVE);
+        log_it = *(volatile int32_t*)(c.iters + b);
+        log_begin(c.log, b, log_it, xb, ub, *(volatile double*)(c.cost + b), lane, QT_WAVE);
       }
       // linearisation about the nominal: LPI lanes per step
       {
@@ -123,56 +79,26 @@ __global__ __launch_bounds__(QT_WAVE, 2) void solve_user_kernel(const UserSolveA
       wave_handoff();
       if constexpr (TILE) {
         FusedArgs fa;
-        fa.B = a.B;
+        fa.B = c.B;
         fa.k_rows = 0;
         fa.rn = NX;
         fa.rm = NU;
-        sweep_tile16_body<MODE_ROWPAD>(a.rec, a.VxN, a.VxxN, N, a.reg, a.K, a.k, a.status, fa, b, lane, s_t, s_vx, s_lin);
+        sweep_tile16_body<MODE_ROWPAD>(a.rec, a.VxN, a.VxxN, N, c.reg, c.K, c.k, c.status, fa, b, lane, s_t, s_vx, s_lin);
       } else {
-        sweep_generic_body<NX, NU>(a.rec, a.VxN, a.VxxN, N, a.reg, a.K, a.k, a.status, b, lane);
+        sweep_generic_body<NX, NU>(a.rec, a.VxN, a.VxxN, N, c.reg, c.K, c.k, c.status, b, lane);
       }
-      if (logging && lane == 0) log_stamp(a.log, b, log_it, 1, 2);
+      if (logging && lane == 0) log_stamp(c.log, b, log_it, 1, 2);
       wave_handoff();
-      linesearch_body<MODEL, RK4, 64>(a.p, a.x, a.u, a.K, a.k, a.al, a.n_alpha, a.B, N, a.tol, a.cost, a.alpha_idx, a.active,
-                                      a.iters, a.scratch, 64 * b + lane, force);
+      linesearch_body<MODEL, RK4, 64>(a.p, c.x, c.u, c.K, c.k, c.al, c.n_alpha, c.B, N, c.tol, c.cost, c.alpha_idx, c.active,
+                                      c.iters, c.scratch, 64 * b + lane, force);
       wave_handoff();
       if (logging)               // gains, accepted step, cost after the iteration, end stamp
-        log_end(a.log, b, log_it, a.K + bb * N * NU * NX, a.k + bb * N * NU, *(volatile int32_t*)(a.alpha_idx + b),
-                *(volatile double*)(a.cost + b), lane, QT_WAVE);
+        log_end(c.log, b, log_it, c.K + bb * N * NU * NX, c.k + bb * N * NU, *(volatile int32_t*)(c.alpha_idx + b),
+                *(volatile double*)(c.cost + b), lane, QT_WAVE);
     }
-    if (a.n_ctrl > 0) {
-      // apply u_0 to the plant (the device model itself), record, shift the warm start u <- (u_1 .. u_{N-1}, u_{N-1})
-      const int tot = (N - 1) * NU;                              // elements that move
-      float u0[NU];
-#pragma unroll
-      for (int q = 0; q < NU; ++q) u0[q] = ub[q];
-      for (int base = 0; base < tot; base += QT_WAVE) {
-        const int e = base + lane;
-        const float v = e < tot ? ub[e + NU] : 0.0f;
-        wave_handoff();                                          // every element of the pass is read before any is written
-        if (e < tot) ub[e] = v;
-        wave_handoff();
-      }
-      if (lane == 0) {
-        float xo[NX], xn[NX];
-#pragma unroll
-        for (int i = 0; i < NX; ++i) xo[i] = a.x_cur[bb * NX + i];
-        qt_step<MODEL, RK4>(a.p, xo, u0, xn);
-        if (a.disturbance != nullptr) {
-#pragma unroll
-          for (int i = 0; i < NX; ++i) xn[i] += a.disturbance[((size_t)cs * a.B + bb) * NX + i];
-        }
-#pragma unroll
-        for (int q = 0; q < NU; ++q) a.traj_u[(bb * a.n_ctrl + cs) * NU + q] = u0[q];
-        a.traj_iters[bb * a.n_ctrl + cs] = a.iters[b];
-#pragma unroll
-        for (int i = 0; i < NX; ++i) {
-          a.x_cur[bb * NX + i] = xn[i];
-          a.traj_x[(bb * (a.n_ctrl + 1) + cs + 1) * NX + i] = xn[i];
-        }
-      }
-      wave_handoff();
-    }
+    if (c.n_ctrl > 0)            // apply u_0 to the plant (the device model itself), record, shift the warm start
+      wave_mpc_epilogue<NX, NU, QT_WAVE>(c, bb, cs, lane, true,
+                                         [&](const float* xo, const float* u0, float* xn) { qt_step<MODEL, RK4>(a.p, xo, u0, xn); });
   }
 }
 
@@ -209,43 +135,10 @@ int quattro_launch_sweep_rowpad_user(const float* rec, const float* VxN, const f
   return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;
 }
 
-int quattro_launch_solve_user(const quattro_model_params& p, const float* x0, float* x, float* u, int B, int N, float reg,
-                              const float* alphas, int n_alpha, double tol, int max_iter, int flags, float* K, float* k,
-                              double* cost, int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status, float* rec,
-                              float* VxN, float* VxxN, float* scratch, int n_ctrl, float* x_cur, float* traj_x, float* traj_u,
-                              int32_t* traj_iters, const float* disturbance, const quattro_solve_log* log, hipStream_t stream) {
-  UserSolveArgs a;
-  a.p = p;
-  a.x0 = n_ctrl > 0 ? x_cur : x0;
-  a.x = x;
-  a.u = u;
-  a.K = K;
-  a.k = k;
-  a.cost = cost;
-  a.alpha_idx = alpha_idx;
-  a.active = active;
-  a.iters = iters;
-  a.status = status;
-  a.rec = rec;
-  a.VxN = VxN;
-  a.VxxN = VxxN;
-  a.scratch = scratch;
-  for (int i = 0; i < QUATTRO_MAX_ALPHAS; ++i) a.al.a[i] = i < n_alpha ? alphas[i] : 0.0f;
-  a.n_alpha = n_alpha;
-  a.B = B;
-  a.N = N;
-  a.max_iter = max_iter;
-  a.flags = flags;
-  a.reg = reg;
-  a.tol = tol;
-  a.n_ctrl = n_ctrl;
-  a.x_cur = x_cur;
-  a.traj_x = traj_x;
-  a.traj_u = traj_u;
-  a.traj_iters = traj_iters;
-  a.disturbance = disturbance;
-  a.log = make_log_dev(n_ctrl > 0 ? nullptr : log, QT_USER_NX, QT_USER_NU, N);
-  const dim3 grid((unsigned)B);
+int quattro_launch_solve_user(const quattro_model_params& p, const SolveLoop& c, float* rec, float* VxN, float* VxxN,
+                              hipStream_t stream) {
+  const UserSolveArgs a{p, rec, VxN, VxxN, c};
+  const dim3 grid((unsigned)c.B);
   if (p.integrator == QUATTRO_INTEGRATOR_EULER)
     hipLaunchKernelGGL((solve_user_kernel<false>), grid, dim3(QT_WAVE), 0, stream, a);
   else if (p.integrator == QUATTRO_INTEGRATOR_RK4)
