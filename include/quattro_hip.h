@@ -46,7 +46,8 @@ extern "C" {
                                   * which assumes a symmetric positive definite block (any convex cost).  A pivot <= 0 or
                                   * <= 1e-6 x the diagonal entry it started from sets this bit: K, k of that trajectory
                                   * may be inaccurate.  The ROWMAJOR path pivots like the reference's LAPACK inverse
-                                  * (quattro_ilqr_tf.py:306) and never sets it; re-run flagged trajectories there.     */
+                                  * (quattro_ilqr_tf.py:306) and never sets it; re-run flagged trajectories there (the
+                                  * iterations and solve loops of a user model's library do it themselves).            */
 
 /* device models: the reference takes Python callables f, L, Lf (quattro_ilqr_tf.py:82-84); a kernel
  * cannot call Python, so the two shipped problems are built in and selected by id.                   */
@@ -115,8 +116,10 @@ typedef struct quattro_model_params {
 /*   ROWMAJOR_TILE : ROWMAJOR records (the same buffer, byte for byte) of a problem with n <= 12, m <= 4, swept by the MFMA
  *             tile kernel instead of the generic one: the kernel zero-pads the problem into its 16 x 16 tile as it loads
  *             (unit pivots for the controls that are not there), so the records stay as small as the problem.  Like every
- *             tile sweep it eliminates WITHOUT pivoting (QUATTRO_TRAJ_ILLCOND): sweep flagged trajectories again with
- *             layout ROWMAJOR — no repacking needed.  What a user-compiled model with n <= 12, m <= 4 gets.              */
+ *             tile sweep it eliminates WITHOUT pivoting (QUATTRO_TRAJ_ILLCOND): quattro_riccati_sweep_f32 reports the bit
+ *             and the caller sweeps flagged trajectories again with layout ROWMAJOR — no repacking needed.  What a
+ *             user-compiled model with n <= 12, m <= 4 gets; its quattro_ilqr_iterate_f32, quattro_ilqr_solve_f32 and
+ *             quattro_mpc_run_f32 re-sweep flagged trajectories with pivoting themselves, in the same launch.            */
 #define QUATTRO_LAYOUT_ROWMAJOR_TILE 4
 
 int quattro_version(void);

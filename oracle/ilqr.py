@@ -172,9 +172,10 @@ def riccati_sweep(d, reg=QUU_REG, dtype=np.float64):
     return k_out, K_out
 
 
-def riccati_sweep_batched(d, reg=QUU_REG, dtype=np.float64):
+def riccati_sweep_batched(d, reg=QUU_REG, dtype=np.float64, quu_out=None):
     """Same recursion over a batch: every array of `d` has a leading batch axis
-    (A: (Bt,S,n,n), ..., VxN: (Bt,n), VxxN: (Bt,n,n)).  Returns k (Bt,S,m), K (Bt,S,m,n)."""
+    (A: (Bt,S,n,n), ..., VxN: (Bt,n), VxxN: (Bt,n,n)).  Returns k (Bt,S,m), K (Bt,S,m,n).
+    quu_out: an array (Bt,S,m,m) that receives the matrices inverted, Q_uu + reg I."""
     A = d["A"].astype(dtype); Bm = d["B"].astype(dtype)
     lx = d["lx"].astype(dtype); lu = d["lu"].astype(dtype)
     lxx = d["lxx"].astype(dtype); luu = d["luu"].astype(dtype); lux = d["lux"].astype(dtype)
@@ -192,6 +193,8 @@ def riccati_sweep_batched(d, reg=QUU_REG, dtype=np.float64):
         Qxx = lxx[:, s] + At @ Vxx @ A[:, s]
         Qux = lux[:, s] + Bt_ @ Vxx @ A[:, s]
         Quu = luu[:, s] + Bt_ @ Vxx @ Bm[:, s]
+        if quu_out is not None:
+            quu_out[:, s] = Quu + dtype(reg) * eye
         W = np.linalg.inv(Quu + dtype(reg) * eye)
         k = -mv(W, Qu)
         K = -(W @ Qux)

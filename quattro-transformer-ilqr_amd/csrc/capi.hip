@@ -36,7 +36,7 @@ int quattro_launch_solve_log_record(const quattro_solve_log&, int, const float*,
                                     hipStream_t);
 #ifdef QT_USER_MODEL_HEADER
 int quattro_launch_sweep_rowpad_user(const float*, const float*, const float*, int, int, int, int, float, float*, float*, int32_t*,
-                                     const int32_t*, hipStream_t);
+                                     const int32_t*, bool, hipStream_t);
 int quattro_launch_solve_user(const quattro_model_params& p, const SolveLoop& loop, float* rec, float* VxN, float* VxxN,
                               hipStream_t stream);
 #endif
@@ -138,7 +138,7 @@ int quattro_riccati_sweep_f32(const float* rec, const float* VxN, const float* V
   const int S = N - t_start;
 #ifdef QT_USER_MODEL_HEADER
   if (layout == QUATTRO_LAYOUT_ROWMAJOR_TILE)      // this library's own instance (its flags: rounds like its persistent kernel)
-    return quattro_launch_sweep_rowpad_user(rec, VxN, VxxN, B, S, n, m, reg, K, k, status, active, (hipStream_t)stream);
+    return quattro_launch_sweep_rowpad_user(rec, VxN, VxxN, B, S, n, m, reg, K, k, status, active, false, (hipStream_t)stream);
 #endif
   if (layout == QUATTRO_LAYOUT_TILE16 || layout == QUATTRO_LAYOUT_TILE16C || layout == QUATTRO_LAYOUT_TILE16R ||
       layout == QUATTRO_LAYOUT_ROWMAJOR_TILE)
@@ -309,7 +309,14 @@ static int quattro_ilqr_iterate_logged(const quattro_model_params* p, float* x_n
   } else {
     rc = quattro_linearize_f32(p, x_nom, u_nom, B, N, 0, layout, rec, VxN, VxxN, active, stream);
     if (rc != QUATTRO_OK) return rc;
-    rc = quattro_riccati_sweep_f32(rec, VxN, VxxN, B, N, 0, p->n, p->m, layout, reg, K, k, status, active, stream);
+#ifdef QT_USER_MODEL_HEADER
+    // a user model's tile sweep re-sweeps the trajectories it flags QUATTRO_TRAJ_ILLCOND with pivoting, in the same launch, as its
+    // persistent kernel does (solve_user.hip): the iteration never hands the line search gains that needed pivoting
+    if (layout == QUATTRO_LAYOUT_ROWMAJOR_TILE)
+      rc = quattro_launch_sweep_rowpad_user(rec, VxN, VxxN, B, N, p->n, p->m, reg, K, k, status, active, true, (hipStream_t)stream);
+    else
+#endif
+      rc = quattro_riccati_sweep_f32(rec, VxN, VxxN, B, N, 0, p->n, p->m, layout, reg, K, k, status, active, stream);
     if (rc != QUATTRO_OK) return rc;
   }
   if (log != nullptr && iters != nullptr) {

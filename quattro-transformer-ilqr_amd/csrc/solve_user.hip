@@ -9,7 +9,9 @@
 //   nominal rollout : lane 0                                              (rollout_body.h: simulate_body)
 //   linearisation   : LPI lanes per step, 64 / LPI steps at a time        (user_linearize.h: forward-mode duals) -> ROWMAJOR records
 //   terminal pair   : lanes 0..n-1                                        (user_linearize.h)
-//   sweep           : the 64 lanes                                        (sweep_generic_body.h: pivoting, the reference's formulas)
+//   sweep           : the 64 lanes   (n <= 12, m <= 4: sweep_tile16_body.h, the MFMA tile recursion without pivoting, and for a
+//                                     trajectory it flags QUATTRO_TRAJ_ILLCOND the same records again through sweep_generic_body.h;
+//                                     larger problems: sweep_generic_body.h alone — pivoting, the reference's formulas)
 //   line search     : lanes 0..5 roll the candidates out, all 64 copy the accepted one   (rollout_body.h: linesearch_body<.., 64>)
 // Bit-identical to the host-driven loop of the same library (all of a user library's translation units are compiled with
 // -ffp-contract=off so that the shared device functions round alike wherever they are inlined).
@@ -23,6 +25,14 @@
 #include "user_linearize.h"
 
 namespace {
+
+// The pivoting re-sweep of a trajectory the tile sweep flagged QUATTRO_TRAJ_ILLCOND, out of line: inlined, it raised the persistent
+// kernel's scratch from 100 to 256 B per lane (planar example, Euler); as a call, to 112.
+template <int NX, int NU>
+__device__ __noinline__ void sweep_generic_repair(const float* rec, const float* VxN, const float* VxxN, int S, float reg, float* Kout,
+                                                  float* kout, int32_t* status, const int b, const int lane) {
+  sweep_generic_body<NX, NU>(rec, VxN, VxxN, S, reg, Kout, kout, status, b, lane);
+}
 
 struct UserSolveArgs {
   quattro_model_params p;
@@ -61,6 +71,8 @@ __global__ __launch_bounds__(QT_WAVE, 2) void solve_user_kernel(const UserSolveA
     const bool logging = c.log.rec != nullptr && c.n_ctrl == 0;
     for (int it = 0; it < c.max_iter; ++it) {
       if (!(force || *act_flag != 0)) break;       // wave-uniform: one trajectory per wave
+      if (force && lane == 0) *act_flag = 1;       // as the enqueued loop sets it before every forced iteration: afterwards
+                                                   // `active` holds the last line search's verdict, not the first stop's
       int log_it = 0;
       if (logging) {             // the record of this iteration: nominal, cost, start stamp
         log_it = *(volatile int32_t*)(c.iters + b);
@@ -83,7 +95,12 @@ __global__ __launch_bounds__(QT_WAVE, 2) void solve_user_kernel(const UserSolveA
         fa.k_rows = 0;
         fa.rn = NX;
         fa.rm = NU;
-        sweep_tile16_body<MODE_ROWPAD>(a.rec, a.VxN, a.VxxN, N, c.reg, c.K, c.k, c.status, fa, b, lane, s_t, s_vx, s_lin);
+        if (sweep_tile16_body<MODE_ROWPAD>(a.rec, a.VxN, a.VxxN, N, c.reg, c.K, c.k, c.status, fa, b, lane, s_t, s_vx, s_lin)) {
+          // a pivot needed pivoting (an indefinite Q_uu + reg I): the pivoting sweep on the same records, like
+          // sweep_rowpad_user_kernel<true> of the host-driven loop; it rewrites K, k and status[b] (wave-uniform branch)
+          wave_handoff();
+          sweep_generic_repair<NX, NU>(a.rec, a.VxN, a.VxxN, N, c.reg, c.K, c.k, c.status, b, lane);
+        }
       } else {
         sweep_generic_body<NX, NU>(a.rec, a.VxN, a.VxxN, N, c.reg, c.K, c.k, c.status, b, lane);
       }
@@ -107,7 +124,12 @@ __global__ __launch_bounds__(QT_WAVE, 2) void solve_user_kernel(const UserSolveA
 // The stand-alone tile sweep of THIS library (layout ROWMAJOR_TILE): the same body, compiled in this translation unit with this
 // library's flags (no implicit fma contraction), so that the host-driven loop of a user model rounds exactly like its persistent
 // kernel above.  (libquattro_hip.so has its own instance for foreign records, compiled with its flags.)
+// REPAIR (the iterations of quattro_ilqr_iterate_f32 / the enqueued solve): a trajectory the tile sweep flags QUATTRO_TRAJ_ILLCOND
+// is swept again, in the same launch, by the pivoting generic body on the same records — exactly what the persistent kernel does,
+// so that no user-model loop returns gains of an unpivoted elimination that needed pivoting.  Without REPAIR (quattro_riccati_sweep_f32)
+// the flag is reported and left to the caller (include/quattro_hip.h).
 namespace {
+template <bool REPAIR>
 __global__ __launch_bounds__(QT_WAVE) void sweep_rowpad_user_kernel(const float* __restrict__ rec, const float* __restrict__ VxN,
                                                                     const float* __restrict__ VxxN, int S, float reg,
                                                                     float* __restrict__ Kout, float* __restrict__ kout,
@@ -123,15 +145,26 @@ __global__ __launch_bounds__(QT_WAVE) void sweep_rowpad_user_kernel(const float*
   fa.k_rows = 0;
   fa.rn = n;
   fa.rm = m;
-  sweep_tile16_body<MODE_ROWPAD>(rec, VxN, VxxN, S, reg, Kout, kout, status, fa, b, lane, s_t, s_vx, s_lin);
+  const bool illc = sweep_tile16_body<MODE_ROWPAD>(rec, VxN, VxxN, S, reg, Kout, kout, status, fa, b, lane, s_t, s_vx, s_lin);
+  if constexpr (REPAIR) {
+    if (illc) {                 // (wave-uniform; the launcher checked (n, m) == (QT_USER_NX, QT_USER_NU))
+      wave_handoff();
+      sweep_generic_body<QT_USER_NX, QT_USER_NU>(rec, VxN, VxxN, S, reg, Kout, kout, status, b, lane);
+    }
+  }
 }
 }  // namespace
 
 int quattro_launch_sweep_rowpad_user(const float* rec, const float* VxN, const float* VxxN, int B, int S, int n, int m, float reg,
-                                     float* K, float* k, int32_t* status, const int32_t* active, hipStream_t stream) {
+                                     float* K, float* k, int32_t* status, const int32_t* active, bool repair, hipStream_t stream) {
   if (n < 1 || n > 12 || m < 1 || m > 4) return QUATTRO_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(sweep_rowpad_user_kernel, dim3((unsigned)B), dim3(QT_WAVE), 0, stream, rec, VxN, VxxN, S, reg, K, k, status,
-                     active, B, n, m);
+  if (repair && (n != QT_USER_NX || m != QT_USER_NU)) return QUATTRO_ERR_UNSUPPORTED;
+  if (repair)
+    hipLaunchKernelGGL(sweep_rowpad_user_kernel<true>, dim3((unsigned)B), dim3(QT_WAVE), 0, stream, rec, VxN, VxxN, S, reg, K, k,
+                       status, active, B, n, m);
+  else
+    hipLaunchKernelGGL(sweep_rowpad_user_kernel<false>, dim3((unsigned)B), dim3(QT_WAVE), 0, stream, rec, VxN, VxxN, S, reg, K, k,
+                       status, active, B, n, m);
   return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;
 }
 

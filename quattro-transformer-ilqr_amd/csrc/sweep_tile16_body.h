@@ -328,8 +328,9 @@ __device__ __forceinline__ Rk4Entry rk4_m_entry(const quattro_model_params& p, i
   return e;
 }
 
+// -> the ILLCOND verdict of this trajectory (wave-uniform; also written to status[b] when there is a status array)
 template <int MODE>
-__device__ __forceinline__ void sweep_tile16_body(const float* __restrict__ rec, const float* __restrict__ VxN,
+__device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec, const float* __restrict__ VxN,
                                                   const float* __restrict__ VxxN, int S, float reg,
                                                   float* __restrict__ Kout, float* __restrict__ kout,
                                                   int32_t* __restrict__ status, const FusedArgs& fa, const int b,
@@ -813,6 +814,7 @@ __device__ __forceinline__ void sweep_tile16_body(const float* __restrict__ rec,
       status[b] = (any_bad ? QUATTRO_TRAJ_NONFINITE : 0) | (singular ? QUATTRO_TRAJ_SINGULAR : 0) |
                   (illc ? QUATTRO_TRAJ_ILLCOND : 0);
   }
+  return illc;
 }
 
 }  // namespace

@@ -7,7 +7,7 @@ import quattro_ilqr_amd as q
 from quattro_ilqr_amd import user_model
 import test_user_model_gpu as t
 
-built = [user_model.example_planar_model().lib_path, t.planar_model("rk4").lib_path]
+built = [user_model.example_planar_model().lib_path, t.planar_model("rk4").lib_path, t.slack_model("rk4").lib_path]
 b = q.quadrotor_model()
 built.append(q.compile_model("quadrotor_user", 12, 4, rate=t.QUAD_RATE, dt=b.dt, integrator="euler", phys=b.phys, q=b.q, r=b.r, qf=b.qf,
                              x_ref=b.x_ref, barrier_alpha=b.barrier_alpha, barrier_beta=b.barrier_beta).lib_path)

@@ -31,7 +31,13 @@ Fixture families:
   G14    mpc_objects_<model>.npz   the reference's QuadrotorMPC / CartPoleMPC as data: the attributes the drop-in recognises them
                                    by and their callables' outputs at the drop-in's probe points (tests/test_host_cpu.py)
 
-`--only dataset` regenerates G10 alone, `--only lqr` G11, `--only user_planar` G13, `--only mpc_objects` G14.
+  G15    user_slack.npz            G13's reference run on the planar vehicle with a slack control (tests/test_user_model_gpu.py: the
+                                   "planar + slack" problem): a stage cost whose Q_uu + reg I is indefinite where the slack is 0, so
+                                   the reference's np.linalg.inv pivots — Euler and RK4, four starts that are indefinite at
+                                   every step or at some
+
+`--only dataset` regenerates G10 alone, `--only lqr` G11, `--only user_planar` G13, `--only mpc_objects` G14,
+`--only user_slack` G15.
 """
 import os
 import sys
@@ -493,6 +499,34 @@ def gen_user_planar(n_states=4, N=30, max_iter=40):
     save("user_planar.npz", **out)
 
 
+# ------------------------------------------------------------------ G15
+SLACK_STARTS = (0.0, -0.5, 0.25, 0.5)   # slack u0 of each start: indefinite Q_uu + reg I at every step (0) or at some, and well
+                                        # conditioned along the whole solve (clear starts pass through a near-singular Q_uu)
+
+
+def gen_user_slack(N=30, max_iter=40):
+    """G15: the reference class on the "planar + slack" callables of tests/test_user_model_gpu.py (problem, starts)."""
+    from quattro_ilqr_tf.quattro_ilqr_tf import iLQR_TF
+    sys.path.insert(0, os.path.dirname(OUT))
+    import test_user_model_gpu as U
+    x0s, u0s = U.slack_batch(np.array(SLACK_STARTS), N, 2)
+    out = dict(phys=np.array(U.PHYS), Q=U.Q, R=U.SLACK_R, QF=U.QF, x_ref=U.XREF, dt=np.array(U.DT), c=np.array(U.SLACK_C),
+               w=np.array(U.SLACK_W), x0=x0s, u_init=u0s, N=np.array(N), max_iter=np.array(max_iter), tol=np.array(1e-3))
+    for method in ("euler", "rk4"):
+        for i in range(len(SLACK_STARTS)):
+            il = iLQR_TF(U.slack_f(method), U.slack_L, U.slack_Lf, x0s[i], [u for u in u0s[i]], N, dt=U.DT, max_iter=max_iter,
+                         tol=1e-3)
+            u_fin, x_fin = il.optimize(U.XREF)
+            lg = _pad_logs(il.logs, N, 6, 3, max_iter)
+            for k_, v in lg.items():
+                out[f"{method}_s{i}_{k_}"] = v
+            out[f"{method}_s{i}_u_final"] = np.array(u_fin)
+            out[f"{method}_s{i}_x_final"] = x_fin
+            print(f"  slack/{method} state {i} (slack {SLACK_STARTS[i]}): {len(il.logs)} iterations, alphas "
+                  f"{[lg_['alpha'] for lg_ in il.logs]}")
+    save("user_slack.npz", **out)
+
+
 # ------------------------------------------------------------------ G14
 PROBE_SEED, PROBE_POINTS = 20240607, 6          # quattro_ilqr_amd.solver.probe_callables: seed and number of probe points
 
@@ -546,6 +580,9 @@ if __name__ == "__main__":
     if sys.argv[1:] == ["--only", "user_planar"]:
         gen_user_planar()
         sys.exit(0)
+    if sys.argv[1:] == ["--only", "user_slack"]:
+        gen_user_slack()
+        sys.exit(0)
     if sys.argv[1:] == ["--only", "hybrid_cartpole"]:
         gen_hybrid("cartpole", max_iter=6)
         sys.exit(0)
@@ -571,3 +608,4 @@ if __name__ == "__main__":
     gen_int8("cartpole"); gen_int8("quadrotor")
     gen_user_planar()
     gen_mpc_objects("quadrotor"); gen_mpc_objects("cartpole")
+    gen_user_slack()

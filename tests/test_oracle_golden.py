@@ -183,6 +183,83 @@ def test_optimize_logs_on_a_problem_the_reference_does_not_ship(integ):
         assert np.max(np.abs(x_fin - g[key + "x_final"])) < 1e-9
 
 
+
+# ------------------------------------------------------------------ G15
+def _slack_problem(g):
+    """The "planar + slack" problem of tests/test_user_model_gpu.py, checked against the parameters G15 was made with."""
+    import test_user_model_gpu as U
+    assert np.array_equal(g["phys"], U.PHYS) and np.array_equal(g["Q"], U.Q) and np.array_equal(g["R"], U.SLACK_R)
+    assert np.array_equal(g["QF"], U.QF) and np.array_equal(g["x_ref"], U.XREF) and float(g["dt"]) == U.DT
+    assert float(g["c"]) == U.SLACK_C and float(g["w"]) == U.SLACK_W
+    return U
+
+
+@pytest.mark.parametrize("integ", ["euler", "rk4"])
+def test_optimize_logs_with_an_indefinite_quu(integ):
+    """G15: the reference's iLQR_TF on the "planar + slack" callables, where Q_uu + reg I is indefinite and its
+    np.linalg.inv pivots (make_golden.py: gen_user_slack); the oracle reproduces its logs to the G13 bounds."""
+    g = load_golden("user_slack.npz")
+    U = _slack_problem(g)
+    f, N = U.slack_f(integ), int(g["N"])
+    for s in range(g["x0"].shape[0]):
+        u_fin, x_fin, logs = ilqr.optimize(f, U.slack_L, U.slack_Lf, g["x0"][s], [u for u in g["u_init"][s]], N,
+                                           max_iter=int(g["max_iter"]), tol=float(g["tol"]))
+        key = f"{integ}_s{s}_"
+        assert len(logs) == int(g[key + "n_iter"])
+        for i, lg in enumerate(logs):
+            assert (-1.0 if lg["alpha"] is None else lg["alpha"]) == g[key + "alpha"][i]
+            assert np.max(np.abs(lg["x_seq"] - g[key + "x_seq"][i])) < 1e-9
+            assert np.max(np.abs(np.array(lg["K_seq"]) - g[key + "K"][i])) <= 1e-7 * np.max(np.abs(g[key + "K"][i]))
+        assert np.max(np.abs(np.array(u_fin) - g[key + "u_final"])) < 1e-8
+        assert np.max(np.abs(x_fin - g[key + "x_final"])) < 1e-9
+
+
+def _gauss_jordan_unpivoted_f32(M):
+    """Inverse by Gauss-Jordan elimination WITHOUT pivoting in fp32: the elimination order of the MFMA tile sweep."""
+    a = np.asarray(M, dtype=np.float32).copy()
+    w = np.eye(a.shape[0], dtype=np.float32)
+    for p in range(a.shape[0]):
+        ip = np.float32(1.0) / a[p, p]
+        a[p] *= ip
+        w[p] *= ip
+        for r in range(a.shape[0]):
+            if r != p:
+                fct = a[r, p]
+                a[r] -= fct * a[p]
+                w[r] -= fct * w[p]
+    return w
+
+
+@pytest.mark.parametrize("integ", ["euler", "rk4"])
+def test_slack_problem_needs_pivoting(integ):
+    """The GPU tests of the "planar + slack" problem can only catch an unpivoted inverse if the problem needs pivoting: at
+    the G15 starts, the fp64 Q_uu + reg I (exact derivatives) of every step with the slack at 0 is indefinite and well
+    conditioned, an fp32 Gauss-Jordan inverse without pivoting is off by far more than the GPU tests' 1e-5 bound, and
+    np.linalg.inv in fp32 is not.  The other starts are indefinite at some steps too."""
+    g = load_golden("user_slack.npz")
+    U = _slack_problem(g)
+    f, N = U.slack_f(integ), int(g["N"])
+    xs = np.array([ilqr.rollout(f, g["x0"][s], g["u_init"][s]) for s in range(g["x0"].shape[0])])
+    _, _, quu = U.exact_sweep(f, U.slack_L, U.slack_Lf, xs, g["u_init"])
+    flag_steps = g["u_init"][:, :, 0] == U.SLACK_FLAG
+    assert flag_steps[0].all() and not flag_steps[1:].any()
+    worst_gj, worst_inv, worst_cond = 0.0, 0.0, 0.0
+    for s in range(quu.shape[0]):
+        ev = np.linalg.eigvalsh(quu[s])
+        indefinite = (ev.min(axis=1) < 0) & (ev.max(axis=1) > 0)
+        assert indefinite[flag_steps[s]].all() and indefinite.any(), (s, ev)      # every start is flagged somewhere
+        for t in np.nonzero(flag_steps[s])[0]:
+            M = quu[s, t]
+            worst_cond = max(worst_cond, np.linalg.cond(M))
+            inv = np.linalg.inv(M)
+            scale = np.max(np.abs(inv))
+            worst_gj = max(worst_gj, np.max(np.abs(_gauss_jordan_unpivoted_f32(M) - inv)) / scale)
+            worst_inv = max(worst_inv, np.max(np.abs(np.linalg.inv(M.astype(np.float32)) - inv)) / scale)
+    print(f"slack/{integ}: flagged blocks cond <= {worst_cond:.1f}, unpivoted fp32 inverse off by {worst_gj:.2e}, "
+          f"pivoted fp32 inverse by {worst_inv:.2e} (relative to max |inverse|)")
+    assert worst_cond < 1e2
+    assert worst_gj > 1e-3 and worst_inv < 1e-6
+
 # ------------------------------------------------------------------ G7
 def _weights(model):
     w = load_golden(f"tf_weights_{model}.npz")

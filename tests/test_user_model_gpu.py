@@ -80,6 +80,63 @@ def planar_batch(B, N, seed=0):
     return x0, u0
 
 
+
+# ---------------------------------------------------------------------------------------------- planar + slack: an indefinite Q_uu
+# The planar vehicle with a third control u[0] that does not enter the dynamics (u[1], u[2] are the thrusts) and a stage cost
+# that couples it to them: planar cost + c u0 (u1 - u2) + w/4 u0^4 (bounded below), r = (0, 0.01, 0.02).  Where u0 = 0 the slack's
+# own second derivative is exactly 0, so Q_uu + reg I starts with the pivot reg = 1e-6 and is indefinite (eigenvalues of both
+# signs, condition number ~40): an elimination without pivoting — the MFMA tile sweep a user model with n <= 12, m <= 4 gets —
+# loses ~10 % of the inverse in fp32 and flags the trajectory QUATTRO_TRAJ_ILLCOND, and every user-model loop must then use
+# the pivoting sweep, as the reference's np.linalg.inv (quattro_ilqr_tf.py:306) does.  Where |u0| >= 1.6 the 3 w u0^2 term
+# makes the block positive definite (not flagged); from u0 = 2 one accepted iteration brings u0 to ~1.3, indefinite again.
+SLACK_C, SLACK_W = 0.3, 1.0
+SLACK_R = np.array([0.0, 0.01, 0.02])
+SLACK_FLAG, SLACK_CLEAR = 0.0, 2.0                 # slack values that make a step flagged / positive definite at the start
+SLACK_RATE = PLANAR_RATE.replace("u[0] + u[1]", "u[1] + u[2]").replace("u[0] - u[1]", "u[1] - u[2]")
+SLACK_L = ("return default_stage_cost<T>(p, x, u) + x[0] * x[2] * 0.3f + exp(u[1] * 0.1f) * 0.01f"
+           f" + u[0] * (u[1] - u[2]) * {SLACK_C}f + u[0] * u[0] * u[0] * u[0] * {0.25 * SLACK_W}f;")
+
+
+def slack_rate(x, u):
+    return planar_rate(x, u[1:])
+
+
+def slack_f(integrator):
+    def f(x, u):
+        if integrator == "euler":
+            return x + DT * slack_rate(x, u)
+        k1 = slack_rate(x, u)
+        k2 = slack_rate(x + 0.5 * DT * k1, u)
+        k3 = slack_rate(x + 0.5 * DT * k2, u)
+        k4 = slack_rate(x + DT * k3, u)
+        return x + DT / 6.0 * (k1 + 2 * k2 + 2 * k3 + k4)
+    return f
+
+
+def slack_L(x, u):
+    d = x - XREF
+    return (np.sum(Q * d * d) + np.sum(SLACK_R * u * u) + 0.3 * x[0] * x[2] + 0.01 * np.exp(0.1 * u[1])
+            + SLACK_C * u[0] * (u[1] - u[2]) + 0.25 * SLACK_W * u[0] ** 4)
+
+
+slack_Lf = planar_Lf
+
+
+def slack_model(integrator):
+    import quattro_ilqr_amd as q
+    return q.compile_model("planar_slack", 6, 3, rate=SLACK_RATE, stage_cost=SLACK_L, final_cost=PLANAR_LF, dt=DT,
+                           integrator=integrator, phys=PHYS, q=Q, r=SLACK_R, qf=QF, x_ref=XREF)
+
+
+def slack_batch(slack, N, seed=0):
+    """x0 (B, 6), u0 (B, N, 3) in fp32-representable fp64: planar starts, u0[b, t, 0] = slack[b] (a value per trajectory, or a
+    row of N values per trajectory)."""
+    slack = np.asarray(slack, dtype=np.float64)
+    B = slack.shape[0]
+    x0, uth = planar_batch(B, N, seed)
+    u0 = np.concatenate([np.broadcast_to(slack.reshape(B, -1, 1), (B, N, 1)), uth], axis=2)
+    return x0.astype(np.float32).astype(np.float64), u0.astype(np.float32).astype(np.float64)
+
 def complex_step_jac(fun, z, h=1e-30):
     """Exact (to fp64 round-off) Jacobian of an analytic function by complex-step differentiation."""
     z = np.asarray(z, dtype=np.complex128)
@@ -103,6 +160,33 @@ def exact_derivs(f, L, x, u):
         H[:, i] = (grad(z + e) - grad(z - e)) / (2 * eps)
     return F[:, :n], F[:, n:], g[:n], g[n:], H[:n, :n], H[n:, n:], H[n:, :n]
 
+
+
+def exact_records(f, L, Lf, xs, us):
+    """fp64 derivative blocks of a batch at the nominal (xs (B, N+1, n), us (B, N, m)) from exact_derivs, in the layout of
+    oracle.ilqr.riccati_sweep_batched."""
+    B, N, n = us.shape[0], us.shape[1], xs.shape[2]
+    names = ("A", "B", "lx", "lu", "lxx", "luu", "lux")
+    d = {k: [] for k in names}
+    for b in range(B):
+        per = [exact_derivs(f, L, xs[b, t], us[b, t]) for t in range(N)]
+        for i, k in enumerate(names):
+            d[k].append(np.array([p[i] for p in per]))
+    d = {k: np.array(v) for k, v in d.items()}
+    grad = lambda z: complex_step_jac(Lf, z)[0]
+    d["VxN"] = np.array([grad(xs[b, N]) for b in range(B)])
+    eps = 1e-6
+    d["VxxN"] = np.array([np.array([(grad(xs[b, N] + eps * e) - grad(xs[b, N] - eps * e)) / (2 * eps) for e in np.eye(n)]).T
+                          for b in range(B)])
+    return d
+
+
+def exact_sweep(f, L, Lf, xs, us):
+    """-> k (B, N, m), K (B, N, m, n), Q_uu + reg I (B, N, m, m): the fp64 oracle sweep on exact derivatives."""
+    d = exact_records(f, L, Lf, xs, us)
+    quu = np.zeros(us.shape + (us.shape[2],))
+    k, K = O.riccati_sweep_batched(d, quu_out=quu)
+    return k, K, quu
 
 # ---------------------------------------------------------------------------------------------- tests
 @pytest.mark.parametrize("integrator", ["euler", "rk4"])
@@ -308,17 +392,26 @@ def test_user_model_whole_workflow_collect_fit_hybrid():
     assert np.max(np.abs(x_fin - out["x"][0].double().cpu().numpy())) < 1e-4
 
 
-@pytest.mark.parametrize("integrator,B,N", [("rk4", 1, 30), ("euler", 37, 25), ("rk4", 300, 50), ("euler", 5, 7)])
-def test_user_model_device_resident_solve_and_mpc_equal_the_host_driven_loops(integrator, B, N):
+@pytest.mark.parametrize("problem,integrator,B,N", [
+    pytest.param("planar", "rk4", 1, 30, id="rk4-1-30"), pytest.param("planar", "euler", 37, 25, id="euler-37-25"),
+    pytest.param("planar", "rk4", 300, 50, id="rk4-300-50"), pytest.param("planar", "euler", 5, 7, id="euler-5-7"),
+    pytest.param("slack", "rk4", 1, 30, id="slack-rk4-1-30"), pytest.param("slack", "euler", 37, 25, id="slack-euler-37-25"),
+    pytest.param("slack", "rk4", 300, 50, id="slack-rk4-300-50")])
+def test_user_model_device_resident_solve_and_mpc_equal_the_host_driven_loops(problem, integrator, B, N):
     """A user model's library has a persistent kernel of its own (csrc/solve_user.hip: one wave per trajectory, the generic
     device bodies): quattro_ilqr_solve_f32 / quattro_mpc_run_f32 as ONE launch against the host-driven loops of the same
     library, bit for bit — real exit tests, capped and fixed iteration counts, warm and cold starts, a disturbed closed loop
-    and a second run that continues from the first one's warm start."""
+    and a second run that continues from the first one's warm start.  "slack": the planar + slack problem, whose flagged
+    trajectories both loops re-sweep with pivoting."""
     import torch
     import quattro_ilqr_amd as q
-    md = planar_model(integrator)
+    if problem == "planar":
+        md = planar_model(integrator)
+        x0, u0 = planar_batch(B, N, 11 * B + N)
+    else:
+        md = slack_model(integrator)
+        x0, u0 = slack_batch(np.where(np.arange(B) % 2 == 0, SLACK_FLAG, SLACK_CLEAR), N, 11 * B + N)
     assert q.ops.model_can_device_loop(md) and not q.ops.model_has_device_loop(md)     # exists; enqueued iterations are the default
-    x0, u0 = planar_batch(B, N, 11 * B + N)
     keys = ("K", "k", "x", "u", "cost", "iters", "alpha", "status")
     tw = 0 if N <= 10 else 10
     for kw in (dict(), dict(max_iter=2), dict(max_iter=3, fixed_iters=True)):
@@ -519,3 +612,244 @@ def test_user_model_of_the_quadrotors_shape_one_sweep_in_all_three_paths():
     for key in ("K", "k", "x", "u", "cost", "iters", "alpha", "status"):
         assert torch.equal(od[key], oh[key]), key
     assert int(od["iters"].max()) >= 2
+
+
+# ---------------------------------------------------------------------------------------------- planar + slack on the GPU
+def _slack_sweeps(md, x, u):
+    """At the device nominal (x, u): the raw tile sweep (ROWMAJOR_TILE: flags, never repairs) and the library's generic pivoting
+    sweep (ROWMAJOR) on the same records."""
+    from quattro_ilqr_amd import _lib, ops
+    B, N = u.shape[0], u.shape[1]
+    lib = _lib.load_for(md)
+    rec, VxN, VxxN, lay = ops.linearize(md, x, u)
+    assert lay == _lib.LAYOUT_ROWMAJOR_TILE
+    Kt, kt, st = ops.riccati_sweep(rec, VxN, VxxN, 6, 3, _lib.LAYOUT_ROWMAJOR_TILE, lib=lib)
+    Kg, kg, sg = ops.riccati_sweep(rec.reshape(B, N, -1), VxN, VxxN, 6, 3, _lib.LAYOUT_ROWMAJOR, lib=lib)
+    assert int(sg.abs().sum()) == 0
+    return dict(Kt=Kt.cpu().numpy(), kt=kt.cpu().numpy(), st=st.cpu().numpy(), Kg=Kg.cpu().numpy(), kg=kg.cpu().numpy())
+
+
+def _slack_nominal(md, x0, u0):
+    import torch
+    from quattro_ilqr_amd import ops
+    x0t = torch.as_tensor(x0, dtype=torch.float32, device="cuda:0")
+    u0t = torch.as_tensor(u0, dtype=torch.float32, device="cuda:0")
+    x, _ = ops.simulate(md, x0t, u0t)
+    return x, u0t
+
+
+def _slack_check(what, K, k, status, sw, ref, flagged, rows=None, tol=1e-5):
+    """Gains handed back by an entry point (K (B, N, 3, 6), k (B, N, 3), status (B,) or None) against the fp64 oracle on exact
+    derivatives (ref = (k, K) of trajectories `rows`), the generic sweep (flagged trajectories, bit for bit) and the raw tile sweep
+    (the others, bit for bit).  -> worst per-step errors (K, k)."""
+    from quattro_ilqr_amd import _lib
+    from conftest import per_step_rel, per_step_rel_floor
+    K, k = np.asarray(K, dtype=np.float32), np.asarray(k, dtype=np.float32)
+    B = K.shape[0]
+    if status is not None:
+        assert not np.any(np.asarray(status) & (_lib.TRAJ_ILLCOND | _lib.TRAJ_SINGULAR)), (what, status)
+    for b in range(B):
+        want = (sw["Kg"][b], sw["kg"][b]) if flagged[b] else (sw["Kt"][b], sw["kt"][b])
+        assert np.array_equal(K[b], want[0]) and np.array_equal(k[b], want[1]), (what, b, bool(flagged[b]))
+    eK = ek = 0.0
+    rows = range(B) if rows is None else rows
+    for i, b in enumerate(rows):
+        eK = max(eK, per_step_rel(K[b], ref[1][i]))
+        ek = max(ek, per_step_rel_floor(k[b], ref[0][i]))
+    print(f"  {what}: per-step K {eK:.2e} k {ek:.2e} vs the fp64 oracle ({int(np.sum(flagged))} of {B} trajectories flagged)")
+    assert eK < tol and ek < tol, (what, eK, ek, tol)
+    return eK, ek
+
+
+def _slack_setup(integrator, slack, N, seed=0, ref_rows=None):
+    md = slack_model(integrator)
+    x0, u0 = slack_batch(slack, N, seed)
+    x, ut = _slack_nominal(md, x0, u0)
+    sw = _slack_sweeps(md, x, ut)
+    flagged = (sw["st"] & 4) != 0
+    rows = list(range(len(x0))) if ref_rows is None else ref_rows
+    xs = x.double().cpu().numpy()
+    k_o, K_o, _ = exact_sweep(slack_f(integrator), slack_L, slack_Lf, xs[rows], u0[rows])
+    return md, x0, u0, sw, flagged, (k_o, K_o), rows
+
+
+def _solver_gains(md, N, x0, u0, max_iter=1, **kw):
+    import quattro_ilqr_amd as q
+    s = q.QuattroILQR(md, N, max_iter=40, device="cuda:0", tf_window=0, **kw)
+    out = s.solve(x0, u0, max_iter=max_iter)
+    return out["K"].cpu().numpy(), out["k"].cpu().numpy(), out["status"].cpu().numpy()
+
+
+SOLVER_PATHS = {"persistent": dict(device_loop="always"), "default": dict(device_loop=True),
+                "host": dict(device_loop=False, check_every=1), "graph": dict(use_graph=True, device_loop=False)}
+
+
+@pytest.mark.parametrize("integrator", ["euler", "rk4"])
+def test_slack_first_sweep_every_entry_point_uses_pivoted_gains(integrator):
+    """One iteration from identical nominals, a batch of flagged and clear trajectories (an indefinite Q_uu + reg I at every
+    step, at one step, nowhere): every entry point of a user model hands back gains within 1e-5 of the fp64 oracle on exact
+    derivatives — the generic pivoting sweep's, bit for bit, where the tile sweep flags the trajectory — and no ILLCOND bit."""
+    import torch
+    import quattro_ilqr_amd as q
+    N = 30
+    slack = np.full((6, N), SLACK_CLEAR)
+    slack[0] = SLACK_FLAG; slack[2, 7] = SLACK_FLAG; slack[4] = SLACK_FLAG; slack[5, N - 1] = SLACK_FLAG
+    md, x0, u0, sw, flagged, ref, _ = _slack_setup(integrator, slack, N, 21)
+    # the raw tile sweep still reports exactly the trajectories with an indefinite step (so the repair below is what ran)
+    assert flagged.tolist() == [True, False, True, False, True, True], sw["st"]
+    print(f"slack/{integrator}: raw tile sweep vs oracle on a flagged trajectory: per-step K "
+          f"{max(float(np.max(np.abs(sw['Kt'][0][t] - ref[1][0][t])) / np.linalg.norm(ref[1][0][t])) for t in range(N)):.2e}")
+    for name, kw in SOLVER_PATHS.items():
+        _slack_check(f"QuattroILQR[{name}]", *_solver_gains(md, N, x0, u0, **kw), sw, ref, flagged)
+    # the drop-in class: optimize() (the persistent kernel, gains from its log) and backward_pass() (repair=True)
+    for b in (0, 1, 2):
+        ul = [u for u in u0[b]]
+        il = q.iLQR_TF(md, md, md, x0[b], ul, N, dt=DT, max_iter=1, tol=1e-3, device="cuda:0")
+        il.optimize(XREF)
+        K_opt, k_opt = np.array(il.logs[0]["K_seq"]), np.array(il.logs[0]["k_seq"])
+        k_bp, K_bp = il.backward_pass(il.simulate(ul), ul)
+        K_bp, k_bp = np.array(K_bp), np.array(k_bp)
+        sub = {key: v[b:b + 1] for key, v in sw.items()}
+        refb = ([ref[0][b]], [ref[1][b]])
+        _slack_check(f"iLQR_TF.optimize b={b}", K_opt[None], k_opt[None], None, sub, refb, flagged[b:b + 1])
+        _slack_check(f"iLQR_TF.backward_pass b={b}", K_bp[None], k_bp[None], None, sub, refb, flagged[b:b + 1])
+    # BatchedMPC, one control step of one iteration, from the same warm start: both of its loops
+    for loop in ("always", False):
+        mpc = q.BatchedMPC(md, N, max_iter=1, device="cuda:0", check_every=1)
+        mpc.u_warm = torch.as_tensor(u0, dtype=torch.float32, device="cuda:0")
+        mpc.run(x0, 1, device_loop=loop)
+        _slack_check(f"BatchedMPC[{loop}]", mpc.solver.K.cpu().numpy(), mpc.solver.k.cpu().numpy(), mpc.solver.status.cpu().numpy(),
+                     sw, ref, flagged)
+
+
+@pytest.mark.parametrize("case", ["N1", "steps", "B1", "B257"])
+def test_slack_sweep_edges(case):
+    """Edges of the repair: N = 1 (the only step is the flagged one); the flagged step first, last or in the middle of the
+    horizon; one trajectory; 257 (more than one wave of a 256-wide grid) with flagged and clear ones interleaved."""
+    integrator = "rk4" if case in ("N1", "B257") else "euler"
+    if case == "N1":
+        N, slack, rows = 1, [[SLACK_FLAG], [SLACK_CLEAR]], None
+    elif case == "steps":
+        N = 30
+        slack = np.full((4, N), SLACK_CLEAR)
+        slack[0, 0] = slack[1, N - 1] = slack[2, N // 2] = SLACK_FLAG
+        rows = None
+    elif case == "B1":
+        N, slack, rows = 20, [SLACK_FLAG], None
+    else:
+        N, rows = 12, [0, 1, 2, 127, 128, 255, 256]
+        slack = np.where(np.arange(257) % 3 == 0, SLACK_FLAG, SLACK_CLEAR)
+    md, x0, u0, sw, flagged, ref, rows = _slack_setup(integrator, slack, N, 5, rows)
+    if case == "steps":
+        assert flagged.tolist() == [True, True, True, False]
+    else:
+        assert flagged.tolist() == [s == SLACK_FLAG for s in np.asarray(slack).reshape(len(x0), -1)[:, 0]]
+    for name in ("persistent", "host"):
+        _slack_check(f"{case} QuattroILQR[{name}]", *_solver_gains(md, N, x0, u0, **SOLVER_PATHS[name]), sw, ref, flagged, rows)
+
+
+def _cond_tol(quu, sw, K_o):
+    """1e-5 x max(1, cond / 100) over the flagged trajectories' Q_uu + reg I; asserts that the raw tile sweep's gains of the
+    flagged trajectories are not the generic sweep's (so that bit equality with the latter shows the repair)."""
+    from conftest import per_step_rel
+    flagged = (sw["st"] & 4) != 0
+    cond = float(np.max(np.linalg.cond(quu[flagged])))
+    tol = 1e-5 * max(1.0, cond / 100.0)
+    raw = max(per_step_rel(sw["Kt"][b], K_o[b]) for b in np.nonzero(flagged)[0])
+    print(f"  cond(Q_uu + reg I) <= {cond:.0f}: bound {tol:.1e}; the raw tile sweep is off by {raw:.2e}")
+    assert not np.array_equal(sw["Kt"][flagged], sw["Kg"][flagged])
+    return tol
+
+
+def test_slack_flag_that_appears_after_an_accepted_iteration_and_in_a_later_mpc_step():
+    """Clear starts (slack 2: positive definite) whose first accepted iteration moves the slack to ~1.3, where Q_uu + reg I is
+    indefinite: the second sweep of a solve, and a later control step of an MPC run, must repair what the first did not flag.
+    There the block is also nearly singular (it has just crossed from definite to indefinite), so fp32 gains can only be as
+    close to the fp64 oracle as its condition number allows (the bound is 1e-5 x max(1, cond / 100)), and the unpivoted
+    elimination is not much worse there: what shows that the repair ran is that the gains equal the generic sweep's bit for bit
+    where the raw tile sweep's differ."""
+    import torch
+    import quattro_ilqr_amd as q
+    integrator, N = "euler", 30
+    md = slack_model(integrator)
+    x0, u0 = slack_batch(np.full(3, SLACK_CLEAR), N, 8)
+    x, ut = _slack_nominal(md, x0, u0)
+    assert not np.any(_slack_sweeps(md, x, ut)["st"] & 4)
+    one = q.QuattroILQR(md, N, device="cuda:0", device_loop="always")
+    o1 = one.solve(x0, u0, max_iter=1)
+    assert bool((o1["alpha"] > 0).all())                   # accepted
+    x1, u1 = o1["x"].clone(), o1["u"].clone()
+    sw = _slack_sweeps(md, x1, u1)
+    flagged = (sw["st"] & 4) != 0
+    assert flagged.all(), sw["st"]
+    k_o, K_o, quu = exact_sweep(slack_f(integrator), slack_L, slack_Lf, x1.double().cpu().numpy(), u1.double().cpu().numpy())
+    tol = _cond_tol(quu, sw, K_o)
+    for name in ("persistent", "host", "default"):
+        _slack_check(f"second iteration [{name}]", *_solver_gains(md, N, x0, u0, max_iter=2, **SOLVER_PATHS[name]), sw, (k_o, K_o),
+                     flagged, tol=tol)
+    # MPC: two control steps, then a third from where they left the plant and the warm start
+    for loop in ("always", False):
+        mpc = q.BatchedMPC(md, N, max_iter=1, device="cuda:0", check_every=1)
+        mpc.u_warm = torch.as_tensor(u0, dtype=torch.float32, device="cuda:0")
+        run = mpc.run(x0, 2, device_loop=loop)
+        x_cur = run["x"][:, -1].contiguous()
+        xn, _ = q.ops.simulate(md, x_cur, mpc.u_warm)
+        sw = _slack_sweeps(md, xn, mpc.u_warm)
+        flagged = (sw["st"] & 4) != 0
+        assert flagged.any(), sw["st"]
+        k_o, K_o, quu = exact_sweep(slack_f(integrator), slack_L, slack_Lf, xn.double().cpu().numpy(), mpc.u_warm.double().cpu().numpy())
+        tol = _cond_tol(quu, sw, K_o)
+        mpc.run(x_cur, 1, device_loop=loop)
+        _slack_check(f"MPC control step 3 [{loop}]", mpc.solver.K.cpu().numpy(), mpc.solver.k.cpu().numpy(),
+                     mpc.solver.status.cpu().numpy(), sw, (k_o, K_o), flagged, tol=tol)
+
+
+@pytest.mark.parametrize("integrator", ["euler", "rk4"])
+def test_slack_solves_match_the_reference_and_the_oracle(integrator):
+    """Whole solves on the G15 starts (tests/golden/user_slack.npz: the REFERENCE's iLQR_TF on these callables) with the rules
+    of test_user_model_solve_matches_the_oracle, against the reference's run and against oracle.optimize; the drop-in's
+    optimize() and backward_pass() agree bit for bit on the first iteration's gains."""
+    import torch
+    import quattro_ilqr_amd as q
+    from conftest import load_golden
+    g = load_golden("user_slack.npz")
+    assert float(g["c"]) == SLACK_C and float(g["w"]) == SLACK_W and np.array_equal(g["R"], SLACK_R)
+    md = slack_model(integrator)
+    f = slack_f(integrator)
+    N, S, max_iter, tol = int(g["N"]), g["x0"].shape[0], int(g["max_iter"]), float(g["tol"])
+    s = q.QuattroILQR(md, N, max_iter=max_iter, tol=tol, device="cuda:0")
+    out = s.solve(torch.as_tensor(g["x0"], dtype=torch.float32), torch.as_tensor(g["u_init"], dtype=torch.float32))
+    u_dev, x_dev = out["u"].double().cpu().numpy(), out["x"].double().cpu().numpy()
+    it_dev, cost_dev = out["iters"].cpu().numpy(), out["cost"].cpu().numpy()
+    assert not np.any(out["status"].cpu().numpy() & 6)
+    for src in ("reference", "oracle"):
+        same = 0
+        for b in range(S):
+            ul = [u for u in g["u_init"][b]]
+            if src == "reference":
+                key = f"{integrator}_s{b}_"
+                n_it, alphas = int(g[key + "n_iter"]), list(g[key + "alpha"][:int(g[key + "n_iter"])])
+                u_r, x_r = g[key + "u_final"], g[key + "x_final"]
+            else:
+                u_r, x_r, logs = O.optimize(f, slack_L, slack_Lf, g["x0"][b], ul, N, max_iter=max_iter, tol=tol)
+                n_it, alphas = len(logs), [(-1.0 if lg["alpha"] is None else lg["alpha"]) for lg in logs]
+                u_r = np.array(u_r)
+            J_r = O.trajectory_cost(slack_L, slack_Lf, x_r, u_r)
+            il = q.iLQR_TF(md, md, md, g["x0"][b], ul, N, dt=DT, max_iter=max_iter, tol=tol, device="cuda:0")
+            il.optimize(XREF)
+            a_dev = [(-1.0 if lg["alpha"] is None else lg["alpha"]) for lg in il.logs]
+            assert len(il.logs) == it_dev[b]
+            same += int(n_it == it_dev[b])
+            ex, eu = np.max(np.abs(x_dev[b] - x_r)), np.max(np.abs(u_dev[b] - u_r))
+            print(f"slack/{integrator} b={b} vs the {src}: iterations {n_it} / device {it_dev[b]}, alphas {alphas} / {a_dev}, "
+                  f"cost {J_r:.6f} / {cost_dev[b]:.6f}, max|dx| {ex:.2e} max|du| {eu:.2e}")
+            assert abs(n_it - it_dev[b]) <= 1
+            if n_it == it_dev[b]:                        # (x: 3e-5 where the planar test has 1e-5 — measured 1.1e-5: the
+                assert a_dev == [float(a) for a in alphas]   # reference's finite-difference noise through cond(Q_uu) ~ 250)
+                assert abs(J_r - cost_dev[b]) < 1e-6 * abs(J_r)
+                assert ex < 3e-5 and eu < 3e-5
+            if src == "reference":                       # first-iteration gains: optimize() vs backward_pass(), bit for bit
+                k_bp, K_bp = il.backward_pass(il.simulate(ul), ul)
+                assert np.array_equal(np.array(il.logs[0]["K_seq"]), np.array(K_bp))
+                assert np.array_equal(np.array(il.logs[0]["k_seq"]), np.array(k_bp))
+        assert same >= S - 1
