@@ -18,8 +18,8 @@
 //     P[i][j], Q[i][j], V'[i][j].  Rows of V reach a lane as DPP quad broadcasts folded into the multiply-add
 //     (v_fmac_f32_dpp), columns of P through ds_bpermute, V'^T (symmetrisation) and the row forms of K and Q_ux through one
 //     transposing ds_bpermute each: ~90 instructions per step.
-// Every dot product keeps the one-lane kernel's operand order (k = 0..3 ascending, same fmaf chain), so K, k are
-// bit-identical to sweep_lane_cartpole_kernel / sweep_quad_cartpole_kernel.
+// Every dot product keeps sweep_generic_kernel's operand order (k = 0..3 ascending, same fmaf chain): K, k are those of the
+// earlier one-lane and quad-lane kernels bit for bit (both removed; they are in the history of sweep_lane.hip).
 #pragma once
 #include "models_device.h"
 
@@ -79,7 +79,7 @@ constexpr int STAGE_FLOATS = CH * RS + 16;               // per trajectory: 6 KB
 #define QT_QP16(a, b, c, d) ((a) | ((b) << 2) | ((c) << 4) | ((d) << 6))
 // Row i of V times two columns of F (four entries each), V[i][k] taken from lane k of this lane's quad by the DPP modifier of
 // the multiply-add itself (v_fmac_f32_dpp): the compiler does not fold a quad_perm move into a multiply-add, and eight
-// broadcasts per step would double this part of the chain.  k ascending, one fmaf chain per accumulator — the one-lane
+// broadcasts per step would double this part of the chain.  k ascending, one fmaf chain per accumulator — the generic
 // kernel's order.  The leading s_nop covers the VALU-write -> DPP-read hazard on `v`, which the hazard recogniser cannot
 // see inside inline asm.
 __device__ __forceinline__ void row_dot2(float v, const float* c0, const float* c1, float& acc0, float& acc1) {

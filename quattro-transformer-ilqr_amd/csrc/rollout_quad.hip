@@ -18,22 +18,17 @@
 //
 // Layouts: line search = 8 candidate quads per trajectory (32 lanes), 2 trajectories per wave; simulate = 16
 // trajectories per wave.  Euler and RK4 (the rate function is the cooperative part; RK4 just calls it four times).
-// Wave priority inside a rollout step (round 4): the state recurrence (dx, K dx, u, rate function, update) at priority 1, the stage
-// cost, the record store and the next loads that hang off it at 0.  Two line-search waves share a SIMD, and vector issue is
-// arbitrated by priority, then age: whichever wave is on its recurrence goes first.  Line search 36.7 -> 33.6 us, RK4 63.2 -> 54.7 us
-// (A/B on one box; same instructions, same results).  The persistent kernel keeps its line-search wave at one constant priority
-// (solve_quad.hip), where toggling inside the step bought nothing.
-#define QT_ROLLOUT_PRIO 1
 #include "rollout_quad_body.h"
-
-// steps of nominal data a line-search quad keeps requested ahead (rollout_quad_body.h: quad_rollout_closed)
-#ifndef QT_LS_PF
-#define QT_LS_PF 4
-#endif
 
 namespace {
 
 // ---------------------------------------------------------------------------------------------- kernels
+// Wave priority inside a rollout step (round 4), PRIO = true in the two closed-loop kernels below: the state recurrence (dx, K dx,
+// u, rate function, update) at priority 1, the stage cost, the record store and the next loads that hang off it at 0.  Two
+// line-search waves share a SIMD, and vector issue is arbitrated by priority, then age: whichever wave is on its recurrence goes
+// first.  Line search 36.7 -> 33.6 us, RK4 63.2 -> 54.7 us (A/B on one box; same instructions, same results).  The persistent
+// kernel keeps its line-search wave at one constant priority (solve_quad.hip: PRIO = false), where toggling inside the step
+// bought nothing.  Both kernels keep PF = 4 steps of nominal data requested ahead (quad_rollout_closed).
 // simulate: quad per trajectory, 16 trajectories per wave
 template <bool RK4>
 __global__ __launch_bounds__(64) void simulate_quad_kernel(const quattro_model_params p, const float* __restrict__ x0,
@@ -73,9 +68,9 @@ __global__ __launch_bounds__(64) void rollout_quad_kernel(const quattro_model_pa
 #pragma unroll
       for (int g = 0; g < 4; ++g) xo[3 * g + L.a] = xn[3 * g + L.a];
     }
-    J = quad_rollout_closed<RK4, 4>(p, L, nom, alpha, N, mine, ArrayStore(L, xo, uo, mine));
+    J = quad_rollout_closed<RK4, 4, true>(p, L, nom, alpha, N, mine, ArrayStore(L, xo, uo, mine));
   } else {
-    J = quad_rollout_closed<RK4, 4>(p, L, nom, alpha, N, mine, NoStore{});
+    J = quad_rollout_closed<RK4, 4, true>(p, L, nom, alpha, N, mine, NoStore{});
   }
   J = quad_sum(J);
   if (mine && L.j == 0) cost[(size_t)ai * B + b] = J;
@@ -89,8 +84,8 @@ __global__ __launch_bounds__(64) void linesearch_quad_kernel(const quattro_model
                                                              double* cost, int32_t* __restrict__ alpha_idx,
                                                              int32_t* active, int32_t* iters,
                                                              float* __restrict__ scratch) {
-  linesearch_quad_body<RK4, QT_LS_PF>(p, x_nom, u_nom, K, k, al, n_alpha, B, N, tol, cost, alpha_idx, active, iters, scratch,
-                               blockIdx.x * blockDim.x + threadIdx.x, false);
+  linesearch_quad_body<RK4, 4, true>(p, x_nom, u_nom, K, k, al, n_alpha, B, N, tol, cost, alpha_idx, active, iters, scratch,
+                                     blockIdx.x * blockDim.x + threadIdx.x, false);
 }
 
 }  // namespace

@@ -8,21 +8,6 @@ namespace {
 
 constexpr int NX = 12, NU = 4, CS = 16;   // candidate record: x'_{t+1} (12) | u'_t (4)
 
-// Diagnostic build only (-DQT_ABLATE_LS=n, scripts/ablate_linesearch.sh): one segment of a rollout step is left out (wrong numbers
-// on purpose) to see its real share of the kernels' time.  1: the gain product K dx; 2: the stage cost and its fp64 accumulation;
-// 3: the rate function (trig and all); 4: the candidate / state stores; 5: the per-step nominal loads (line search) ; 6: the
-// commit copy of the accepted candidate.  The shipped library is built without it.
-#ifndef QT_ABLATE_LS
-#define QT_ABLATE_LS 0
-#endif
-
-#ifndef QT_ROLLOUT_PRIO
-#define QT_ROLLOUT_PRIO 0
-#endif
-#ifndef QT_ROLLOUT_PRIO_LO
-#define QT_ROLLOUT_PRIO_LO 0
-#endif
-
 #define QT_QP(a, b, c, d) ((a) | ((b) << 2) | ((c) << 4) | ((d) << 6))
 template <int CTRL>
 __device__ __forceinline__ float quad_perm(float v) {
@@ -84,10 +69,6 @@ struct QuadU {
   __device__ __forceinline__ explicit QuadU(float uo)
       : u0(quad_bcast<0>(uo)), u1(quad_bcast<1>(uo)), u2(quad_bcast<2>(uo)), u3(quad_bcast<3>(uo)) {}
 };
-
-#ifndef QT_RK4_STAGE_TRIG
-#define QT_RK4_STAGE_TRIG true
-#endif
 
 // time derivative of the own states xo = (p_a, v_a, angle_a, omega_a) given the quad's controls
 // sin / cos of the own angle at an RK4 stage point from the step's base values by angle addition: the stage angle is the base
@@ -153,13 +134,13 @@ __device__ __forceinline__ void quad_step(const LaneConst& L, const float* xo, c
   float k2[4], k3[4], k4[4], xs[4];
 #pragma unroll
   for (int g = 0; g < 4; ++g) xs[g] = fmaf(0.5f * dt, k1[g], xo[g]);
-  quad_rate<QT_RK4_STAGE_TRIG>(L, xs, uo, k2, tb);
+  quad_rate<true>(L, xs, uo, k2, tb);
 #pragma unroll
   for (int g = 0; g < 4; ++g) xs[g] = fmaf(0.5f * dt, k2[g], xo[g]);
-  quad_rate<QT_RK4_STAGE_TRIG>(L, xs, uo, k3, tb);
+  quad_rate<true>(L, xs, uo, k3, tb);
 #pragma unroll
   for (int g = 0; g < 4; ++g) xs[g] = fmaf(dt, k3[g], xo[g]);
-  quad_rate<QT_RK4_STAGE_TRIG>(L, xs, uo, k4, tb);
+  quad_rate<true>(L, xs, uo, k4, tb);
 #pragma unroll
   for (int g = 0; g < 4; ++g) xn[g] = xo[g] + (dt / 6.0f) * (k1[g] + 2.0f * k2[g] + 2.0f * k3[g] + k4[g]);
 }
@@ -302,7 +283,9 @@ __device__ __forceinline__ float gain_dot(const float4* K, const float* dx, floa
 }
 
 // One closed-loop rollout by a quad.  Returns this LANE's partial of sum_t L + Lf (fp64); quad_sum() gives the total.
-template <bool RK4, int PF, class Store>
+// PRIO: the state recurrence of a step at wave priority 1, the stage cost, the store and the loads that hang off it at 0
+// (rollout_quad.hip); without it the step runs at the caller's priority throughout and adds its stage cost ahead of the rate function.
+template <bool RK4, int PF, bool PRIO, class Store>
 __device__ __forceinline__ double quad_rollout_closed(const quattro_model_params& p, const LaneConst& L,
                                                       const NomSrc& src, float alpha, int N, bool counted, Store store) {
   // nominal data is requested PF steps ahead (PF register buffers, loop unrolled by PF): the loads come from HBM / the
@@ -318,40 +301,21 @@ __device__ __forceinline__ double quad_rollout_closed(const quattro_model_params
   for (int g = 0; g < 4; ++g) xh[g] = nb[0].x[g];
   double J = 0.0;
   auto step = [&](const NomLane& b, int t) __attribute__((always_inline)) {
-#if QT_ROLLOUT_PRIO != 0
-    __builtin_amdgcn_s_setprio(QT_ROLLOUT_PRIO);
-#endif
+    if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
     float dx[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) dx[g] = xh[g] - b.x[g];
-#if QT_ABLATE_LS != 1
     const float du = gain_dot(b.K, dx, b.k);
-#else
-    const float du = b.k + dx[0] * b.K[0].x;
-#endif
     const float uh = fmaf(alpha, du, b.u);
-#if QT_ROLLOUT_PRIO == 0
-#if QT_ABLATE_LS != 2
-    J += (double)lane_stage_cost(p, L, xh, uh, counted_mask);
-#endif
-#endif
+    if constexpr (!PRIO) J += (double)lane_stage_cost(p, L, xh, uh, counted_mask);
     float xnext[4];
     const QuadU U(uh);
-#if QT_ABLATE_LS != 3
     quad_step<RK4>(L, xh, U, xnext);
-#else
-    for (int g = 0; g < 4; ++g) xnext[g] = fmaf(L.dt, U.u0 + xh[(g + 1) & 3], xh[g]);
-#endif
-#if QT_ROLLOUT_PRIO != 0
-    // (experiment: the state recurrence at a higher wave priority than the cost, the store and the loads that hang off it)
-    __builtin_amdgcn_s_setprio(QT_ROLLOUT_PRIO_LO);
-    J += (double)lane_stage_cost(p, L, xh, uh, counted_mask);
-#endif
-#if QT_ABLATE_LS != 4
+    if constexpr (PRIO) {
+      __builtin_amdgcn_s_setprio(0);
+      J += (double)lane_stage_cost(p, L, xh, uh, counted_mask);
+    }
     store(L, t, U, xnext);
-#else
-    if (t == 0) store(L, t, U, xnext);
-#endif
 #pragma unroll
     for (int g = 0; g < 4; ++g) xh[g] = xnext[g];
   };
@@ -360,9 +324,7 @@ __device__ __forceinline__ double quad_rollout_closed(const quattro_model_params
 #pragma unroll
     for (int d = 0; d < PF; ++d) {
       step(nb[d], t + d);
-#if QT_ABLATE_LS != 5
       nb[d].load(src, t + d + PF < N ? t + d + PF : N - 1);
-#endif
     }
   }
 #pragma unroll
@@ -384,7 +346,6 @@ __device__ __forceinline__ void simulate_quad_body(const quattro_model_params& p
   const LaneConst L = lane_const(p, gid & 3);
   const float* ub = u + bb * N * NU + L.j;
   float* xo = x + bb * (N + 1) * NX + L.a;
-  float* xrow = x + bb * (N + 1) * NX + 4 * (L.j < 3 ? L.j : 0);      // this lane's 16-byte quarter of a state row
   float xh[4];
 #pragma unroll
   for (int g = 0; g < 4; ++g) xh[g] = x0[bb * NX + 3 * g + L.a];
@@ -401,24 +362,13 @@ __device__ __forceinline__ void simulate_quad_body(const quattro_model_params& p
   const unsigned long long live_mask = __builtin_amdgcn_ballot_w64(live);
   float u0 = ub[0], u1 = ub[(size_t)(N > 1 ? 1 : 0) * NU];
   auto step = [&](float ut, int t) __attribute__((always_inline)) {
-#if QT_ABLATE_LS != 2
     J += (double)lane_stage_cost(p, L, xh, ut, live_mask);
-#endif
     float xn[4];
     const QuadU U(ut);
-#if QT_ABLATE_LS != 3
     quad_step<RK4>(L, xh, U, xn);
-#else
-    for (int g = 0; g < 4; ++g) xn[g] = fmaf(L.dt, U.u0 + xh[(g + 1) & 3], xh[g]);
-#endif
-#if QT_ABLATE_LS != 4
-#ifdef QT_SIM_GATHER_STORE
-    const float4 row = gather_quarter(L, U, xn);
-    if (writer) *reinterpret_cast<float4*>(xrow + (size_t)(t + 1) * NX) = row;
-#else
     // Round 4: the lane's four states go out as they sit in its registers (x[t+1][3g + a], four dword stores).  The in-quad
     // transposition that made one 16-byte store per lane of them (gather_quarter: two DPP permutes and ten selects) was 27 %
-    // of this kernel by the ablation of scripts/ablate_linesearch.sh — a lone wave per SIMD pays for every instruction it issues,
+    // of this kernel by an ablation build (since removed) — a lone wave per SIMD pays for every instruction it issues,
     // and at 256 waves the request rate that made dword stores expensive in the line search (2048 waves) is no issue.
     // ... through buffer stores: the wave's 16 trajectories are one wave-uniform resource, the row a scalar offset, and a lane
     // that writes nothing (the quad's control lane, a lane past the batch) carries an out-of-range offset the range check drops.
@@ -428,10 +378,6 @@ __device__ __forceinline__ void simulate_quad_body(const quattro_model_params& p
 #pragma unroll
     for (int g = 0; g < 4; ++g)
       __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(xn[g]), rsx, vox, (t + 1) * (NX * 4) + 12 * g, 0);
-#endif
-#else
-    if (t == 0 && writer) *reinterpret_cast<float4*>(xrow + NX) = gather_quarter(L, U, xn);
-#endif
 #pragma unroll
     for (int g = 0; g < 4; ++g) xh[g] = xn[g];
   };
@@ -459,7 +405,7 @@ __device__ __forceinline__ void simulate_quad_body(const quattro_model_params& p
 // (x', u') in the scratch; after the ballot the trajectory's 32 lanes copy the accepted candidate over the nominal.
 // `gid` = 32 * trajectory + lane-in-trajectory for this lane (the 64 lanes of a wave hold two consecutive trajectories);
 // `force` treats every trajectory as active whatever its flag says (fixed-iteration benchmarking runs).
-template <bool RK4, int PF>
+template <bool RK4, int PF, bool PRIO>
 __device__ __forceinline__ void linesearch_quad_body(const quattro_model_params& p, float* x_nom, float* u_nom,
                                                      const float* __restrict__ K, const float* __restrict__ k,
                                                      const AlphaList& al, int n_alpha, int B, int N, double tol,
@@ -483,7 +429,7 @@ __device__ __forceinline__ void linesearch_quad_body(const quattro_model_params&
 #pragma unroll
   for (int i = 1; i < QUATTRO_MAX_ALPHAS; ++i) alpha = (aa == i) ? al.a[i] : alpha;
   const double J0 = live ? cost[bb] : 0.0;
-  double J = quad_rollout_closed<RK4, PF>(p, L, nom, alpha, N, mine, ScratchStore(L, sc + (size_t)aa * N * CS, mine));
+  double J = quad_rollout_closed<RK4, PF, PRIO>(p, L, nom, alpha, N, mine, ScratchStore(L, sc + (size_t)aa * N * CS, mine));
   J = quad_sum(J);
   const bool ok = mine && (J <= J0);     // false for NaN, like the reference's comparison
   // first accepted alpha among this trajectory's 8 quads (bit 4*ai of its 32-bit half of the ballot)
@@ -508,9 +454,8 @@ __device__ __forceinline__ void linesearch_quad_body(const quattro_model_params&
     const int slot = isx ? 4 * (e % 3) + e / 3 : e;
     float* dst = isx ? xn + NX + e : un + (e - 12);
     const int dstride = isx ? NX : NU;
-#if QT_ABLATE_LS != 6
     // COPY_U records per lane in flight: all of a block's loads are issued before its first store (a dword load / wait / store
-    // per record, as the plain loop compiles, is a round trip to L2 per four records: 10 % of the kernel by the ablation)
+    // per record, as the plain loop compiles, is a round trip to L2 per four records: 10 % of the kernel by ablation)
     constexpr int COPY_U = 13;
     for (int t0 = half; t0 < N; t0 += 2 * COPY_U) {
       float v[COPY_U];
@@ -525,9 +470,6 @@ __device__ __forceinline__ void linesearch_quad_body(const quattro_model_params&
         if (t < N) dst[(size_t)t * dstride] = v[q];
       }
     }
-#else
-    dst[0] = src[slot];
-#endif
     if (ai == first && L.j == 0) {
       cost[b] = J;
       if (active != nullptr && fabs(J0 - J) < tol) active[b] = 0;   // converged

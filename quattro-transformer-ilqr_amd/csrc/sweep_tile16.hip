@@ -42,45 +42,23 @@ __global__ __launch_bounds__(QT_WAVE * WPB, 4) void sweep_tile16_kernel(const fl
                                                                float* __restrict__ Kout, float* __restrict__ kout,
                                                                int32_t* __restrict__ status,
                                                                const int32_t* __restrict__ active,
-                                                               const FusedArgs fa QT_SWEEP_DBG_PARAM) {
+                                                               const FusedArgs fa) {
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int b = blockIdx.x * WPB + wv;
   const int lane = threadIdx.x & 63;
-  if (WPB > 1 && b >= fa.B) return;
+  if (b >= fa.B) return;
   if (active != nullptr && active[b] == 0) return;
   __shared__ __attribute__((aligned(16))) float s_t_all[WPB * 16 * LD];
   __shared__ __attribute__((aligned(16))) float s_vx_all[WPB * 64];
   // MODE_FUSED: [header record (TILE16) | FUSED_BATCH compact records (TILE16F)]
   constexpr int LIN_FLOATS = sweep_lin_floats<MODE>();
   __shared__ __attribute__((aligned(16))) float s_lin_all[WPB * LIN_FLOATS];
-#ifdef QT_SWEEP_PROFILE
-  sweep_tile16_body<MODE>(rec, VxN, VxxN, S, reg, Kout, kout, status, fa, b, lane, s_t_all + wv * 16 * LD, s_vx_all + wv * 64,
-                          s_lin_all + wv * LIN_FLOATS, dbg);
-#else
   sweep_tile16_body<MODE>(rec, VxN, VxxN, S, reg, Kout, kout, status, fa, b, lane, s_t_all + wv * 16 * LD, s_vx_all + wv * 64,
                           s_lin_all + wv * LIN_FLOATS);
-#endif
 }
 
 }  // namespace
 
-#ifdef QT_SWEEP_PROFILE
-extern "C" int quattro_sweep_profile(const float* rec, const float* VxN, const float* VxxN, int B, int S, float reg,
-                                     float* K, float* k, int compact, unsigned long long* dbg, void* stream) {
-  FusedArgs none{};
-  none.B = B;
-  none.k_rows = 0;
-  none.rn = 12;
-  none.rm = 4;
-  if (compact)
-    hipLaunchKernelGGL(sweep_tile16_kernel<MODE_COMPACT>, dim3((B + WPB - 1) / WPB), dim3(QT_WAVE * WPB), 0, (hipStream_t)stream, rec, VxN, VxxN, S,
-                       reg, K, k, nullptr, nullptr, none, dbg);
-  else
-    hipLaunchKernelGGL(sweep_tile16_kernel<MODE_TILE16>, dim3((B + WPB - 1) / WPB), dim3(QT_WAVE * WPB), 0, (hipStream_t)stream, rec, VxN, VxxN, S,
-                       reg, K, k, nullptr, nullptr, none, dbg);
-  return (int)hipGetLastError();
-}
-#else
 int quattro_launch_sweep_tile16(const float* rec, const float* VxN, const float* VxxN, int B, int S, float reg,
                                 float* K, float* k, int32_t* status, const int32_t* active, int layout, int n, int m,
                                 hipStream_t stream) {
@@ -145,4 +123,3 @@ int quattro_launch_sweep_fused_rk4(const quattro_model_params& p, const float* x
                      nullptr, N - t_start, reg, K, k, status, active, fa);
   return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;
 }
-#endif

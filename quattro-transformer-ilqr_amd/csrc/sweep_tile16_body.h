@@ -88,46 +88,16 @@ __device__ __forceinline__ void gj_step(float& R, const float S, int r, int c4, 
   R = (r == P) ? rowp * ip : fmaf(-f, rowp, R);
 }
 
-// Diagnostic build only (-DQT_ABLATE=n, scripts/ablate_sweep.sh): one segment of the step is left out (the numbers that come out are
-// wrong on purpose) so that the segment's REAL share of the time shows — at full load and for a lone wave — without stamps that
-// serialise what the hardware overlaps.  1: the four pivots; 2: the LDS transposition; 3: the three Q MFMAs; 4: the V' MFMA and the
-// V_x' row sum; 5: the stores of K, k.  The shipped library is built without it.
 // Wave priority along a step of the recursion (round 4).  A SIMD arbitrates vector issue between its resident waves by priority, then
 // age (MI355X_MICROARCH.md, "Two waves per SIMD"); the four waves it holds here sit at different points of their steps, and the
 // one inside the elimination — a chain of dependent cross-lane hops, reciprocals and row operations where every issue delay is
-// latency — should not queue behind another wave's run of MFMAs.  QT_SWEEP_PRIO = 1 (default): the four pivots at priority 2, the
-// rest of the step's chain (E, stores, V' product, row sum, LDS transposition, symmetrisation) at 1, the P / Q MFMA block at 0:
-// 64.9 -> 59.8 us at B = 4096, persistent loop 97.4 -> 90.8 us per iteration (A/B on one box; a lone wave pays ~1 us per
-// iteration for the three s_setprio per step).  Other placements measured: pivots only 60.7, pivots .. row sum 60.6, pivots .. end
-// of step 60.5, the MFMA block raised instead 64.0, three levels (pivots 3, transposition 2, rest 1) 60.1 us.  0 = none.
-#ifndef QT_SWEEP_PRIO
-#define QT_SWEEP_PRIO 1
-#endif
-#ifndef QT_ABLATE
-#define QT_ABLATE 0
-#endif
+// latency — should not queue behind another wave's run of MFMAs.  The four pivots run at priority 2, the rest of the step's
+// chain (E, stores, V' product, row sum, LDS transposition, symmetrisation) at 1, the P / Q MFMA block at 0: 64.9 -> 59.8 us at
+// B = 4096, persistent loop 97.4 -> 90.8 us per iteration (A/B on one box; a lone wave pays ~1 us per iteration for the three
+// s_setprio per step).  Other placements measured: pivots only 60.7, pivots .. row sum 60.6, pivots .. end of step 60.5, the MFMA
+// block raised instead 64.0, three levels (pivots 3, transposition 2, rest 1) 60.1 us.
 
 constexpr int LD = 20;  // LDS row pitch (floats) of the 16x16 transpose tile: 16-B aligned rows, conflict-free b128 writes
-
-// Diagnostic build only (-DQT_SWEEP_PROFILE, scripts/sweep_profile.sh): s_memtime deltas per phase of a step, summed over
-// the sweep by every wave; each stamp first forces the phase's result (a readfirstlane on it), so the deltas follow the
-// dependency chain.  The shipped library is built without it.
-#ifdef QT_SWEEP_PROFILE
-#define QT_SWEEP_DBG_PARAM , unsigned long long* __restrict__ dbg
-#define QT_PH(i, v)                                                          \
-  do {                                                                       \
-    __builtin_amdgcn_sched_barrier(0);                                       \
-    const int force_ = __builtin_amdgcn_readfirstlane(__float_as_int(v));    \
-    asm volatile("" ::"s"(force_));                                          \
-    const unsigned long long now_ = __builtin_amdgcn_s_memtime();            \
-    ph[i] += now_ - last;                                                    \
-    last = now_;                                                             \
-    __builtin_amdgcn_sched_barrier(0);                                       \
-  } while (0)
-#else
-#define QT_SWEEP_DBG_PARAM
-#define QT_PH(i, v)
-#endif
 
 // MODE_FUSED (Euler quadrotor): no record buffer at all.  The 76 state-dependent floats of a TILE16C record are functions
 // of (x_t, u_t) only, not of the value function, so the wave linearises its own trajectory ahead of the chain: 16 lanes
@@ -185,18 +155,11 @@ struct FusedArgs {
   int rn, rm;       // MODE_ROWPAD: the problem's own dimensions (records, terminal pair and gains are laid out for them)
 };
 
-#ifndef QT_SWEEP_WPB
-#define QT_SWEEP_WPB 2
-#endif
-constexpr int WPB = QT_SWEEP_WPB;   // trajectories (waves) per workgroup; the waves of a workgroup never synchronise
+constexpr int WPB = 2;   // trajectories (waves) per workgroup; the waves of a workgroup never synchronise
 __device__ __forceinline__ void wave_sync() {
-  if constexpr (WPB == 1) {
-    __syncthreads();   // single-wave workgroup: orders this wave's LDS traffic, no s_barrier is emitted
-  } else {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // The recursion for ONE trajectory `b`, run by one wavefront (`lane` = lane id); s_t (16 * LD floats), s_vx (64) and s_lin
@@ -334,7 +297,7 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
                                                   const float* __restrict__ VxxN, int S, float reg,
                                                   float* __restrict__ Kout, float* __restrict__ kout,
                                                   int32_t* __restrict__ status, const FusedArgs& fa, const int b,
-                                                  const int lane, float* s_t, float* s_vx, float* s_lin QT_SWEEP_DBG_PARAM) {
+                                                  const int lane, float* s_t, float* s_vx, float* s_lin) {
   constexpr bool ROWPAD = MODE == MODE_ROWPAD;
   constexpr bool COMPACT = MODE != MODE_TILE16 && !ROWPAD;   // constants of the problem in a header record
   constexpr int REC_STRIDE = MODE == MODE_TILE16 ? Tile16Rec::STRIDE : MODE == MODE_DENSEF ? Tile16RRec::STRIDE : Tile16CRec::STRIDE;
@@ -503,11 +466,6 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
   bool bad = false, illc = false;
   float pivmin = 3.0e38f;   // smallest |pivot| seen: 0 (or NaN-poisoned gains) marks a singular Q_uu + reg I
 
-#ifdef QT_SWEEP_PROFILE
-  unsigned long long ph[6] = {0, 0, 0, 0, 0, 0};
-  unsigned long long last = __builtin_amdgcn_s_memtime();
-  const unsigned long long t_begin = last;
-#endif
   // one step of the recursion on the record held in `cur`
   auto step = [&](const StepRegs& cur, int s) __attribute__((always_inline)) {
     // P = V_xx F   (tile rows 4r+s <-> x_{3r+s}; the control slot s = 3 contributes nothing)
@@ -524,21 +482,15 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
       Q = cur.lq;
       if (ucol) Q = f32x4{0.0f, 0.0f, 0.0f, sel4(g, cur.lq[0], cur.lq[1], cur.lq[2], cur.lq[3])};
     }
-#if QT_ABLATE != 3
     Q = __builtin_amdgcn_mfma_f32_16x16x4f32(cur.f0, P[0], Q, 0, 0, 0);
     Q = __builtin_amdgcn_mfma_f32_16x16x4f32(cur.f1, P[1], Q, 0, 0, 0);
     Q = __builtin_amdgcn_mfma_f32_16x16x4f32(cur.f2, P[2], Q, 0, 0, 0);
-#else
-    Q[0] += P[0]; Q[1] += P[1]; Q[2] += P[2]; Q[3] += P[3];
-#endif
     // q_z = l_z + F^T V_x comes out of the P product for free (round 4): the four tile rows 4r + 3 are the control slots of the
     // x' index, whose rows of V_xx are not data — the A operand of the lanes that own them (tile column c % 4 == 3) carries V_x
     // instead (vA_s = V_x[x_{3r+s}], see the symmetrisation below), so P[4r' + 3][c] = sum_i V_x[i] F[i][z(c)] lands in register 3
     // of EVERY lane group.  Those rows of P never enter Q (its k-steps use P[0..2] only).  This removes the separate
     // F^T V_x (3 multiply-adds and a 4-row sum through the LDS crossbar: 185 of a lone wave's 1 730 cycles per step).
-    QT_PH(0, Q[3]);
     const float qz = cur.lz + P[3];
-    QT_PH(1, qz);
 
     // (Q_uu + reg I)^-1 [Q_ux | Q_u] by Gauss-Jordan on the control rows
     const float q3 = Q[3];
@@ -550,54 +502,33 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
     // and after the last pivot lane (r, 3) holds (Q_uu + reg I)^-1 Q_u.  Same operations on Q_u as the separate register got
     // (bit-identical k), sixteen vector instructions fewer per step — the elimination is 23 % of the kernel.
     R = (c == 3) ? qu : R;
-#if QT_ABLATE != 1
-#if QT_SWEEP_PRIO
     __builtin_amdgcn_s_setprio(2);          // the pivots
-#endif
     gj_step<0, CHECK_PIVOTS>(R, R0, r, c4, pivmin, R0, illc);
     gj_step<1, CHECK_PIVOTS>(R, R, r, c4, pivmin, R0, illc);
     gj_step<2, CHECK_PIVOTS>(R, R, r, c4, pivmin, R0, illc);
     gj_step<3, CHECK_PIVOTS>(R, R, r, c4, pivmin, R0, illc);
-#else
-    R *= 0.01f;
-#endif
     // In the control columns of the tile the three values below are meaningless (they hold -I, Q_uu - reg I): they
     // are left as they are.  Every product that follows only ever combines state-column lanes with state-row
     // registers into the state-state entries that survive, so nothing is spent on zeroing the rest.
-#if QT_SWEEP_PRIO
     __builtin_amdgcn_s_setprio(1);          // the rest of the step's chain
-#endif
-    QT_PH(2, R);
     const float Kv = -R;                                  // K[r][j]; in tile column 3: k[r]
     const float kr = bcast_col<3>(Kv);                    // k[r] in every lane of group r
     const float E = fmaf(-reg, Kv, q3);                   // (Q_ux - reg K)[r][j]
     bad = bad || !qt_finite(Kv);                          // (covers k: it is column 3 of the same register)
 
     // outputs: K [m][n] row-major, k [m]
-#if QT_ABLATE != 5
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(Kv), rsK, voK, 4 * s * kK, 0);
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(Kv), rsk, vok, 4 * s * pm, 0);      // (tile column 3 of Kv is k)
-#else
-    if (s == 0) __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(Kv), rsK, voK, 0, 0);
-#endif
 
     // V_xx' = Q_xx + E^T K ; V_x' = Q_x + E^T k
-#if QT_ABLATE != 4
     f32x4 Vn = __builtin_amdgcn_mfma_f32_16x16x4f32(E, Kv, Q, 0, 0, 0);
     const float vxn = qz + sum_rows(E * kr, a16, a32);
-#else
-    f32x4 Vn = Q;
-    Vn[0] += E;
-    const float vxn = qz + E * kr;
-#endif
     // (control rows / columns of V_xx' hold leftovers of Q_xu, Q_uz: never read as state-state data below)
 
-    QT_PH(3, Vn[0] + vxn);
     // symmetrise through LDS: write the tile transposed, read it back in place.  (Needed: without the 1/2 (V + V^T) the
     // fp32 recursion is unstable — K off by 5 % after 50 steps.  Measured alternative: V'^T from four more MFMAs with the
     // operand roles swapped, no data movement at all — 101 vs 86 us, the MFMA pipe is the contended resource at 4 waves
     // per SIMD.)
-#if QT_ABLATE != 2
     wave_sync();
     *reinterpret_cast<f32x4*>(&s_t[c * LD + 4 * r]) = Vn;
     s_vx[lane] = vxn;        // (every lane into a slot of its own — s_vx has 64 floats, the first 16 are read: a store behind
@@ -607,18 +538,11 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
     const f32x4 vxq = *reinterpret_cast<const f32x4*>(&s_vx[4 * r]);
     asm volatile("" : "+v"(t0), "+v"(t1), "+v"(t2));      // (all three loads unconditional: left alone, the compiler sinks one of
                                                           //  them into an exec-masked block around the select below: a branch per step)
-#else
-    const float t0 = Vn[1], t1 = Vn[2], t2 = Vn[0];
-    const f32x4 vxq = f32x4{vxn, vxn * 0.5f, vxn * 0.25f, 0.0f};
-#endif
     // (control-slot columns: the A operand carries V_x there — it becomes the row of P that is q_z - l_z, see above)
     vA0 = ucol ? vxq[0] : 0.5f * (Vn[0] + t0);
     vA1 = ucol ? vxq[1] : 0.5f * (Vn[1] + t1);
     vA2 = ucol ? vxq[2] : 0.5f * (Vn[2] + t2);
-#if QT_SWEEP_PRIO
     __builtin_amdgcn_s_setprio(0);          // the next step's P / Q MFMA block (and the loads around it)
-#endif
-    QT_PH(4, vA0);
   };
 
   // record of local step `ls` (global step base + ls)
@@ -729,7 +653,6 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
   if constexpr (RK4F) {
     float* coef = fa.coef + (size_t)b * S * Rk4Coef::STRIDE;
     // (1) one lane per step: stage points -> coefficient records in the global scratch
-#ifndef QT_X_NO_PHASE1
     for (int c0 = 0; c0 < S; c0 += QT_WAVE) {
       const int ls = c0 + lane;
       if (ls < S) {
@@ -743,7 +666,6 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
         rk4_step_coefs(fa.p, xs, us, [&](int q, float4 v) __attribute__((always_inline)) { dst[(size_t)q * S] = v; });
       }
     }
-#endif
     // the records are read back by other lanes of this same wave: complete (written through to L2) before any is loaded
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -801,12 +723,6 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
   } else {
     run(S, 0);
   }
-#ifdef QT_SWEEP_PROFILE
-  if (lane == 0) {
-    for (int i = 0; i < 5; ++i) dbg[(size_t)b * 8 + i] = ph[i];
-    dbg[(size_t)b * 8 + 5] = __builtin_amdgcn_s_memtime() - t_begin;
-  }
-#endif
   const bool singular = !(pivmin > 0.0f);
   if (status != nullptr) {
     const bool any_bad = __any(bad);

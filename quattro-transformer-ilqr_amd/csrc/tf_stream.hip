@@ -142,24 +142,6 @@ __device__ __forceinline__ float relu1(float x) {
   return __int_as_float(b > 0 ? b : 0);
 }
 
-// Diagnostic build only (-DQT_TF_PROFILE, scripts/tf_profile.sh): every wave accumulates s_memtime deltas per phase
-// (and, separately, the cycles spent inside the ring rendezvous: counted wait + barrier) into a buffer of its own; the
-// shipped library is built without it and executes no stamp.
-#ifdef QT_TF_PROFILE
-#define QT_DBG_PARAM , unsigned long long* __restrict__ dbg
-#define QT_PH(i)                                               \
-  do {                                                         \
-    __builtin_amdgcn_sched_barrier(0);                         \
-    const unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
-    ph[i] += now_ - last_;                                     \
-    last_ = now_;                                              \
-    __builtin_amdgcn_sched_barrier(0);                         \
-  } while (0)
-#else
-#define QT_DBG_PARAM
-#define QT_PH(i)
-#endif
-
 // optional direct output of the prediction into gain stacks K [B][N][m][n], k [B][N][m] (quattro_tf_gains_bf16)
 struct TfGainsOut {
   float* K;
@@ -179,7 +161,7 @@ template <int NW, int FFMAX, class E>
 __global__ __launch_bounds__(64 * NW, 2) void tf_stream_kernel(const quattro_tf_weights W,
                                                                 const float* __restrict__ x_err,
                                                                 const float* __restrict__ prompt,
-                                                                float* __restrict__ pred, TfGainsOut go QT_DBG_PARAM) {
+                                                                float* __restrict__ pred, TfGainsOut go) {
   using Cfg = StreamCfg<NW, FFMAX>;
   using ex8 = typename Vec8<E>::type;
   constexpr int C = Cfg::C;
@@ -197,11 +179,6 @@ __global__ __launch_bounds__(64 * NW, 2) void tf_stream_kernel(const quattro_tf_
   const int n_panels = W.n_layers * tf_panels_per_layer(FF) + tf_out_panels(CD);
   const int pstride = tf_pstride(FF);
 
-#ifdef QT_TF_PROFILE
-  unsigned long long ph[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long last_ = __builtin_amdgcn_s_memtime(), rdv_ = 0;
-  const unsigned long long t_begin_ = last_;
-#endif
   const char* gw = reinterpret_cast<const char*>(W.w_stream) + (size_t)EMB_FRAGS * FRAG_B;   // panel 0
   const uint32_t ring_lds = lds_addr(s_ring);                // LDS byte address of the ring (LDS-DMA destination)
   const char* ring0 = s_ring + lane * 16;                    // this lane's 16 bytes of fragment 0 of slot 0
@@ -323,7 +300,6 @@ __global__ __launch_bounds__(64 * NW, 2) void tf_stream_kernel(const quattro_tf_
   // waits for ITS OWN copies of the next panel (all but the C (RING - 2) youngest), joins the workgroup barrier (every
   // wave's copies of that panel have then landed, and nobody reads the current panel's slot any more), requests
   // fragments 0..3 of the next panel, runs the last four MFMAs and refills the slot just freed.
-  QT_PH(0);                                                  // prologue: inputs, first copies issued, embeddings
   unsigned p = 0;                                            // panel being consumed
   ex8 fa[4];
   ring_rendezvous<C * (RING - 1)>();
@@ -341,15 +317,7 @@ __global__ __launch_bounds__(64 * NW, 2) void tf_stream_kernel(const quattro_tf_
     __builtin_amdgcn_sched_barrier(0);   // requested NOW: sunk to just before the rendezvous, their latency is a stall of its own
     static_for<0, 4>([&](auto ic) { mf(ic, fa[decltype(ic)::value]); });
     mid();
-#ifdef QT_TF_PROFILE
-    __builtin_amdgcn_sched_barrier(0);
-    const unsigned long long r0_ = __builtin_amdgcn_s_memtime();
-#endif
     ring_rendezvous<C * (RING - 2)>();
-#ifdef QT_TF_PROFILE
-    rdv_ += __builtin_amdgcn_s_memtime() - r0_;
-    __builtin_amdgcn_sched_barrier(0);
-#endif
     if (prefetch) {     // not ahead of a register-hungry phase (attention, LayerNorm): ring_load_fa() after it instead
 #pragma unroll
       for (int i = 0; i < 4; ++i) fa[i] = frag(nxt, i);
@@ -433,20 +401,8 @@ __global__ __launch_bounds__(64 * NW, 2) void tf_stream_kernel(const quattro_tf_
   for (int layer = 0; layer < W.n_layers; ++layer) {
     const float* par = s_par + (layer & 1) * Cfg::PSTRIDE_MAX;
     param_step(layer);
-    QT_PH(1);
-    // Last-layer pruning: an experiment, NOT in the shipped build (-DQT_TF_PRUNE_LAST_LAYER enables it).  Measured
-    // on one MI355X, B = 4096, three alternating runs each: 719 / 718 / 723 us with it against 700 / 699 / 700 us without —
-    // 2.7 % SLOWER (213 instead of 196 registers, a scalar branch around every MFMA group), results unchanged.  The output head reads only
-    // the T target tokens, so in the LAST layer a wave none of whose 32 tokens is a target (wave 0 of the shipped shapes:
-    // tokens 0..31 are states) only has to contribute its K and V tiles: its Q projection, attention, out-projection,
-    // LayerNorms and feed-forward are skipped.  It still walks every ring step (the weight stream and its barriers are the
-    // workgroup's), so the workgroup's own critical path does not move; what is freed is matrix / vector pipe time on that
-    // wave's SIMD for the co-resident workgroup.
-#ifdef QT_TF_PRUNE_LAST_LAYER
-    const bool idle = (layer == W.n_layers - 1) && (32 * (w + 1) <= L - T);
-#else
-    constexpr bool idle = false;
-#endif
+    // (every wave does every layer's work: skipping, in the last layer, what a wave without a target token only does for the
+    //  output head was built and measured 2.7 % slower — DESIGN.md §4.5)
     static_for<0, 4>([&](auto hc) {
       constexpr int h = decltype(hc)::value;
       char* xw = xch_w + (h & 1) * NW * 4 * FRAG_B;
@@ -454,7 +410,7 @@ __global__ __launch_bounds__(64 * NW, 2) void tf_stream_kernel(const quattro_tf_
       f32x16 qa, ka, va;
       // Q^T of head h (hd x tokens): W_q rows x X^T, bias as initial value
       ring_step([&] { qa = par_rows(par + P_BQ + 32 * h); },
-                [&](auto ic, ex8 f) { if (!idle) qa = mfma(f, Xb[decltype(ic)::value], qa); }, no_mid);
+                [&](auto ic, ex8 f) { qa = mfma(f, Xb[decltype(ic)::value], qa); }, no_mid);
       // K^T of head h, no bias; leaves as the A operand of S^T = K Q^T.  (Q is packed under K's first MFMAs.)
       ka = zero16();
       ring_step(no_hook, [&](auto ic, ex8 f) { ka = mfma(f, Xb[decltype(ic)::value], ka); },
@@ -472,9 +428,7 @@ __global__ __launch_bounds__(64 * NW, 2) void tf_stream_kernel(const quattro_tf_
                 false);
       *reinterpret_cast<ex8*>(xw + 2 * FRAG_B) = pack8<0, E>(va);
       *reinterpret_cast<ex8*>(xw + 3 * FRAG_B) = pack8<1, E>(va);
-      QT_PH(2);                                              // Q, K, V steps
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      QT_PH(3);                                              // exchange barrier
       // causal attention of this wave's 32 queries against the key tiles kt <= w, online softmax in base 2.  The scores
       // of tile kt + 1 are requested (two MFMAs) BEFORE the softmax arithmetic of tile kt, which then runs in their shadow.
       f32x16 O = zero16();
@@ -487,11 +441,10 @@ __global__ __launch_bounds__(64 * NW, 2) void tf_stream_kernel(const quattro_tf_
         f32x16 S = mfma(K0, Qp0, zero16());
         return mfma(K1, Qp1, S);                             // S^T tile: rows keys, columns queries
       };
-      f32x16 Sn = zero16();
-      if (!idle) Sn = scores(0);
+      f32x16 Sn = scores(0);
       static_for<0, NW>([&](auto kc) {
         constexpr int kt = decltype(kc)::value;
-        if (kt <= w && !idle) {
+        if (kt <= w) {
           f32x16 S = Sn;
           const char* xr = xch_tile(kt);
           const ex8 V0 = *reinterpret_cast<const ex8*>(xr + 2 * FRAG_B);
@@ -528,11 +481,10 @@ __global__ __launch_bounds__(64 * NW, 2) void tf_stream_kernel(const quattro_tf_
           O = mfma(V1, pack8<1, E>(S), O);
         }
       });
-      const float inv = idle ? 0.0f : 1.0f / add_halves(l);
+      const float inv = 1.0f / add_halves(l);
 #pragma unroll
       for (int r = 0; r < 16; ++r) O[r] *= inv;
       const ex8 Oh0 = pack8<0, E>(O), Oh1 = pack8<1, E>(O);
-      QT_PH(4);                                              // attention
       ring_load_fa();
       // this head's two k-steps of the out-projection, accumulated straight into the residual tiles; the step of
       // head h also adds the (folded) out-projection bias of feature tile h
@@ -544,13 +496,11 @@ __global__ __launch_bounds__(64 * NW, 2) void tf_stream_kernel(const quattro_tf_
           },
           [&](auto ic, ex8 f) {
             constexpr int i = decltype(ic)::value;
-            if (!idle) XT[i >> 1] = mfma(f, (i & 1) ? Oh1 : Oh0, XT[i >> 1]);
+            XT[i >> 1] = mfma(f, (i & 1) ? Oh1 : Oh0, XT[i >> 1]);
           },
           no_mid, h < 3);
-      QT_PH(5);                                              // out-projection step
     });
-    if (!idle) layer_norm(par + P_LN1G, par + P_LN1B, par + P_B2);      // XT = LN1(..) + b_2, Xb = bf16(LN1(..))
-    QT_PH(6);
+    layer_norm(par + P_LN1G, par + P_LN1B, par + P_B2);      // XT = LN1(..) + b_2, Xb = bf16(LN1(..))
     ring_load_fa();
 
     // -------------------------------------------------------------- feed-forward in hidden chunks of 32, LayerNorm 2
@@ -570,19 +520,19 @@ __global__ __launch_bounds__(64 * NW, 2) void tf_stream_kernel(const quattro_tf_
       // at the head of the MFMA chain), packing the previous chunk `Hp` under its first MFMAs; then W2 of the previous
       // chunk, during which the bias rows of the chunk after `Hn`'s are requested into `Hp`'s registers.
       auto pair = [&](f32x16& Hn, f32x16& Hp, int c_next_bias, bool last) {
-        ring_step(no_hook, [&](auto ic, ex8 f) { if (!idle) Hn = mfma(f, Xb[decltype(ic)::value], Hn); },
-                  [&] { if (!idle) h_pack(Hp); });
+        ring_step(no_hook, [&](auto ic, ex8 f) { Hn = mfma(f, Xb[decltype(ic)::value], Hn); },
+                  [&] { h_pack(Hp); });
         ring_step(no_hook,
                   [&](auto ic, ex8 f) {
                     constexpr int i = decltype(ic)::value;
-                    if (!idle) XT[i >> 1] = mfma(f, (i & 1) ? H1 : H0, XT[i >> 1]);
+                    XT[i >> 1] = mfma(f, (i & 1) ? H1 : H0, XT[i >> 1]);
                   },
                   [&] {
                     if (!last) Hp = par_rows(par + P_B1 + c_next_bias);
                   });
       };
       Ha = par_rows(par + P_B1);
-      ring_step(no_hook, [&](auto ic, ex8 f) { if (!idle) Ha = mfma(f, Xb[decltype(ic)::value], Ha); },
+      ring_step(no_hook, [&](auto ic, ex8 f) { Ha = mfma(f, Xb[decltype(ic)::value], Ha); },
                 [&] { Hb = par_rows(par + P_B1 + 32); });
       // FF is a multiple of 64: an odd number (FF / 32 - 1) of further chunks; two per trip, the last one peeled
       for (int c0 = 32; c0 + 32 < FF; c0 += 64) {
@@ -590,17 +540,15 @@ __global__ __launch_bounds__(64 * NW, 2) void tf_stream_kernel(const quattro_tf_
         pair(Ha, Hb, c0 + 64, false);                        // chunk c0 + 32 into Ha; pack chunk c0 (Hb); Hb <- bias of c0 + 64
       }
       pair(Hb, Ha, 0, true);                                 // last chunk FF - 32 into Hb; pack chunk FF - 64 (Ha)
-      if (!idle) h_pack(Hb);
+      h_pack(Hb);
       ring_step(no_hook,
                 [&](auto ic, ex8 f) {
                   constexpr int i = decltype(ic)::value;
-                  if (!idle) XT[i >> 1] = mfma(f, (i & 1) ? H1 : H0, XT[i >> 1]);
+                  XT[i >> 1] = mfma(f, (i & 1) ? H1 : H0, XT[i >> 1]);
                 },
                 no_mid, false);
     }
-    QT_PH(7);                                                // feed-forward steps
-    if (!idle) layer_norm(par + P_LN2G, par + P_LN2B, nullptr);         // (the parameter step that follows does not use fa)
-    QT_PH(8);
+    layer_norm(par + P_LN2G, par + P_LN2B, nullptr);         // (the parameter step that follows does not use fa)
   }
 
   // ------------------------------------------------------------------ output head on the last T tokens, de-normalised
@@ -649,16 +597,6 @@ __global__ __launch_bounds__(64 * NW, 2) void tf_stream_kernel(const quattro_tf_
     });
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // trailing (redundant) ring copies land before the LDS is released
-#ifdef QT_TF_PROFILE
-  QT_PH(9);                                                  // output head + stores
-  if (lane == 0) {
-    unsigned long long* d = dbg + ((size_t)blockIdx.x * NW + w) * 16;
-    for (int i = 0; i < 10; ++i) d[i] = ph[i];
-    d[10] = rdv_;
-    d[11] = __builtin_amdgcn_s_memtime() - t_begin_;
-    d[12] = __builtin_amdgcn_s_memrealtime();
-  }
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------ stream packing
@@ -779,15 +717,6 @@ int quattro_launch_tf_pack(const quattro_tf_weights& W, uint16_t* ws, float* ps,
   return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;
 }
 
-#ifdef QT_TF_PROFILE
-extern "C" int quattro_tf_stream_profile(const quattro_tf_weights* Wp, const float* x_err, const float* prompt, int B,
-                                         float* pred, unsigned long long* dbg, void* stream) {
-  const quattro_tf_weights& W = *Wp;
-  const TfGainsOut go{nullptr, nullptr, nullptr, 0, 0, 0};
-  hipLaunchKernelGGL((tf_stream_kernel<4, 512, __bf16>), dim3(B), dim3(256), 0, (hipStream_t)stream, W, x_err, prompt, pred, go, dbg);
-  return (int)hipGetLastError();
-}
-#else
 int quattro_launch_tf_stream(const quattro_tf_weights& W, const float* x_err, const float* prompt, int B, float* pred,
                              float* Kout, float* kout, const int32_t* active, int N, int n, int m, hipStream_t stream) {
   if (!stream_shape_ok(W) || W.w_stream == nullptr || W.p_stream == nullptr || W.tok_bias_t == nullptr)
@@ -816,4 +745,3 @@ int quattro_launch_tf_stream(const quattro_tf_weights& W, const float* x_err, co
 #undef QT_TF_LAUNCH
   return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;
 }
-#endif

@@ -12,8 +12,7 @@
 // v_mfma_f32_32x32x2_f32 (fp32 operands, fp32 accumulation: gradients agree with fp32 autograd to ~1e-6, so the tests can
 // be tight); the weight-gradient products reduce over all B L tokens and are split along that dimension across
 // workgroups (fp32 atomic accumulation).  Attention (L ~ 100, head dimension 32) runs one workgroup per (sequence, head)
-// out of LDS, on the same fp32 MFMA with transposed tiles whose accumulators feed the next product directly (a first
-// version on the vector ALUs is kept behind -DQT_ATTN_VALU).  This is not the inference hot path (that is tf_stream.hip, bf16): a training step at
+// out of LDS, on the same fp32 MFMA with transposed tiles whose accumulators feed the next product directly.  This is not the inference hot path (that is tf_stream.hip, bf16): a training step at
 // batch 256 is ~0.1 TFLOP and the target here is correctness first, then "not the bottleneck of fit()".
 //
 // Dropout masks are a counter hash of (seed, site, element index), recomputed wherever they are needed (forward and
@@ -192,19 +191,10 @@ void gemm_launch(hipStream_t st, const float* A, long sai, long sar, const float
 
 void gemm(hipStream_t st, const float* A, long sai, long sar, const float* B, long sbr, long sbj, float* C, long ldc,
           int M, int N, int K, const float* bias, int mode, float* arowsum = nullptr) {
-  // workgroups the problem yields with 128 x 128 / 128 x 64 tiles (a split reduction multiplies them further)
-  const long reduce_slices = mode == MODE_ATOMIC ? (K + 127) / 128 : 1;
-  const long big = (long)((M + 127) / 128) * ((N + 127) / 128) * reduce_slices;
-  const long mid = (long)((M + 127) / 128) * ((N + 63) / 64) * reduce_slices;
-  // Measured on one box (scripts/time_train.py, B = 256, whole step): 64 x 64 tiles only 3.37 ms, 128 x 64 allowed 3.92,
-  // 128 x 128 allowed 4.23 — the larger tiles need 179 / 237 registers (two waves per SIMD) and this kernel hides its
-  // load -> LDS -> MFMA phases by occupancy, not by a deeper pipeline.  The larger instantiations stay selectable.
-#ifndef QT_GEMM_MAXTILE
-#define QT_GEMM_MAXTILE 0
-#endif
-  if (QT_GEMM_MAXTILE >= 2 && big >= 512 && N > 64) gemm_launch<2, 2>(st, A, sai, sar, B, sbr, sbj, C, ldc, M, N, K, bias, mode, arowsum);
-  else if (QT_GEMM_MAXTILE >= 1 && mid >= 384) gemm_launch<2, 1>(st, A, sai, sar, B, sbr, sbj, C, ldc, M, N, K, bias, mode, arowsum);
-  else gemm_launch<1, 1>(st, A, sai, sar, B, sbr, sbj, C, ldc, M, N, K, bias, mode, arowsum);
+  // 64 x 64 tiles only.  Measured on one box (scripts/time_train.py, B = 256, whole step): 3.37 ms, with 128 x 64 tiles allowed
+  // 3.92, with 128 x 128 allowed 4.23 — the larger tiles need 179 / 237 registers (two waves per SIMD) and this kernel hides its
+  // load -> LDS -> MFMA phases by occupancy, not by a deeper pipeline.
+  gemm_launch<1, 1>(st, A, sai, sar, B, sbr, sbj, C, ldc, M, N, K, bias, mode, arowsum);
 }
 // Y[M][N] = X[M][K] W[N][K]^T + b
 void linear_fwd(hipStream_t st, const float* X, const float* W, const float* b, float* Y, int M, int N, int K) {
@@ -276,161 +266,15 @@ __global__ __launch_bounds__(256) void tail_scatter_kernel(const float* __restri
   }
 }
 
-// ------------------------------------------------------------------------------------------------ attention
-// One workgroup per (sequence, head).  softmax(Q K^T / sqrt(hd) + causal mask) V with dropout on the attention weights
-// (torch.nn.MultiheadAttention as configured at transformer_model.py:104-111).  Two adjacent lanes share a query row (a
-// key row in the second half of the backward): lane `half` takes the keys j = half, half + 2, ... and the pair combines
-// its partial maxima / sums / output rows with lane-pair exchanges, so the four waves of the workgroup cover rows
-// 0 .. 127 and the longest row costs (L + 1) / 2 iterations instead of L.
-constexpr int HD = 32, HDP = HD + 1, ATT_THREADS = 256, ATT_ROWS = ATT_THREADS / 2;
-
-__device__ __forceinline__ float pair_sum(float v) { return v + __shfl_xor(v, 1); }
-__device__ __forceinline__ float pair_max(float v) { return fmaxf(v, __shfl_xor(v, 1)); }
-
-__global__ __launch_bounds__(ATT_THREADS) void attn_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ Pout,
-                                                               float* __restrict__ out, int L, int d, int H, float scale,
-                                                               Drop dr, uint32_t site) {
-  extern __shared__ float sm[];
-  float* Ks = sm;                    // [L][HDP]
-  float* Vs = Ks + L * HDP;          // [L][HDP]
-  float* Ss = Vs + L * HDP;          // [L][L + 1]
-  const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const long row0 = (long)b * L;
-  for (int idx = tid; idx < L * HD; idx += ATT_THREADS) {
-    const int j = idx / HD, e = idx % HD;
-    const float* src = qkv + (row0 + j) * 3 * d + h * HD + e;
-    Ks[j * HDP + e] = src[d];
-    Vs[j * HDP + e] = src[2 * d];
-  }
-  __syncthreads();
-  const int i = tid >> 1, half = tid & 1;
-  const long pbase = ((long)b * H + h) * L * L;
-  if (i < L) {
-    float q[HD], o[HD];
-    const float* qs = qkv + (row0 + i) * 3 * d + h * HD;
-#pragma unroll
-    for (int e = 0; e < HD; ++e) { q[e] = qs[e] * scale; o[e] = 0.0f; }
-    float* S = Ss + i * (L + 1);
-    float mx = -3.0e38f;
-    for (int j = half; j <= i; j += 2) {
-      float sc = 0.0f;
-#pragma unroll
-      for (int e = 0; e < HD; ++e) sc = fmaf(q[e], Ks[j * HDP + e], sc);
-      S[j] = sc;
-      mx = fmaxf(mx, sc);
-    }
-    mx = pair_max(mx);
-    float sum = 0.0f;
-    for (int j = half; j <= i; j += 2) {
-      const float ex = expf(S[j] - mx);
-      S[j] = ex;
-      sum += ex;
-    }
-    const float inv = 1.0f / pair_sum(sum);
-    for (int j = half; j <= i; j += 2) {
-      const float p = S[j] * inv;
-      S[j] = p;
-      const float pd = p * keep_scale(dr, site, (uint64_t)(pbase + (long)i * L + j));
-#pragma unroll
-      for (int e = 0; e < HD; ++e) o[e] = fmaf(pd, Vs[j * HDP + e], o[e]);
-    }
-    for (int j = i + 1 + half; j < L; j += 2) S[j] = 0.0f;
-    float* od = out + (row0 + i) * d + h * HD;
-#pragma unroll
-    for (int e = 0; e < HD; ++e) {
-      const float v = pair_sum(o[e]);
-      if ((e & 1) == half) od[e] = v;
-    }
-  }
-  __syncthreads();
-  for (int idx = tid; idx < L * L; idx += ATT_THREADS) Pout[pbase + idx] = Ss[(idx / L) * (L + 1) + idx % L];
-}
-
-__global__ __launch_bounds__(ATT_THREADS) void attn_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ Pin,
-                                                               const float* __restrict__ dout, float* __restrict__ dqkv,
-                                                               int L, int d, int H, float scale, Drop dr, uint32_t site) {
-  extern __shared__ float sm[];
-  float* Qs = sm;                    // [L][HDP] each
-  float* Ks = Qs + L * HDP;
-  float* Vs = Ks + L * HDP;
-  float* Os = Vs + L * HDP;          // dO
-  float* Ps = Os + L * HDP;          // [L][L + 1]
-  float* Ds = Ps + L * (L + 1);      // [L][L + 1]  dS (already times scale)
-  const int h = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  const long row0 = (long)b * L;
-  const long pbase = ((long)b * H + h) * L * L;
-  for (int idx = tid; idx < L * HD; idx += ATT_THREADS) {
-    const int j = idx / HD, e = idx % HD;
-    const float* src = qkv + (row0 + j) * 3 * d + h * HD + e;
-    Qs[j * HDP + e] = src[0];
-    Ks[j * HDP + e] = src[d];
-    Vs[j * HDP + e] = src[2 * d];
-    Os[j * HDP + e] = dout[(row0 + j) * d + h * HD + e];
-  }
-  for (int idx = tid; idx < L * L; idx += ATT_THREADS) Ps[(idx / L) * (L + 1) + idx % L] = Pin[pbase + idx];
-  __syncthreads();
-  const int half = tid & 1;
-  const int i = tid >> 1;
-  if (i < L) {
-    float g[HD], dq[HD];
-#pragma unroll
-    for (int e = 0; e < HD; ++e) { g[e] = Os[i * HDP + e]; dq[e] = 0.0f; }
-    const float* P = Ps + i * (L + 1);
-    float* D = Ds + i * (L + 1);
-    float dot = 0.0f;
-    for (int j = half; j <= i; j += 2) {
-      float dpd = 0.0f;
-#pragma unroll
-      for (int e = 0; e < HD; ++e) dpd = fmaf(g[e], Vs[j * HDP + e], dpd);
-      const float dp = dpd * keep_scale(dr, site, (uint64_t)(pbase + (long)i * L + j));
-      D[j] = dp;
-      dot = fmaf(P[j], dp, dot);
-    }
-    dot = pair_sum(dot);
-    for (int j = half; j <= i; j += 2) {
-      const float ds = P[j] * (D[j] - dot) * scale;
-      D[j] = ds;
-#pragma unroll
-      for (int e = 0; e < HD; ++e) dq[e] = fmaf(ds, Ks[j * HDP + e], dq[e]);
-    }
-    float* dst = dqkv + (row0 + i) * 3 * d + h * HD;
-#pragma unroll
-    for (int e = 0; e < HD; ++e) {
-      const float v = pair_sum(dq[e]);
-      if ((e & 1) == half) dst[e] = v;
-    }
-  }
-  __syncthreads();
-  const int j = tid >> 1;
-  if (j < L) {
-    float dk[HD], dv[HD];
-#pragma unroll
-    for (int e = 0; e < HD; ++e) { dk[e] = 0.0f; dv[e] = 0.0f; }
-    for (int i2 = j + half; i2 < L; i2 += 2) {
-      const float ds = Ds[i2 * (L + 1) + j];
-      const float pd = Ps[i2 * (L + 1) + j] * keep_scale(dr, site, (uint64_t)(pbase + (long)i2 * L + j));
-#pragma unroll
-      for (int e = 0; e < HD; ++e) {
-        dk[e] = fmaf(ds, Qs[i2 * HDP + e], dk[e]);
-        dv[e] = fmaf(pd, Os[i2 * HDP + e], dv[e]);
-      }
-    }
-    float* dst = dqkv + (row0 + j) * 3 * d + h * HD;
-#pragma unroll
-    for (int e = 0; e < HD; ++e) {
-      const float vk = pair_sum(dk[e]), vv = pair_sum(dv[e]);
-      if ((e & 1) == half) { dst[d + e] = vk; dst[2 * d + e] = vv; }
-    }
-  }
-}
-
 // ------------------------------------------------------------------------------------------------ attention on the MFMA pipe
-// The same attention with every product on v_mfma_f32_32x32x2_f32 (fp32 operands).  One workgroup per (sequence, head),
+// softmax(Q K^T / sqrt(hd) + causal mask) V with dropout on the attention weights (torch.nn.MultiheadAttention as configured
+// at transformer_model.py:104-111), every product on v_mfma_f32_32x32x2_f32 (fp32 operands).  One workgroup per (sequence, head),
 // wave w owns the 32 queries of tile w; everything is computed TRANSPOSED (keys x queries), so a lane holds one query's
 // column: its keys sit in the 16 accumulator registers of each key tile — softmax statistics are sums over registers plus
 // one exchange between the two lane halves, and the probability tile is, as it stands, the B operand of the next product
 // (O^T = V^T P^T, dQ^T = K^T dS^T): nothing moves between the products.  The forward keeps only the row statistics
 // (max, 1 / sum) for the backward, which recomputes the probabilities (no [L][L] array in memory).
+constexpr int HD = 32, HDP = HD + 1;   // largest head dimension (one tile); LDS row pitch
 constexpr int LP = 128;   // padded sequence length: four tiles of 32 (rows >= L are zero)
 __device__ __forceinline__ int acc_row(int e, int hl) { return 8 * (e >> 2) + 4 * hl + (e & 3); }   // row held by register e
 __device__ __forceinline__ float half_max(float v) { return fmaxf(v, __shfl_xor(v, 32)); }
@@ -867,20 +711,14 @@ ParamOff param_offsets(const quattro_tf_train_desc& D) {
   return o;
 }
 
-// head dimensions the attention kernels take: up to one 32-wide tile (8, 16, 32 in practice); the vector-ALU version only 32
-bool head_dim_ok(int hd) {
-#ifndef QT_ATTN_VALU
-  return hd >= 1 && hd <= HD;
-#else
-  return hd == HD;
-#endif
-}
+// head dimensions the attention kernels take: up to one 32-wide tile (8, 16, 32 in practice)
+bool head_dim_ok(int hd) { return hd >= 1 && hd <= HD; }
 
 bool desc_ok(const quattro_tf_train_desc* D) {
   return D && D->state_dim > 0 && D->control_dim > 0 && D->d_model > 0 && D->d_model <= 64 * LN_MAXE &&
          D->nhead > 0 && D->d_model % D->nhead == 0 && head_dim_ok(D->d_model / D->nhead) && D->d_ff > 0 && D->n_layers > 0 &&
          D->n_layers <= QUATTRO_TF_MAX_LAYERS && D->n_state_tok > 0 && D->prompt_len > 0 && D->target_len > 0 &&
-         D->n_state_tok + D->prompt_len + D->target_len <= ATT_ROWS && D->dropout >= 0.0f && D->dropout < 1.0f;
+         D->n_state_tok + D->prompt_len + D->target_len <= LP && D->dropout >= 0.0f && D->dropout < 1.0f;
 }
 
 struct LayerWs {
@@ -912,11 +750,7 @@ Ws carve(const quattro_tf_train_desc& D, int Bn, char* base) {
   for (int l = 0; l < D.n_layers; ++l) {
     LayerWs& q = w.layer[l];
     q.qkv = take(M * 3 * d);
-#ifndef QT_ATTN_VALU
     q.P = take((size_t)Bn * D.nhead * L * 2);      // row statistics (max, 1 / sum) of the softmax
-#else
-    q.P = take((size_t)Bn * D.nhead * L * L);      // the probabilities themselves
-#endif
     q.ao = take(M * d);
     q.o = take(M * d);
     q.s1 = take(M * d);
@@ -944,8 +778,6 @@ Ws carve(const quattro_tf_train_desc& D, int Bn, char* base) {
   return w;
 }
 
-size_t attn_fwd_lds(int L) { return (size_t)(2 * L * HDP + L * (L + 1)) * sizeof(float); }
-size_t attn_bwd_lds(int L) { return (size_t)(4 * L * HDP + 2 * L * (L + 1)) * sizeof(float); }
 size_t attn_mfma_fwd_lds() { return (size_t)(3 * LP * HDP + 4 * 32 * HDP) * sizeof(float); }
 size_t attn_mfma_bwd_lds() { return (size_t)(4 * LP * HDP + 4 * 32 * HDP + 3 * LP) * sizeof(float); }
 
@@ -1016,15 +848,6 @@ int quattro_tf_train_step_f32(const quattro_tf_train_desc* D, const float* param
   const bool dropping = dr.p > 0.0f;
   auto site = [](int layer, int kind) { return (uint32_t)(1 + 4 * layer + kind); };   // 0: positions; per layer: attention
                                                                                        // weights, out-proj, ff hidden, ff out
-#ifdef QT_ATTN_VALU
-  if (attn_bwd_lds(L) > 160 * 1024) return QUATTRO_ERR_UNSUPPORTED;   // (the MFMA attention pads to 128 rows whatever L is)
-#endif
-#ifdef QT_ATTN_VALU
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                      (int)attn_fwd_lds(L));
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                      (int)attn_bwd_lds(L));
-#endif
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                       (int)attn_mfma_fwd_lds());
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1040,13 +863,8 @@ int quattro_tf_train_step_f32(const quattro_tf_train_desc* D, const float* param
     const LayerOff& q = po.layer[l];
     const LayerWs& a = w.layer[l];
     linear_fwd(st, hin, params + q.wqkv, params + q.bqkv, a.qkv, M, 3 * d, d);
-#ifndef QT_ATTN_VALU
     hipLaunchKernelGGL(attn_fwd_mfma_kernel, dim3(H, Bn), dim3(256), attn_mfma_fwd_lds(), st, a.qkv, a.P, a.ao, L, d, H, hd, scale, dr,
                        site(l, 0));
-#else
-    hipLaunchKernelGGL(attn_fwd_kernel, dim3(H, Bn), dim3(ATT_THREADS), attn_fwd_lds(L), st, a.qkv, a.P, a.ao, L, d, H, scale,
-                       dr, site(l, 0));
-#endif
     linear_fwd(st, a.ao, params + q.wo, params + q.bo, a.o, M, d, d);
     hipLaunchKernelGGL(ln_fwd_kernel, dim3((M + 3) / 4), dim3(256), 0, st, hin, a.o, a.s1, a.h1, a.mean1, a.rstd1,
                        params + q.g1, params + q.be1, M, d, dr, site(l, 1));
@@ -1108,13 +926,8 @@ int quattro_tf_train_step_f32(const quattro_tf_train_desc* D, const float* param
     }
     linear_bwd_weight(st, dob, a.ao, grads + q.wo, grads + q.bo, M, d, d);
     linear_bwd_input(st, dob, params + q.wo, w.dao, M, d, d, false);
-#ifndef QT_ATTN_VALU
     hipLaunchKernelGGL(attn_bwd_mfma_kernel, dim3(H, Bn), dim3(256), attn_mfma_bwd_lds(), st, a.qkv, a.P, a.ao, w.dao, w.dqkv, L, d,
                        H, hd, scale, dr, site(l, 0));
-#else
-    hipLaunchKernelGGL(attn_bwd_kernel, dim3(H, Bn), dim3(ATT_THREADS), attn_bwd_lds(L), st, a.qkv, a.P, w.dao, w.dqkv, L, d, H,
-                       scale, dr, site(l, 0));
-#endif
     linear_bwd_weight(st, w.dqkv, lin, grads + q.wqkv, grads + q.bqkv, M, 3 * d, d);
     // d(lin) = ds1 (residual, in dh) + dqkv Wqkv
     linear_bwd_input(st, w.dqkv, params + q.wqkv, w.dh, M, 3 * d, d, true);
