@@ -128,16 +128,21 @@ __device__ __forceinline__ CartpoleTerms cartpole_terms(const quattro_model_para
 struct QuadTrig {
   float sph, cph, sth, cth, sps, cps, tth, sec;
 };
-__device__ __forceinline__ QuadTrig quad_trig(float phi, float th, float psi) {
-  QuadTrig t;
-  qt_sincos(phi, &t.sph, &t.cph);
-  qt_sincos(th, &t.sth, &t.cth);
-  qt_sincos(psi, &t.sps, &t.cps);
+// sec and tan of theta from the sines and cosines (quad_trig's last part; the fused sweep evaluates the sines and cosines of
+// one step's three angles on two lanes and finishes here)
+__device__ __forceinline__ void quad_trig_finish(QuadTrig& t) {
   {  // 1 / cos(theta): hardware reciprocal + one Newton step (<= 1 ulp) instead of the ~10-instruction division
     const float y = __builtin_amdgcn_rcpf(t.cth);
     t.sec = fmaf(fmaf(-t.cth, y, 1.0f), y, y);
   }
   t.tth = t.sth * t.sec;
+}
+__device__ __forceinline__ QuadTrig quad_trig(float phi, float th, float psi) {
+  QuadTrig t;
+  qt_sincos(phi, &t.sph, &t.cph);
+  qt_sincos(th, &t.sth, &t.cth);
+  qt_sincos(psi, &t.sps, &t.cps);
+  quad_trig_finish(t);
   return t;
 }
 
@@ -322,12 +327,21 @@ struct EulerRecord<QUATTRO_MODEL_QUADROTOR, L> {
   }
   static __device__ __forceinline__ void fill_state(float* rec, const quattro_model_params& p, const float* x,
                                                     const float* u) {
-    // no implicit fma contraction here: the same entries are produced through different offset maps (TILE16, TILE16C,
-    // ROWMAJOR) in different kernels, and they must come out bit-identical (explicit fmaf calls stay fused)
+    fill_dynamics(rec, p, quad_trig(x[6], x[7], x[8]), x, u);
+    fill_lx(rec, p, x);
+#pragma unroll
+    for (int a = 0; a < 4; ++a) fill_control(rec, p, a, p.r[a], u[a]);
+  }
+  // fill_state in parts that write exactly its entries with the same expressions (the fused sweep runs them on two lanes
+  // per step): [A | B] at (x, u) from the sines and cosines of the Euler angles; l_x; l_u and l_uu of one control a, whose
+  // index and weight r_a = p.r[a] may differ from lane to lane.
+  // No implicit fma contraction in any of them: the same entries are produced through different offset maps (TILE16,
+  // TILE16C, ROWMAJOR) in different kernels, and they must come out bit-identical (explicit fmaf calls stay fused).
+  static __device__ __forceinline__ void fill_dynamics(float* rec, const quattro_model_params& p, const QuadTrig& t,
+                                                       const float* x, const float* u) {
 #pragma clang fp contract(off)
     const float mass = p.phys[0], Ix = p.phys[1], Iy = p.phys[2], Iz = p.phys[3];
     const float dt = p.dt;
-    const QuadTrig t = quad_trig(x[6], x[7], x[8]);
     const float wp = x[9], wq = x[10], wr = x[11];
     const float tm = (u[0] + u[1] + u[2] + u[3]) / mass;
     const float rx = t.sps * t.sph + t.cps * t.sth * t.cph;
@@ -370,19 +384,22 @@ struct EulerRecord<QUATTRO_MODEL_QUADROTOR, L> {
     rec[L::a(10, 11)] = dt * c2 * wp;
     rec[L::a(11, 9)] = dt * c3 * wq;
     rec[L::a(11, 10)] = dt * c3 * wp;
+  }
+  static __device__ __forceinline__ void fill_lx(float* rec, const quattro_model_params& p, const float* x) {
+#pragma clang fp contract(off)
 #pragma unroll
     for (int i = 0; i < 12; ++i) rec[L::lx(i)] = 2.0f * p.q[i] * (x[i] - p.x_ref[i]);
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      float lu = 2.0f * p.r[a] * u[a], luu = 2.0f * p.r[a];
-      if (p.barrier_alpha != 0.0f) {
-        const float sp = qt_softplus(-u[a], p.barrier_beta), sg = qt_sigmoid(-p.barrier_beta * u[a]);
-        lu = fmaf(p.barrier_alpha, -2.0f * sp * sg, lu);
-        luu = fmaf(p.barrier_alpha, 2.0f * sg * sg + 2.0f * sp * p.barrier_beta * sg * (1.0f - sg), luu);
-      }
-      rec[L::lu(a)] = lu;
-      rec[L::luu(a, a)] = luu;
+  }
+  static __device__ __forceinline__ void fill_control(float* rec, const quattro_model_params& p, int a, float ra, float ua) {
+#pragma clang fp contract(off)
+    float lu = 2.0f * ra * ua, luu = 2.0f * ra;
+    if (p.barrier_alpha != 0.0f) {
+      const float sp = qt_softplus(-ua, p.barrier_beta), sg = qt_sigmoid(-p.barrier_beta * ua);
+      lu = fmaf(p.barrier_alpha, -2.0f * sp * sg, lu);
+      luu = fmaf(p.barrier_alpha, 2.0f * sg * sg + 2.0f * sp * p.barrier_beta * sg * (1.0f - sg), luu);
     }
+    rec[L::lu(a)] = lu;
+    rec[L::luu(a, a)] = luu;
   }
 };
 

@@ -100,8 +100,8 @@ __device__ __forceinline__ void gj_step(float& R, const float S, int r, int c4, 
 constexpr int LD = 20;  // LDS row pitch (floats) of the 16x16 transpose tile: 16-B aligned rows, conflict-free b128 writes
 
 // MODE_FUSED (Euler quadrotor): no record buffer at all.  The 76 state-dependent floats of a TILE16C record are functions
-// of (x_t, u_t) only, not of the value function, so the wave linearises its own trajectory ahead of the chain: 16 lanes
-// produce the records of 16 steps at a time into an LDS stage (the SAME fill_const / fill_state code as
+// of (x_t, u_t) only, not of the value function, so the wave linearises its own trajectory ahead of the chain: two lanes
+// per step produce the records of FUSED_BATCH steps at a time into an LDS stage (the SAME fill_const / fill_state code as
 // linearize_compact_kernel: bit-identical records), the constants of the problem sit once in an LDS header record, and
 // the recursion reads both exactly as the TILE16C kernel reads its record buffer.  Per step 64 B (x_t, u_t) come from
 // HBM instead of 304 B, and the separate linearisation launch (and its 62 MB of record writes) is gone; the terminal
@@ -325,10 +325,14 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
     vx1 = 2.0f * fa.p.qf[3 * r + 1] * (xN[3 * r + 1] - fa.p.x_ref[3 * r + 1]);
     vx2 = 2.0f * fa.p.qf[3 * r + 2] * (xN[3 * r + 2] - fa.p.x_ref[3 * r + 2]);
     if constexpr (FUSED) {
-      // the constants of the problem, once
-      for (int i = lane; i < Tile16Rec::STRIDE; i += QT_WAVE) s_lin[i] = 0.0f;
+      // the constants of the problem, once: the header record, and the constant image (zeros, fill_const) of every stage
+      // slot — a refill runs fill_state only, which writes the same entries of a slot every time
+      static_assert(sweep_lin_floats<MODE>() % 4 == 0, "the LDS slice is zeroed in 16-byte pieces");
+      for (int i = lane; i < sweep_lin_floats<MODE>() / 4; i += QT_WAVE) reinterpret_cast<f32x4*>(s_lin)[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
       wave_sync();
       if (lane == 0) EulerRecord<QUATTRO_MODEL_QUADROTOR, Tile16Rec>::fill_const(s_lin, fa.p);
+      if (lane < FUSED_BATCH)
+        EulerRecord<QUATTRO_MODEL_QUADROTOR, Tile16FRec>::fill_const(s_lin + Tile16Rec::STRIDE + lane * Tile16FRec::STRIDE, fa.p);
       wave_sync();
     }
   } else if constexpr (ROWPAD) {
@@ -689,12 +693,23 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
     }
   } else if constexpr (FUSED) {
     float* stage = s_lin + Tile16Rec::STRIDE;
-    // (x_t, u_t) of a batch's steps, one step per lane: requested a whole batch ahead (the loads of batch j - 1 fly while
-    // the 16 steps of batch j run; waiting for them at the refill would expose an HBM round trip four times per sweep)
+    // Two lanes per stage slot, lane sl and lane sl + 32: one writes the dynamics entries, the other l_x, and each writes
+    // l_u / l_uu of two of the four controls.  The wave issues both lanes' code one after the other where it differs (a
+    // divergent branch is not parallel); what is parallel is the code they share: the four controls' barrier terms (two per
+    // lane instead of four) and the sines and cosines (phi and theta on the dynamics lane, psi on the other: two rounds of
+    // qt_sincos instead of three, psi's pair over the LDS crossbar).  Slots 0-12 have their dynamics lane in lanes 0-31 and
+    // slots 13-24 in lanes 32-63, so that the stores of either part reach each 32-lane half at most twice per bank
+    // (pitch 68: slots sl and sl + 8 share a bank); with one part in one half they were 4-way conflicts.
+    const int sl = lane & 31;
+    const bool dynl = (lane < 32) == (sl < 13);
+    const int ca = dynl ? 0 : 2;                                   // this lane's two controls: ca, ca + 1
+    const float ra0 = dynl ? fa.p.r[0] : fa.p.r[2], ra1 = dynl ? fa.p.r[1] : fa.p.r[3];
+    // (x_t, u_t) of a batch's steps, both lanes of a slot: requested a whole batch ahead (the loads of batch j - 1 fly while
+    // the steps of batch j run; waiting for them at the refill would expose an HBM round trip twice per sweep)
     float4 xa, xb, xc, ua;
     auto fetch = [&](int base) __attribute__((always_inline)) {
       const int cnt = S - base < FUSED_BATCH ? S - base : FUSED_BATCH;
-      const int t = fa.t_start + base + (lane < cnt ? lane : 0);
+      const int t = fa.t_start + base + (sl < cnt ? sl : 0);
       const float4* px = reinterpret_cast<const float4*>(fa.x + ((size_t)b * (fa.N + 1) + t) * 12);
       xa = px[0];
       xb = px[1];
@@ -706,15 +721,29 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
     for (int base = top; base >= 0; base -= FUSED_BATCH) {
       const int cnt = S - base < FUSED_BATCH ? S - base : FUSED_BATCH;
       wave_sync();                                       // the previous batch's records are no longer read
-      if (lane < cnt) {
+      {
+        using ER = EulerRecord<QUATTRO_MODEL_QUADROTOR, Tile16FRec>;
         const float xs[12] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w, xc.x, xc.y, xc.z, xc.w};
         const float us[4] = {ua.x, ua.y, ua.z, ua.w};
-        float* mine = stage + lane * Tile16FRec::STRIDE;
-        // exactly linearize_compact_kernel's sequence (a dynamic lane's triple may hold constants and structural zeros)
-#pragma unroll
-        for (int i = 0; i < Tile16FRec::SIZE / 4; ++i) reinterpret_cast<float4*>(mine)[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        EulerRecord<QUATTRO_MODEL_QUADROTOR, Tile16FRec>::fill_const(mine, fa.p);
-        EulerRecord<QUATTRO_MODEL_QUADROTOR, Tile16FRec>::fill_state(mine, fa.p, xs, us);
+        // (all 64 lanes: the lanes past cnt hold a real step's (x, u), and the crossbar hop wants every lane active)
+        QuadTrig tr;
+        qt_sincos(dynl ? xs[6] : xs[8], &tr.sph, &tr.cph);
+        qt_sincos(xs[7], &tr.sth, &tr.cth);
+        tr.sps = __int_as_float(__builtin_amdgcn_ds_bpermute(a32, __float_as_int(tr.sph)));
+        tr.cps = __int_as_float(__builtin_amdgcn_ds_bpermute(a32, __float_as_int(tr.cph)));
+        if (sl < cnt) {
+          // fill_state's entries, over the constant image of the slot (the dynamic lanes' triples hold constants and
+          // structural zeros too: what linearize_compact_kernel writes, bit for bit)
+          float* mine = stage + sl * Tile16FRec::STRIDE;
+          if (dynl) {
+            quad_trig_finish(tr);
+            ER::fill_dynamics(mine, fa.p, tr, xs, us);
+          } else {
+            ER::fill_lx(mine, fa.p, xs);
+          }
+          ER::fill_control(mine, fa.p, ca, ra0, dynl ? us[0] : us[2]);
+          ER::fill_control(mine, fa.p, ca + 1, ra1, dynl ? us[1] : us[3]);
+        }
       }
       if (base > 0) fetch(base - FUSED_BATCH);
       wave_sync();
