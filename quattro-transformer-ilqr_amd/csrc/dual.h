@@ -8,7 +8,12 @@
 #pragma once
 #include <type_traits>
 
+#ifdef QT_DUAL_HOST   // a host build of this header alone (tests): the including file supplies qt_sincos and qt_softplus
+#define __device__
+#define __forceinline__ inline
+#else
 #include "models_device.h"
+#endif
 
 namespace qtad {
 
@@ -62,9 +67,8 @@ QT_AR __device__ __forceinline__ Dual<T>& operator/=(Dual<T>& a, S s) { a = a / 
   template <class T> __device__ __forceinline__ bool operator op(const Dual<T>& a, const Dual<T>& b) { return primal(a) op primal(b); } \
   QT_AR __device__ __forceinline__ bool operator op(const Dual<T>& a, S s) { return primal(a) op (float)s; }             \
   QT_AR __device__ __forceinline__ bool operator op(S s, const Dual<T>& a) { return (float)s op primal(a); }
-QT_CMP(<) QT_CMP(>) QT_CMP(<=) QT_CMP(>=)
+QT_CMP(<) QT_CMP(>) QT_CMP(<=) QT_CMP(>=) QT_CMP(==) QT_CMP(!=)
 #undef QT_CMP
-#undef QT_AR
 
 // elementary functions: float versions first (a model's rollout code and its differentiated code call the same names)
 __device__ __forceinline__ float sin(float x) { float s, c; qt_sincos(x, &s, &c); return s; }
@@ -105,10 +109,19 @@ template <class T> __device__ __forceinline__ Dual<T> atan(const Dual<T>& a) { r
 template <class T> __device__ __forceinline__ Dual<T> fabs(const Dual<T>& a) { return primal(a) < 0.0f ? -a : a; }
 template <class T> __device__ __forceinline__ Dual<T> abs(const Dual<T>& a) { return fabs(a); }
 template <class T> __device__ __forceinline__ Dual<T> pow(const Dual<T>& a, float e) {   // constant exponent
+  // e = 0 and e = 1 have finite derivatives at a zero base, where the general rule forms pow(0, -1) * 0 = inf * 0 (e = 1
+  // reaches it one level of nesting down, through pow(a.v, 0)); away from zero both branches give what the general rule gives
+  if (e == 0.0f) return {pow(a.v, e), a.d * 0.0f};
+  if (e == 1.0f) return {pow(a.v, e), a.d};
   return {pow(a.v, e), pow(a.v, e - 1.0f) * e * a.d};
 }
+// a tie takes the first argument's branch
 template <class T> __device__ __forceinline__ Dual<T> fmax(const Dual<T>& a, const Dual<T>& b) { return primal(a) >= primal(b) ? a : b; }
 template <class T> __device__ __forceinline__ Dual<T> fmin(const Dual<T>& a, const Dual<T>& b) { return primal(a) <= primal(b) ? a : b; }
+QT_AR __device__ __forceinline__ Dual<T> fmax(const Dual<T>& a, S s) { return fmax(a, Dual<T>(s)); }
+QT_AR __device__ __forceinline__ Dual<T> fmax(S s, const Dual<T>& a) { return fmax(Dual<T>(s), a); }
+QT_AR __device__ __forceinline__ Dual<T> fmin(const Dual<T>& a, S s) { return fmin(a, Dual<T>(s)); }
+QT_AR __device__ __forceinline__ Dual<T> fmin(S s, const Dual<T>& a) { return fmin(Dual<T>(s), a); }
 template <class T> __device__ __forceinline__ Dual<T> square(const Dual<T>& a) { return a * a; }
 template <class T> __device__ __forceinline__ Dual<T> softplus(const Dual<T>& z, float beta) {
   // d/dz softplus_beta(z) = sigmoid(beta z); written through exp / log so that every level of nesting differentiates it
@@ -116,5 +129,7 @@ template <class T> __device__ __forceinline__ Dual<T> softplus(const Dual<T>& z,
   const Dual<T> e = exp(-fabs(bz));
   return (fmax(bz, Dual<T>(0.0f)) + log(e + 1.0f)) / beta;
 }
+
+#undef QT_AR
 
 }  // namespace qtad

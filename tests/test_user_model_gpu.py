@@ -147,6 +147,20 @@ def complex_step_jac(fun, z, h=1e-30):
     return np.array(cols).T
 
 
+# branch-on-real-part versions of the kinked functions, for complex-step differentiation through a model that uses them
+# (ties as in csrc/dual.h: fabs(0) = +z, fmax / fmin take the first argument)
+def cs_fabs(z):
+    return -z if np.real(z) < 0 else z
+
+
+def cs_fmax(a, b):
+    return a if np.real(a) >= np.real(b) else b
+
+
+def cs_fmin(a, b):
+    return a if np.real(a) <= np.real(b) else b
+
+
 def exact_derivs(f, L, x, u):
     n, m = x.size, u.size
     z = np.concatenate([x, u])
