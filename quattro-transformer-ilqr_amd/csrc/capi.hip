@@ -407,7 +407,7 @@ SolveLoop solve_loop(const quattro_model_params& p, const float* x0, float* x_no
   c.active = active;
   c.iters = iters;
   c.status = status;
-  for (int i = 0; i < QUATTRO_MAX_ALPHAS; ++i) c.al.a[i] = i < n_alpha ? alphas[i] : 0.0f;
+  c.al = make_alpha_list(alphas, n_alpha);
   c.n_alpha = n_alpha;
   c.B = B;
   c.N = N;

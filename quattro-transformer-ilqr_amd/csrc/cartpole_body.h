@@ -35,32 +35,22 @@ __device__ __forceinline__ void cartpole_record(const quattro_model_params& p, c
   if constexpr (!RK4) {
     EulerRecord<MODEL, R>::fill_const(rec, p);
     EulerRecord<MODEL, R>::fill_state(rec, p, xs, us);
-  } else {                                                 // linearize_rk4_kernel, one direction after the other
-    const float dt = p.dt;
+  } else {                        // the stage points once, then the five unit directions through them, one after the other (rk4.h)
+    float xp[4][NX];
+    rk4_points<NX>(p.dt, xs, xp, [&](int, const float* xst, float* k) __attribute__((always_inline)) { qt_rate<MODEL>(p, xst, us, k); });
 #pragma unroll
     for (int j = 0; j < NZ; ++j) {
-      float dx0[NX], du[NU], k[NX], dk[NX], xst[NX], dxs[NX], acc[NX];
+      float dx0[NX], du[NU], col[NX];
 #pragma unroll
       for (int i = 0; i < NX; ++i) dx0[i] = (i == j) ? 1.0f : 0.0f;
       du[0] = (j == NX) ? 1.0f : 0.0f;
-      qt_rate<MODEL>(p, xs, us, k);
-      qt_rate_jvp<MODEL>(p, xs, us, dx0, du, dk);
-#pragma unroll
-      for (int i = 0; i < NX; ++i) { acc[i] = dk[i]; xst[i] = fmaf(0.5f * dt, k[i], xs[i]); dxs[i] = fmaf(0.5f * dt, dk[i], dx0[i]); }
-      qt_rate<MODEL>(p, xst, us, k);
-      qt_rate_jvp<MODEL>(p, xst, us, dxs, du, dk);
-#pragma unroll
-      for (int i = 0; i < NX; ++i) { acc[i] = fmaf(2.0f, dk[i], acc[i]); xst[i] = fmaf(0.5f * dt, k[i], xs[i]); dxs[i] = fmaf(0.5f * dt, dk[i], dx0[i]); }
-      qt_rate<MODEL>(p, xst, us, k);
-      qt_rate_jvp<MODEL>(p, xst, us, dxs, du, dk);
-#pragma unroll
-      for (int i = 0; i < NX; ++i) { acc[i] = fmaf(2.0f, dk[i], acc[i]); xst[i] = fmaf(dt, k[i], xs[i]); dxs[i] = fmaf(dt, dk[i], dx0[i]); }
-      qt_rate_jvp<MODEL>(p, xst, us, dxs, du, dk);
+      rk4_tangent<NX>(p.dt, dx0, col, [&](int s, const float* dxs, float* dk) __attribute__((always_inline)) {
+        qt_rate_jvp<MODEL>(p, xp[s], us, dxs, du, dk);
+      });
 #pragma unroll
       for (int i = 0; i < NX; ++i) {
-        const float v = fmaf(dt / 6.0f, acc[i] + dk[i], dx0[i]);
-        if (j < NX) rec[R::a(i, j < NX ? j : 0)] = v;
-        else rec[R::b(i, 0)] = v;
+        if (j < NX) rec[R::a(i, j < NX ? j : 0)] = col[i];
+        else rec[R::b(i, 0)] = col[i];
       }
     }
     fill_cost_entries<MODEL, R>(rec, p, xs, us);
@@ -147,14 +137,14 @@ __device__ __forceinline__ void sweep16_cartpole_body(const quattro_model_params
   for (int k = 0; k < 4; ++k) gat[k] = 4 * (row0 + 4 * k + j);
   const int tra = 4 * (row0 + 4 * j + i);                  // the transposed lane (j, i)
 
-  // terminal pair: V_x(N) = 2 Qf (x_N - x_ref), V_xx(N) = 2 Qf, used as given
+  // terminal pair (V_x(N), V_xx(N) = 2 Qf), used as given
   float Vij, vx[NX];
   {
     const float4 xN = px[N];
     const float xn[NX] = {xN.x, xN.y, xN.z, xN.w};
 #pragma unroll
-    for (int c = 0; c < NX; ++c) vx[c] = 2.0f * p.qf[c] * (xn[c] - p.x_ref[c]);
-    Vij = (i == j) ? 2.0f * p.qf[i] : 0.0f;
+    for (int c = 0; c < NX; ++c) vx[c] = qt_terminal_vx(p, c, xn[c]);
+    Vij = (i == j) ? qt_terminal_vxx(p, i) : 0.0f;
   }
   bool bad = false, singular = false;
 

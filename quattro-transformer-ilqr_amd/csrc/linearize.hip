@@ -112,17 +112,17 @@ __global__ __launch_bounds__(LIN_THREADS) void linearize_compact_kernel(const qu
     EulerRecord<MODEL, L>::fill_const(mine, p);
     EulerRecord<MODEL, L>::fill_state(mine, p, xs, us);
     if (t == N - 1 && VxN != nullptr) {
-      // the item of a trajectory's last step also writes the terminal pair V_x(N) = 2 Qf (x_N - x_ref), V_xx(N) = 2 Qf
-      // (the values terminal_kernel produces; one launch less per iteration)
+      // the item of a trajectory's last step also writes the terminal pair (qt_terminal_vx / qt_terminal_vxx, as terminal_kernel
+      // does; one launch less per iteration)
       float* vx = VxN + (size_t)b * NX;
       float4* vxx = reinterpret_cast<float4*>(VxxN + (size_t)b * NX * NX);
 #pragma unroll
-      for (int i = 0; i < NX; ++i) vx[i] = 2.0f * p.qf[i] * (px[NX + i] - p.x_ref[i]);
+      for (int i = 0; i < NX; ++i) vx[i] = qt_terminal_vx(p, i, px[NX + i]);
 #pragma unroll
       for (int i = 0; i < NX; ++i) {
 #pragma unroll
         for (int j4 = 0; j4 < NX / 4; ++j4) {
-          const float d = 2.0f * p.qf[i];
+          const float d = qt_terminal_vxx(p, i);
           vxx[i * (NX / 4) + j4] = make_float4(i == 4 * j4 ? d : 0.0f, i == 4 * j4 + 1 ? d : 0.0f,
                                                i == 4 * j4 + 2 ? d : 0.0f, i == 4 * j4 + 3 ? d : 0.0f);
         }
@@ -138,7 +138,7 @@ __global__ __launch_bounds__(LIN_THREADS) void linearize_compact_kernel(const qu
 }
 
 // RK4 discretisation: column j of [A | B] = d x_next / d z_j is the forward-mode derivative of the four-stage step along
-// the unit direction e_j (zero-order-hold u): LPI lanes per (b,t) item, lane j pushes direction j through the stages with
+// the unit direction e_j (zero-order-hold u): LPI lanes per (b,t) item, lane j pushes direction j through the stages (rk4.h) with
 // the analytic JVP of the rate function (models_device.h).  The record is zero-filled by the caller (hipMemsetAsync);
 // lane 0 of each item adds the integrator-independent cost entries.  Not on the headline path (both shipped drivers
 // integrate with Euler, quadrotor_sim.py:100, cartpole_sim.py:63), so simple rather than staged through LDS.
@@ -165,33 +165,18 @@ __global__ __launch_bounds__(64) void linearize_rk4_kernel(const quattro_model_p
   for (int i = 0; i < NX; ++i) dx0[i] = (i == j) ? 1.0f : 0.0f;
 #pragma unroll
   for (int a = 0; a < NU; ++a) du[a] = (NX + a == j) ? 1.0f : 0.0f;
-  const float dt = p.dt;
-  float k[NX], dk[NX], xst[NX], dxs[NX], acc[NX];
-  // stage 1
-  qt_rate<MODEL>(p, xs, us, k);
-  qt_rate_jvp<MODEL>(p, xs, us, dx0, du, dk);
-#pragma unroll
-  for (int i = 0; i < NX; ++i) { acc[i] = dk[i]; xst[i] = fmaf(0.5f * dt, k[i], xs[i]); dxs[i] = fmaf(0.5f * dt, dk[i], dx0[i]); }
-  // stage 2
-  qt_rate<MODEL>(p, xst, us, k);
-  qt_rate_jvp<MODEL>(p, xst, us, dxs, du, dk);
-#pragma unroll
-  for (int i = 0; i < NX; ++i) { acc[i] = fmaf(2.0f, dk[i], acc[i]); xst[i] = fmaf(0.5f * dt, k[i], xs[i]); dxs[i] = fmaf(0.5f * dt, dk[i], dx0[i]); }
-  // stage 3
-  qt_rate<MODEL>(p, xst, us, k);
-  qt_rate_jvp<MODEL>(p, xst, us, dxs, du, dk);
-#pragma unroll
-  for (int i = 0; i < NX; ++i) { acc[i] = fmaf(2.0f, dk[i], acc[i]); xst[i] = fmaf(dt, k[i], xs[i]); dxs[i] = fmaf(dt, dk[i], dx0[i]); }
-  // stage 4
-  qt_rate_jvp<MODEL>(p, xst, us, dxs, du, dk);
+  float xp[4][NX], col[NX];
+  rk4_points<NX>(p.dt, xs, xp, [&](int, const float* xst, float* k) __attribute__((always_inline)) { qt_rate<MODEL>(p, xst, us, k); });
+  rk4_tangent<NX>(p.dt, dx0, col, [&](int s, const float* dxs, float* dk) __attribute__((always_inline)) {
+    qt_rate_jvp<MODEL>(p, xp[s], us, dxs, du, dk);
+  });
   float* r = rec + (size_t)g * L::STRIDE;
 #pragma unroll
   for (int i = 0; i < NX; ++i) {
-    const float v = fmaf(dt / 6.0f, acc[i] + dk[i], dx0[i]);
     if (j < NX) {
-      r[L::a(i, j < NX ? j : 0)] = v;
+      r[L::a(i, j < NX ? j : 0)] = col[i];
     } else {
-      r[L::b(i, j >= NX ? j - NX : 0)] = v;
+      r[L::b(i, j >= NX ? j - NX : 0)] = col[i];
     }
   }
   if (j == 0) fill_cost_entries<MODEL, L>(r, p, xs, us);
@@ -248,43 +233,21 @@ __global__ __launch_bounds__(64) void linearize_rk4_quad_kernel(const quattro_mo
     us[0] = v.x; us[1] = v.y; us[2] = v.z; us[3] = v.w;
   }
   const float dt = p.dt;
-  float k[NX], xst[NX];
-  const QuadStage s1 = quad_stage(p, xs, us);
-  quad_rate_at(s1, p, xs, us, k);
-#pragma unroll
-  for (int i = 0; i < NX; ++i) xst[i] = fmaf(0.5f * dt, k[i], xs[i]);
-  const QuadStage s2 = quad_stage(p, xst, us);
-  quad_rate_at(s2, p, xst, us, k);
-#pragma unroll
-  for (int i = 0; i < NX; ++i) xst[i] = fmaf(0.5f * dt, k[i], xs[i]);
-  const QuadStage s3 = quad_stage(p, xst, us);
-  quad_rate_at(s3, p, xst, us, k);
-#pragma unroll
-  for (int i = 0; i < NX; ++i) xst[i] = fmaf(dt, k[i], xs[i]);
-  const QuadStage s4 = quad_stage(p, xst, us);
+  QuadStage st[4];
+  quad_rk4_stages(p, xs, us, [&](int s, const QuadStage& q) __attribute__((always_inline)) { st[s] = q; });
 
   float* mine = s_stage + lane * RK4Q_PITCH;
   float* out = rec + L::HEADER + (size_t)g0 * L::STRIDE;     // the block's 64 consecutive records
   // column j of [A | B] -> 12 floats at `dst`
   auto column = [&](int j, float* dst) __attribute__((always_inline)) {
-    float dx0[NX], du[NU], dk[NX], dxs[NX], acc[NX];
+    float dx0[NX], du[NU], col[NX];
 #pragma unroll
     for (int i = 0; i < NX; ++i) dx0[i] = (i == j) ? 1.0f : 0.0f;
 #pragma unroll
     for (int a = 0; a < NU; ++a) du[a] = (NX + a == j) ? 1.0f : 0.0f;
-    quad_jvp_at(s1, p, dx0, du, dk);
-#pragma unroll
-    for (int i = 0; i < NX; ++i) { acc[i] = dk[i]; dxs[i] = fmaf(0.5f * dt, dk[i], dx0[i]); }
-    quad_jvp_at(s2, p, dxs, du, dk);
-#pragma unroll
-    for (int i = 0; i < NX; ++i) { acc[i] = fmaf(2.0f, dk[i], acc[i]); dxs[i] = fmaf(0.5f * dt, dk[i], dx0[i]); }
-    quad_jvp_at(s3, p, dxs, du, dk);
-#pragma unroll
-    for (int i = 0; i < NX; ++i) { acc[i] = fmaf(2.0f, dk[i], acc[i]); dxs[i] = fmaf(dt, dk[i], dx0[i]); }
-    quad_jvp_at(s4, p, dxs, du, dk);
-    float col[NX];
-#pragma unroll
-    for (int i = 0; i < NX; ++i) col[i] = fmaf(dt / 6.0f, acc[i] + dk[i], dx0[i]);
+    rk4_tangent<NX>(dt, dx0, col, [&](int s, const float* dxs, float* dk) __attribute__((always_inline)) {
+      quad_jvp_at(st[s], p, dxs, du, dk);
+    });
     float4* d4 = reinterpret_cast<float4*>(dst);
     d4[0] = make_float4(col[0], col[1], col[2], col[3]);
     d4[1] = make_float4(col[4], col[5], col[6], col[7]);
@@ -329,10 +292,10 @@ __global__ void terminal_kernel(const quattro_model_params p, const float* __res
   if (g >= B * NX) return;
   const int b = g / NX, i = g % NX;
   const float xi = x[((size_t)b * (N + 1) + N) * NX + i];
-  VxN[g] = 2.0f * p.qf[i] * (xi - p.x_ref[i]);
+  VxN[g] = qt_terminal_vx(p, i, xi);
   float* row = VxxN + (size_t)g * NX;
 #pragma unroll
-  for (int j = 0; j < NX; ++j) row[j] = (i == j) ? 2.0f * p.qf[i] : 0.0f;
+  for (int j = 0; j < NX; ++j) row[j] = (i == j) ? qt_terminal_vxx(p, i) : 0.0f;
 }
 
 // one thread per record float, enumerated in ROWMAJOR order; writes to the requested layout

@@ -8,6 +8,7 @@
 // reference's own finite differences through the oracle (tests/test_oracle_golden.py, tests/test_linearize_gpu.py).
 #pragma once
 #include "quattro_device.h"
+#include "rk4.h"
 
 template <int MODEL>
 struct ModelDims;
@@ -195,26 +196,14 @@ __device__ __forceinline__ void qt_rate<QUATTRO_MODEL_QUADROTOR>(const quattro_m
 template <int MODEL, bool RK4>
 __device__ __forceinline__ void qt_step(const quattro_model_params& p, const float* x, const float* u, float* xn) {
   constexpr int NX = ModelDims<MODEL>::NX;
-  const float dt = p.dt;
-  float k1[NX];
-  qt_rate<MODEL>(p, x, u, k1);
   if constexpr (!RK4) {
+    float k1[NX];
+    qt_rate<MODEL>(p, x, u, k1);
 #pragma unroll
-    for (int i = 0; i < NX; ++i) xn[i] = fmaf(dt, k1[i], x[i]);
-    return;
+    for (int i = 0; i < NX; ++i) xn[i] = fmaf(p.dt, k1[i], x[i]);
+  } else {
+    rk4_step<NX>(p.dt, x, xn, [&](int, const float* xs, float* k) __attribute__((always_inline)) { qt_rate<MODEL>(p, xs, u, k); });
   }
-  float k2[NX], k3[NX], k4[NX], xs[NX];
-#pragma unroll
-  for (int i = 0; i < NX; ++i) xs[i] = fmaf(0.5f * dt, k1[i], x[i]);
-  qt_rate<MODEL>(p, xs, u, k2);
-#pragma unroll
-  for (int i = 0; i < NX; ++i) xs[i] = fmaf(0.5f * dt, k2[i], x[i]);
-  qt_rate<MODEL>(p, xs, u, k3);
-#pragma unroll
-  for (int i = 0; i < NX; ++i) xs[i] = fmaf(dt, k3[i], x[i]);
-  qt_rate<MODEL>(p, xs, u, k4);
-#pragma unroll
-  for (int i = 0; i < NX; ++i) xn[i] = x[i] + (dt / 6.0f) * (k1[i] + 2.0f * k2[i] + 2.0f * k3[i] + k4[i]);
 }
 
 // running cost L(x,u) and terminal cost Lf(x)
@@ -265,6 +254,31 @@ __device__ __forceinline__ float qt_final_cost(const quattro_model_params& p, co
   return c;
 }
 
+// l_u and l_uu of ONE control (weight ra, value ua): the quadratic term plus the softplus barrier.  No implicit fma contraction:
+// the same entries are produced in kernels of different layouts and surroundings and must come out bit-identical (explicit fmaf
+// calls stay fused).  Two sites keep a copy of these expressions because their translation units contract implicitly and moving
+// them here would split an fma there: EulerRecord<CARTPOLE>::fill_state below and rk4_step_coefs (sweep_tile16_body.h).
+__device__ __forceinline__ void qt_control_cost_derivs(const quattro_model_params& p, float ra, float ua, float* lu_out,
+                                                       float* luu_out) {
+#pragma clang fp contract(off)
+  float lu = 2.0f * ra * ua, luu = 2.0f * ra;
+  if (p.barrier_alpha != 0.0f) {
+    const float sp = qt_softplus(-ua, p.barrier_beta), sg = qt_sigmoid(-p.barrier_beta * ua);
+    lu = fmaf(p.barrier_alpha, -2.0f * sp * sg, lu);
+    luu = fmaf(p.barrier_alpha, 2.0f * sg * sg + 2.0f * sp * p.barrier_beta * sg * (1.0f - sg), luu);
+  }
+  *lu_out = lu;
+  *luu_out = luu;
+}
+
+// the terminal pair of the built-in cost: V_x(N)[i] = 2 Qf_i (x_N[i] - x_ref[i]) and the diagonal of V_xx(N) = 2 Qf (no product
+// feeds an add: the same bits with or without contraction).  Used by terminal_kernel, linearize_compact_kernel and the cart-pole
+// sweep; the tile sweep's fused modes keep the two expressions inline (sweep_tile16_body.h says why).
+__device__ __forceinline__ float qt_terminal_vx(const quattro_model_params& p, int i, float xi) {
+  return 2.0f * p.qf[i] * (xi - p.x_ref[i]);
+}
+__device__ __forceinline__ float qt_terminal_vxx(const quattro_model_params& p, int i) { return 2.0f * p.qf[i]; }
+
 // ------------------------------------------------------------------------------------------------ linearisation
 // Record fillers for the Euler discretisation (A = I + dt Jx, B = dt Ju).  `fill_const` writes every entry that
 // does not depend on (x,u) into a zeroed record once; `fill_state` overwrites the state-dependent entries.
@@ -295,6 +309,8 @@ struct EulerRecord<QUATTRO_MODEL_CARTPOLE, L> {
     rec[L::b(3, 0)] = dt * t.dthdd_F;
 #pragma unroll
     for (int i = 0; i < 4; ++i) rec[L::lx(i)] = 2.0f * p.q[i] * (x[i] - p.x_ref[i]);
+    // (qt_control_cost_derivs' expressions, kept as a copy: this function is compiled with implicit contraction in linearize.hip
+    //  and without in sweep_lane.hip / solve_cartpole.hip, and the helper's contract(off) would split luu's fma in the former)
     float lu = 2.0f * p.r[0] * u[0], luu = 2.0f * p.r[0];
     if (p.barrier_alpha != 0.0f) {
       const float sp = qt_softplus(-u[0], p.barrier_beta), sg = qt_sigmoid(-p.barrier_beta * u[0]);
@@ -391,13 +407,8 @@ struct EulerRecord<QUATTRO_MODEL_QUADROTOR, L> {
     for (int i = 0; i < 12; ++i) rec[L::lx(i)] = 2.0f * p.q[i] * (x[i] - p.x_ref[i]);
   }
   static __device__ __forceinline__ void fill_control(float* rec, const quattro_model_params& p, int a, float ra, float ua) {
-#pragma clang fp contract(off)
-    float lu = 2.0f * ra * ua, luu = 2.0f * ra;
-    if (p.barrier_alpha != 0.0f) {
-      const float sp = qt_softplus(-ua, p.barrier_beta), sg = qt_sigmoid(-p.barrier_beta * ua);
-      lu = fmaf(p.barrier_alpha, -2.0f * sp * sg, lu);
-      luu = fmaf(p.barrier_alpha, 2.0f * sg * sg + 2.0f * sp * p.barrier_beta * sg * (1.0f - sg), luu);
-    }
+    float lu, luu;
+    qt_control_cost_derivs(p, ra, ua, &lu, &luu);
     rec[L::lu(a)] = lu;
     rec[L::luu(a, a)] = luu;
   }
@@ -405,7 +416,8 @@ struct EulerRecord<QUATTRO_MODEL_QUADROTOR, L> {
 
 // ------------------------------------------------------------------------------------------------ forward-mode pieces
 // Directional derivative of the continuous rate function: xd_dot = (d rate / d x) dx + (d rate / d u) du at (x, u).
-// Used to push the 16 (5) unit directions of z = (x, u) through the RK4 stages (linearize_rk4_kernel).
+// Used to push the 16 (5) unit directions of z = (x, u) through the RK4 stages (rk4_tangent: linearize_rk4_kernel,
+// cartpole_record).  The quadrotor's is quad_jvp_at below, at a stage computed on the spot.
 template <int MODEL>
 __device__ __forceinline__ void qt_rate_jvp(const quattro_model_params& p, const float* x, const float* u,
                                             const float* dx, const float* du, float* out);
@@ -419,37 +431,6 @@ __device__ __forceinline__ void qt_rate_jvp<QUATTRO_MODEL_CARTPOLE>(const quattr
   out[1] = t.dxdd_th * dx[2] + t.dxdd_thd * dx[3] + t.dxdd_F * du[0];
   out[2] = dx[3];
   out[3] = t.dthdd_th * dx[2] + t.dthdd_thd * dx[3] + t.dthdd_F * du[0];
-}
-
-template <>
-__device__ __forceinline__ void qt_rate_jvp<QUATTRO_MODEL_QUADROTOR>(const quattro_model_params& p, const float* x,
-                                                                     const float* u, const float* dx, const float* du,
-                                                                     float* out) {
-  const float mass = p.phys[0], Ix = p.phys[1], Iy = p.phys[2], Iz = p.phys[3], arm = p.phys[4], kyaw = p.phys[6];
-  const QuadTrig t = quad_trig(x[6], x[7], x[8]);
-  const float wp = x[9], wq = x[10], wr = x[11];
-  const float tm = (u[0] + u[1] + u[2] + u[3]) / mass;
-  const float dT = (du[0] + du[1] + du[2] + du[3]) / mass;
-  const float rx = t.sps * t.sph + t.cps * t.sth * t.cph;
-  const float ry = t.cps * t.sph - t.sps * t.sth * t.cph;
-  const float rz = t.cth * t.cph;
-  const float dphi = dx[6], dth = dx[7], dpsi = dx[8];
-  out[0] = dx[3];
-  out[1] = dx[4];
-  out[2] = dx[5];
-  out[3] = tm * ((t.sps * t.cph - t.cps * t.sth * t.sph) * dphi + (t.cps * t.cth * t.cph) * dth + ry * dpsi) + rx * dT;
-  out[4] = tm * ((t.cps * t.cph + t.sps * t.sth * t.sph) * dphi - (t.sps * t.cth * t.cph) * dth - rx * dpsi) + ry * dT;
-  out[5] = tm * (-t.cth * t.sph * dphi - t.sth * t.cph * dth) + rz * dT;
-  const float mix = wq * t.sph + wr * t.cph;
-  const float dmix = wq * t.cph - wr * t.sph;
-  const float sec2 = t.sec * t.sec;
-  out[6] = dmix * t.tth * dphi + mix * sec2 * dth + dx[9] + t.sph * t.tth * dx[10] + t.cph * t.tth * dx[11];
-  out[7] = -mix * dphi + t.cph * dx[10] - t.sph * dx[11];
-  out[8] = dmix * t.sec * dphi + mix * t.sth * sec2 * dth + t.sph * t.sec * dx[10] + t.cph * t.sec * dx[11];
-  const float c1 = (Iy - Iz) / Ix, c2 = (Iz - Ix) / Iy, c3 = (Ix - Iy) / Iz;
-  out[9] = c1 * (wr * dx[10] + wq * dx[11]) + (arm / Ix) * ((du[1] + du[2]) - (du[0] + du[3]));
-  out[10] = c2 * (wr * dx[9] + wp * dx[11]) + (arm / Iy) * ((du[0] + du[1]) - (du[2] + du[3]));
-  out[11] = c3 * (wq * dx[9] + wp * dx[10]) + (kyaw / Iz) * (du[0] - du[1] + du[2] - du[3]);
 }
 
 // The quadrotor's rate function and its directional derivative at one stage point, split into "everything that depends on
@@ -476,7 +457,8 @@ __device__ __forceinline__ QuadStage quad_stage(const quattro_model_params& p, c
   s.sec2 = s.t.sec * s.t.sec;
   return s;
 }
-// xd = rate(x, u) at the stage point (the expressions of qt_rate<QUADROTOR>)
+// xd = rate(x, u) at the stage point.  NOT qt_rate<QUADROTOR>'s bits: that one multiplies by reciprocals hoisted out of the rollout
+// loop (* inv_mass, tau * inv_Ix), this one divides (/ mass, (arm / Ix) *); merging them would move rollouts or records in the last bit.
 __device__ __forceinline__ void quad_rate_at(const QuadStage& s, const quattro_model_params& p, const float* x,
                                              const float* u, float* xd) {
   const float Ix = p.phys[1], Iy = p.phys[2], Iz = p.phys[3], arm = p.phys[4], grav = p.phys[5], kyaw = p.phys[6];
@@ -493,7 +475,7 @@ __device__ __forceinline__ void quad_rate_at(const QuadStage& s, const quattro_m
   xd[10] = ((Iz - Ix) / Iy) * (s.wp * s.wr) + (arm / Iy) * ((u[0] + u[1]) - (u[2] + u[3]));
   xd[11] = ((Ix - Iy) / Iz) * (s.wp * s.wq) + (kyaw / Iz) * (u[0] - u[1] + u[2] - u[3]);
 }
-// out = (d rate / d x) dx + (d rate / d u) du at the stage point (the expressions of qt_rate_jvp<QUADROTOR>)
+// out = (d rate / d x) dx + (d rate / d u) du at the stage point
 __device__ __forceinline__ void quad_jvp_at(const QuadStage& s, const quattro_model_params& p, const float* dx,
                                             const float* du, float* out) {
   const float mass = p.phys[0], Ix = p.phys[1], Iy = p.phys[2], Iz = p.phys[3], arm = p.phys[4], kyaw = p.phys[6];
@@ -514,6 +496,38 @@ __device__ __forceinline__ void quad_jvp_at(const QuadStage& s, const quattro_mo
   out[10] = c2 * (s.wr * dx[9] + s.wp * dx[11]) + (arm / Iy) * ((du[0] + du[1]) - (du[2] + du[3]));
   out[11] = c3 * (s.wq * dx[9] + s.wp * dx[10]) + (kyaw / Iz) * (du[0] - du[1] + du[2] - du[3]);
 }
+template <>
+__device__ __forceinline__ void qt_rate_jvp<QUATTRO_MODEL_QUADROTOR>(const quattro_model_params& p, const float* x,
+                                                                     const float* u, const float* dx, const float* du,
+                                                                     float* out) {
+  quad_jvp_at(quad_stage(p, x, u), p, dx, du, out);
+}
+
+// The four RK4 stage points of one quadrotor step (rk4.h's value chain with quad_rate_at as the rate function): visit(s, stage)
+// runs as soon as point s = 0..3 is known, before the next one is computed, so a caller that only needs a stage's coefficients
+// (rk4_step_coefs) can emit them and let the stage die.  Shared by linearize_rk4_quad_kernel and the fused RK4 sweep.
+template <class Visit>
+__device__ __forceinline__ void quad_rk4_stages(const quattro_model_params& p, const float* xs, const float* us, Visit visit) {
+  constexpr int NX = 12;
+  const float dt = p.dt;
+  float k[NX], xst[NX];
+  const QuadStage s1 = quad_stage(p, xs, us);
+  visit(0, s1);
+  quad_rate_at(s1, p, xs, us, k);
+#pragma unroll
+  for (int i = 0; i < NX; ++i) xst[i] = fmaf(0.5f * dt, k[i], xs[i]);
+  const QuadStage s2 = quad_stage(p, xst, us);
+  visit(1, s2);
+  quad_rate_at(s2, p, xst, us, k);
+#pragma unroll
+  for (int i = 0; i < NX; ++i) xst[i] = fmaf(0.5f * dt, k[i], xs[i]);
+  const QuadStage s3 = quad_stage(p, xst, us);
+  visit(2, s3);
+  quad_rate_at(s3, p, xst, us, k);
+#pragma unroll
+  for (int i = 0; i < NX; ++i) xst[i] = fmaf(dt, k[i], xs[i]);
+  visit(3, quad_stage(p, xst, us));
+}
 
 // cost derivative entries of a record (independent of the integrator): l_x, l_u, diag(l_xx), diag(l_uu); l_ux = 0
 template <int MODEL, class L>
@@ -530,12 +544,8 @@ __device__ __forceinline__ void fill_cost_entries(float* rec, const quattro_mode
   }
 #pragma unroll
   for (int a = 0; a < NU; ++a) {
-    float lu = 2.0f * p.r[a] * u[a], luu = 2.0f * p.r[a];
-    if (p.barrier_alpha != 0.0f) {
-      const float sp = qt_softplus(-u[a], p.barrier_beta), sg = qt_sigmoid(-p.barrier_beta * u[a]);
-      lu = fmaf(p.barrier_alpha, -2.0f * sp * sg, lu);
-      luu = fmaf(p.barrier_alpha, 2.0f * sg * sg + 2.0f * sp * p.barrier_beta * sg * (1.0f - sg), luu);
-    }
+    float lu, luu;
+    qt_control_cost_derivs(p, p.r[a], u[a], &lu, &luu);
     rec[L::lu(a)] = lu;
     rec[L::luu(a, a)] = luu;
   }

@@ -168,7 +168,24 @@ namespace {
 struct AlphaList {
   float a[QUATTRO_MAX_ALPHAS];
 };
+inline AlphaList make_alpha_list(const float* alphas, int n_alpha) {   // (host) unused slots are zero
+  AlphaList al;
+  for (int i = 0; i < QUATTRO_MAX_ALPHAS; ++i) al.a[i] = i < n_alpha ? alphas[i] : 0.0f;
+  return al;
+}
 }  // namespace
+
+// launchers: run the statement with `constexpr bool RK4` set from p.integrator, or return QUATTRO_ERR_UNSUPPORTED
+#define QT_DISPATCH_INTEG(p, ...)                                 \
+  if ((p).integrator == QUATTRO_INTEGRATOR_EULER) {               \
+    constexpr bool RK4 = false;                                   \
+    __VA_ARGS__;                                                  \
+  } else if ((p).integrator == QUATTRO_INTEGRATOR_RK4) {          \
+    constexpr bool RK4 = true;                                    \
+    __VA_ARGS__;                                                  \
+  } else {                                                        \
+    return QUATTRO_ERR_UNSUPPORTED;                               \
+  }
 
 // ----------------------------------------------------------------------------------------------
 // wave helpers

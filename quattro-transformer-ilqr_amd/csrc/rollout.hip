@@ -87,16 +87,6 @@ __global__ __launch_bounds__(64) void linesearch_kernel(const quattro_model_para
 
 }  // namespace
 
-#define QT_DISPATCH_INTEG(p, ...)                                 \
-  if ((p).integrator == QUATTRO_INTEGRATOR_EULER) {               \
-    constexpr bool RK4 = false;                                   \
-    __VA_ARGS__;                                                  \
-  } else if ((p).integrator == QUATTRO_INTEGRATOR_RK4) {          \
-    constexpr bool RK4 = true;                                    \
-    __VA_ARGS__;                                                  \
-  } else {                                                        \
-    return QUATTRO_ERR_UNSUPPORTED;                               \
-  }
 // the one-lane-per-candidate kernels of this file serve the cart-pole; quadrotor calls were routed to rollout_quad.hip
 // by the launchers before they get here
 #ifdef QT_USER_MODEL_HEADER
@@ -163,8 +153,7 @@ int quattro_launch_rollout(const quattro_model_params& p, const float* x_nom, co
                            double* cost, const int32_t* active, hipStream_t stream) {
   if (p.model_id == QUATTRO_MODEL_QUADROTOR)
     return quattro_launch_rollout_quad(p, x_nom, u_nom, K, k, alphas, n_alpha, B, N, x_new, u_new, cost, active, stream);
-  AlphaList al;
-  for (int i = 0; i < QUATTRO_MAX_ALPHAS; ++i) al.a[i] = i < n_alpha ? alphas[i] : 0.0f;
+  const AlphaList al = make_alpha_list(alphas, n_alpha);
   const int threads = 64;
   const long long tot = (long long)B * 8;
   QT_DISPATCH_MODEL(p, hipLaunchKernelGGL((rollout_kernel<MODEL, RK4>), dim3((unsigned)((tot + threads - 1) / threads)),
@@ -180,8 +169,7 @@ int quattro_launch_linesearch(const quattro_model_params& p, float* x_nom, float
   if (p.model_id == QUATTRO_MODEL_QUADROTOR)
     return quattro_launch_linesearch_quad(p, x_nom, u_nom, K, k, alphas, n_alpha, B, N, tol, cost, alpha_idx, active,
                                           iters, scratch, stream);
-  AlphaList al;
-  for (int i = 0; i < QUATTRO_MAX_ALPHAS; ++i) al.a[i] = i < n_alpha ? alphas[i] : 0.0f;
+  const AlphaList al = make_alpha_list(alphas, n_alpha);
   const int threads = 64;
   const long long tot = (long long)B * 8;
   QT_DISPATCH_MODEL(p, hipLaunchKernelGGL((linesearch_kernel<MODEL, RK4>), dim3((unsigned)((tot + threads - 1) / threads)),

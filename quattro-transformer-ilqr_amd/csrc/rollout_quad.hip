@@ -90,21 +90,10 @@ __global__ __launch_bounds__(64) void linesearch_quad_kernel(const quattro_model
 
 }  // namespace
 
-#define QT_QUAD_DISPATCH(p, ...)                              \
-  if ((p).integrator == QUATTRO_INTEGRATOR_EULER) {           \
-    constexpr bool RK4 = false;                               \
-    __VA_ARGS__;                                              \
-  } else if ((p).integrator == QUATTRO_INTEGRATOR_RK4) {      \
-    constexpr bool RK4 = true;                                \
-    __VA_ARGS__;                                              \
-  } else {                                                    \
-    return QUATTRO_ERR_UNSUPPORTED;                           \
-  }
-
 int quattro_launch_simulate_quad(const quattro_model_params& p, const float* x0, const float* u, int B, int N, float* x,
                                  double* cost, hipStream_t stream) {
   const long long tot = (long long)B * 4;
-  QT_QUAD_DISPATCH(p, hipLaunchKernelGGL((simulate_quad_kernel<RK4>), dim3((unsigned)((tot + 63) / 64)), dim3(64), 0,
+  QT_DISPATCH_INTEG(p, hipLaunchKernelGGL((simulate_quad_kernel<RK4>), dim3((unsigned)((tot + 63) / 64)), dim3(64), 0,
                                          stream, p, x0, u, B, N, x, cost));
   return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;
 }
@@ -112,10 +101,9 @@ int quattro_launch_simulate_quad(const quattro_model_params& p, const float* x0,
 int quattro_launch_rollout_quad(const quattro_model_params& p, const float* x_nom, const float* u_nom, const float* K,
                                 const float* k, const float* alphas, int n_alpha, int B, int N, float* x_new,
                                 float* u_new, double* cost, const int32_t* active, hipStream_t stream) {
-  AlphaList al;
-  for (int i = 0; i < QUATTRO_MAX_ALPHAS; ++i) al.a[i] = i < n_alpha ? alphas[i] : 0.0f;
+  const AlphaList al = make_alpha_list(alphas, n_alpha);
   const long long tot = (long long)B * 32;
-  QT_QUAD_DISPATCH(p, hipLaunchKernelGGL((rollout_quad_kernel<RK4>), dim3((unsigned)((tot + 63) / 64)), dim3(64), 0,
+  QT_DISPATCH_INTEG(p, hipLaunchKernelGGL((rollout_quad_kernel<RK4>), dim3((unsigned)((tot + 63) / 64)), dim3(64), 0,
                                          stream, p, x_nom, u_nom, K, k, al, n_alpha, B, N, x_new, u_new, cost, active));
   return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;
 }
@@ -124,10 +112,9 @@ int quattro_launch_linesearch_quad(const quattro_model_params& p, float* x_nom, 
                                    const float* k, const float* alphas, int n_alpha, int B, int N, double tol,
                                    double* cost, int32_t* alpha_idx, int32_t* active, int32_t* iters, float* scratch,
                                    hipStream_t stream) {
-  AlphaList al;
-  for (int i = 0; i < QUATTRO_MAX_ALPHAS; ++i) al.a[i] = i < n_alpha ? alphas[i] : 0.0f;
+  const AlphaList al = make_alpha_list(alphas, n_alpha);
   const long long tot = (long long)B * 32;
-  QT_QUAD_DISPATCH(p, hipLaunchKernelGGL((linesearch_quad_kernel<RK4>), dim3((unsigned)((tot + 63) / 64)), dim3(64), 0,
+  QT_DISPATCH_INTEG(p, hipLaunchKernelGGL((linesearch_quad_kernel<RK4>), dim3((unsigned)((tot + 63) / 64)), dim3(64), 0,
                                          stream, p, x_nom, u_nom, K, k, al, n_alpha, B, N, tol, cost, alpha_idx, active,
                                          iters, scratch));
   return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;

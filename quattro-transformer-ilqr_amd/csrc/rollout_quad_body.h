@@ -122,27 +122,18 @@ __device__ __forceinline__ void quad_rate(const LaneConst& L, const float* xo, c
 
 template <bool RK4>
 __device__ __forceinline__ void quad_step(const LaneConst& L, const float* xo, const QuadU& uo, float* xn) {
-  const float dt = L.dt;
-  float k1[4];
   TrigBase tb;
-  quad_rate<false>(L, xo, uo, k1, tb);
   if constexpr (!RK4) {
+    float k1[4];
+    quad_rate<false>(L, xo, uo, k1, tb);
 #pragma unroll
-    for (int g = 0; g < 4; ++g) xn[g] = fmaf(dt, k1[g], xo[g]);
-    return;
+    for (int g = 0; g < 4; ++g) xn[g] = fmaf(L.dt, k1[g], xo[g]);
+  } else {   // stage 0 sets the trig base, the later stages reach their angles from it by angle addition
+    rk4_step<4>(L.dt, xo, xn, [&](int s, const float* xs, float* k) __attribute__((always_inline)) {
+      if (s == 0) quad_rate<false>(L, xs, uo, k, tb);
+      else quad_rate<true>(L, xs, uo, k, tb);
+    });
   }
-  float k2[4], k3[4], k4[4], xs[4];
-#pragma unroll
-  for (int g = 0; g < 4; ++g) xs[g] = fmaf(0.5f * dt, k1[g], xo[g]);
-  quad_rate<true>(L, xs, uo, k2, tb);
-#pragma unroll
-  for (int g = 0; g < 4; ++g) xs[g] = fmaf(0.5f * dt, k2[g], xo[g]);
-  quad_rate<true>(L, xs, uo, k3, tb);
-#pragma unroll
-  for (int g = 0; g < 4; ++g) xs[g] = fmaf(dt, k3[g], xo[g]);
-  quad_rate<true>(L, xs, uo, k4, tb);
-#pragma unroll
-  for (int g = 0; g < 4; ++g) xn[g] = xo[g] + (dt / 6.0f) * (k1[g] + 2.0f * k2[g] + 2.0f * k3[g] + k4[g]);
 }
 
 // this lane's share of L(x,u): its four state terms, its control's R and barrier terms.  `counted` = lane belongs to a

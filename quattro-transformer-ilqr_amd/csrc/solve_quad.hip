@@ -265,16 +265,7 @@ int quattro_launch_solve_quad(const quattro_model_params& p, const SolveLoop& c,
   if (p.integrator != QUATTRO_INTEGRATOR_EULER && p.integrator != QUATTRO_INTEGRATOR_RK4) return QUATTRO_ERR_UNSUPPORTED;
   if (p.integrator == QUATTRO_INTEGRATOR_RK4 && coef == nullptr) return QUATTRO_ERR_WORKSPACE;
   SolveArgs a;
-  a.fa.p = p;
-  a.fa.x = c.x;
-  a.fa.u = c.u;
-  a.fa.N = c.N;
-  a.fa.t_start = 0;
-  a.fa.B = c.B;
-  a.fa.coef = coef;     // RK4: the sweep's coefficient scratch, B * N * 132 floats
-  a.fa.k_rows = 0;
-  a.fa.rn = 12;
-  a.fa.rm = 4;
+  a.fa = fused_args(p, c.x, c.u, c.B, c.N, 0, coef, 0);     // (coef: the RK4 sweep's coefficient scratch, B * N * 132 floats)
   a.c = c;
   a.stamps = stamps;
   a.stamp_rows = stamp_rows;

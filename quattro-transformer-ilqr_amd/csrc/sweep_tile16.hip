@@ -87,17 +87,7 @@ int quattro_launch_sweep_tile16(const float* rec, const float* VxN, const float*
 int quattro_launch_sweep_fused(const quattro_model_params& p, const float* x, const float* u, int B, int N, int t_start,
                                float reg, float* K, float* k, int k_rows, int32_t* status, const int32_t* active,
                                hipStream_t stream) {
-  FusedArgs fa;
-  fa.p = p;
-  fa.x = x;
-  fa.u = u;
-  fa.N = N;
-  fa.t_start = t_start;
-  fa.B = B;
-  fa.coef = nullptr;
-  fa.k_rows = k_rows;
-  fa.rn = 12;
-  fa.rm = 4;
+  const FusedArgs fa = fused_args(p, x, u, B, N, t_start, nullptr, k_rows);
   hipLaunchKernelGGL(sweep_tile16_kernel<MODE_FUSED>, dim3((B + WPB - 1) / WPB), dim3(QT_WAVE * WPB), 0, stream, nullptr, nullptr, nullptr,
                      N - t_start, reg, K, k, status, active, fa);
   return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;
@@ -108,17 +98,7 @@ size_t quattro_sweep_fused_rk4_scratch_floats(int B, int S) { return (size_t)B *
 int quattro_launch_sweep_fused_rk4(const quattro_model_params& p, const float* x, const float* u, int B, int N, int t_start,
                                    float reg, float* K, float* k, int k_rows, int32_t* status, const int32_t* active,
                                    float* coef, hipStream_t stream) {
-  FusedArgs fa;
-  fa.p = p;
-  fa.x = x;
-  fa.u = u;
-  fa.N = N;
-  fa.t_start = t_start;
-  fa.B = B;
-  fa.coef = coef;
-  fa.k_rows = k_rows;
-  fa.rn = 12;
-  fa.rm = 4;
+  const FusedArgs fa = fused_args(p, x, u, B, N, t_start, coef, k_rows);
   hipLaunchKernelGGL(sweep_tile16_kernel<MODE_FUSED_RK4>, dim3((B + WPB - 1) / WPB), dim3(QT_WAVE * WPB), 0, stream, nullptr, nullptr,
                      nullptr, N - t_start, reg, K, k, status, active, fa);
   return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;

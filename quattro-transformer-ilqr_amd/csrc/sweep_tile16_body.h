@@ -154,6 +154,22 @@ struct FusedArgs {
                     // N = the full stacks, step t written in place at row t (quattro_linearize_sweep_rows_f32)
   int rn, rm;       // MODE_ROWPAD: the problem's own dimensions (records, terminal pair and gains are laid out for them)
 };
+// (host) the argument block of the fused quadrotor modes; coef = NULL unless MODE_FUSED_RK4
+inline FusedArgs fused_args(const quattro_model_params& p, const float* x, const float* u, int B, int N, int t_start,
+                            float* coef, int k_rows) {
+  FusedArgs fa;
+  fa.p = p;
+  fa.x = x;
+  fa.u = u;
+  fa.N = N;
+  fa.t_start = t_start;
+  fa.B = B;
+  fa.coef = coef;
+  fa.k_rows = k_rows;
+  fa.rn = 12;
+  fa.rm = 4;
+  return fa;
+}
 
 constexpr int WPB = 2;   // trajectories (waves) per workgroup; the waves of a workgroup never synchronise
 __device__ __forceinline__ void wave_sync() {
@@ -172,6 +188,8 @@ constexpr int sweep_lin_floats() {
 }
 
 // ---- MODE_FUSED_RK4, stage (1): the four stage points of one step -> Rk4Coef record (132 floats)
+// (tm * ... here against fill_dynamics' (dt * tm) * ... under contract(off): the same Jacobian entries, rounded differently; merging
+// them would change Euler or RK4 records in the last bit)
 __device__ __forceinline__ void rk4_stage_entries(const QuadStage& s, const quattro_model_params& p, float* c) {
   const QuadTrig& t = s.t;
   const float inv_mass = 1.0f / p.phys[0];
@@ -209,34 +227,17 @@ __device__ __forceinline__ void rk4_stage_entries(const QuadStage& s, const quat
 template <class Emit>
 __device__ __forceinline__ void rk4_step_coefs(const quattro_model_params& p, const float* xs, const float* us, Emit emit) {
   constexpr int NX = 12;
-  const float dt = p.dt;
-  float k[NX], xst[NX], c[Rk4Coef::PER_STAGE];
-  auto flush = [&](int stage) __attribute__((always_inline)) {
+  // each stage's 28 coefficients leave before the next stage point is computed
+  float c[Rk4Coef::PER_STAGE];
+  quad_rk4_stages(p, xs, us, [&](int stage, const QuadStage& s) __attribute__((always_inline)) {
+    rk4_stage_entries(s, p, c);
 #pragma unroll
     for (int q = 0; q < Rk4Coef::PER_STAGE / 4; ++q) emit(stage * (Rk4Coef::PER_STAGE / 4) + q, make_float4(c[4 * q], c[4 * q + 1], c[4 * q + 2], c[4 * q + 3]));
-  };
-  const QuadStage s1 = quad_stage(p, xs, us);
-  rk4_stage_entries(s1, p, c);
-  flush(0);
-  quad_rate_at(s1, p, xs, us, k);
-#pragma unroll
-  for (int i = 0; i < NX; ++i) xst[i] = fmaf(0.5f * dt, k[i], xs[i]);
-  const QuadStage s2 = quad_stage(p, xst, us);
-  rk4_stage_entries(s2, p, c);
-  flush(1);
-  quad_rate_at(s2, p, xst, us, k);
-#pragma unroll
-  for (int i = 0; i < NX; ++i) xst[i] = fmaf(0.5f * dt, k[i], xs[i]);
-  const QuadStage s3 = quad_stage(p, xst, us);
-  rk4_stage_entries(s3, p, c);
-  flush(2);
-  quad_rate_at(s3, p, xst, us, k);
-#pragma unroll
-  for (int i = 0; i < NX; ++i) xst[i] = fmaf(dt, k[i], xs[i]);
-  const QuadStage s4 = quad_stage(p, xst, us);
-  rk4_stage_entries(s4, p, c);
-  flush(3);
-  // cost entries (fill_cost_entries' expressions): l_z = (l_x, l_u), diag(l_uu)
+  });
+  // cost entries: l_z = (l_x, l_u), diag(l_uu).  fill_cost_entries' expressions, but NOT its bits: these are compiled with the
+  // implicit contraction of their translation units (sweep_tile16.hip, solve_quad.hip), where l_uu's barrier term is one fma more
+  // than under qt_control_cost_derivs' contract(off); the fused RK4 sweep and the persistent loop agree with each other, and
+  // moving the copy onto the helper would change their rounding.
   float lz[16], luud[4];
 #pragma unroll
   for (int i = 0; i < NX; ++i) lz[i] = 2.0f * p.q[i] * (xs[i] - p.x_ref[i]);
@@ -311,7 +312,9 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
   const float regadd = (c == 4 * r + 3) ? reg : 0.0f;   // this lane holds Q_uu[r][r]
   const int c4 = 4 * c, a16 = 4 * (lane ^ 16), a32 = 4 * (lane ^ 32);   // ds_bpermute byte addresses
 
-  // terminal values: A-operand layout of V_xx is lane(r,c) = V[x_j][3r+s]; used as given (not symmetrised)
+  // terminal values: A-operand layout of V_xx is lane(r,c) = V[x_j][3r+s]; used as given (not symmetrised).  The fused modes form
+  // qt_terminal_vx / qt_terminal_vxx's expressions inline: through the helper the last state is loaded before Qf instead of after
+  // it, which reorders the Euler kernels' loads and costs the register-bound RK4 persistent kernel 140 instructions of spills.
   float vA0 = 0.0f, vA1 = 0.0f, vA2 = 0.0f;
   float vx0, vx1, vx2;
   if constexpr (FUSED || RK4F) {

@@ -61,7 +61,10 @@ __device__ __forceinline__ T default_final_cost(const quattro_model_params& p, c
 
 #include QT_USER_MODEL_HEADER
 
-// x_next = f(x, u) for any scalar type: explicit Euler or classic RK4 with zero-order-hold u (what qt_step does in fp32)
+// x_next = f(x, u) for any scalar type: explicit Euler or classic RK4 with zero-order-hold u.  The scheme of rk4.h, which the
+// rollouts of a user model go through (qt_step), but NOT its bits: this one is generic over dual numbers and written as
+// x + k * (0.5f * dt) without fmaf, so a linearisation's value part may differ from the rollout in the last bit.  Moving it onto
+// rk4_step would change user-model records; it stays a copy.
 template <class T, bool RK4>
 __device__ __forceinline__ void step(const quattro_model_params& p, const T* x, const T* u, T* xn) {
   const float dt = p.dt;
