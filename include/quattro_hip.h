@@ -354,6 +354,37 @@ int quattro_mpc_run_f32(const quattro_model_params* p, float* x_cur, float* x_no
                         int32_t* active, int32_t* iters, int32_t* status, void* workspace, size_t workspace_bytes,
                         void* stream);
 
+/* The closed loop with a PLANT OF ITS OWN and gain feedback between solves.  A real controller replans slowly and, between
+ * plans, runs u = u_nom[j] + K[j] (x - x_nom[j]) at the plant rate; and the plant is never exactly the model it plans with.
+ *
+ * quattro_track_f32: n_steps <= N tracked plant steps from x0 [B][n] along rows 0 .. n_steps-1 of a nominal (x_nom [B][N+1][n],
+ * u_nom [B][N][m]) and its gains K [B][N][m][n] (required also without feedback).  For j = 0 .. n_steps-1:
+ *     u_app = u_nom[j] + (feedback ? K[j] (x - x_nom[j]) : 0),   x <- f_plant(x, u_app) + disturbance[j][b]
+ *   plant       : the plant's parameters, NULL = p.  Its model_id, n, m and dt must equal p's (QUATTRO_ERR_BAD_ARG otherwise); its
+ *                 integrator and phys define f_plant; its cost fields are ignored.
+ *   plant_phys  : [B][8] device array or NULL: row b replaces plant->phys for controller b (a user model's free parameters
+ *                 likewise: the study of B controllers against B different plants)
+ *   disturbance : [n_steps][B][n] or NULL
+ *   out         : x_out [B][n_steps+1][n] (row 0 = x0), u_out [B][n_steps][m] applied controls
+ *
+ * quattro_mpc_run_plant_f32: quattro_mpc_run_f32 (its arguments, in its order) with such a plant and a hold count.  n_steps PLANT
+ * steps; for plan c = 0 .. n_steps/hold - 1: solve from x_cur with the warm start exactly as quattro_mpc_run_f32 does (x_nom,
+ * u_nom, K are what that solve leaves behind, K from its last backward pass), run `hold` tracked steps as above (the device
+ * function of quattro_track_f32: bit-identical), shift the warm start by hold (u_hold .. u_{N-1}, u_{N-1} x hold), and
+ * traj_iters[b][c] = iterations of the solve.  traj_x / traj_u as in quattro_mpc_run_f32, traj_iters [B][n_steps/hold],
+ * disturbance [n_steps][B][n] or NULL.  With hold = 1 the feedback term is exactly zero (x_cur == x_nom[0]).
+ * QUATTRO_ERR_BAD_ARG, nothing launched: hold outside 1..N, n_steps % hold != 0, a plant whose model_id, n, m or dt differ from
+ * p's, feedback with max_iter < 1.  quattro_mpc_run_f32 itself keeps its own kernels and results.                               */
+int quattro_track_f32(const quattro_model_params* p, const quattro_model_params* plant, const float* plant_phys, const float* x0,
+                      const float* x_nom, const float* u_nom, const float* K, int feedback, int B, int N, int n_steps,
+                      const float* disturbance, float* x_out, float* u_out, void* stream);
+int quattro_mpc_run_plant_f32(const quattro_model_params* p, float* x_cur, float* x_nom, float* u_nom, int B, int N, float reg,
+                              const float* alphas, int n_alpha, double tol, int max_iter, int n_steps, float* traj_x,
+                              float* traj_u, int32_t* traj_iters, const float* disturbance, float* K, float* k, double* cost,
+                              int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status, void* workspace,
+                              size_t workspace_bytes, const quattro_model_params* plant, const float* plant_phys, int hold,
+                              int feedback, void* stream);
+
 /* Transformer gain predictor: weights of the reference's TransformerPredictor (quattro_ilqr_tf/transformer_model.py:85-138)
  * as DEVICE pointers, plus the DataNormalizer vectors (:15-50).  Matrices are PyTorch Linear layout [out][in];
  * the `w_*` matrices are 16-bit (raw uint16 bit patterns: bf16, or IEEE half when `precision` says so), everything else

@@ -26,6 +26,8 @@ int quattro_launch_rollout(const quattro_model_params&, const float*, const floa
 int quattro_launch_linesearch(const quattro_model_params&, float*, float*, const float*, const float*, const float*,
                               int, int, int, double, double*, int32_t*, int32_t*, int32_t*, float*, hipStream_t);
 size_t quattro_linesearch_scratch_bytes_impl(int, int, int, int);
+int quattro_launch_track(const quattro_model_params&, const PlantSpec&, const float*, const float*, const float*, const float*,
+                         const float*, int, int, int, int, const float*, float*, float*, hipStream_t);
 int quattro_launch_solve_cartpole(const quattro_model_params& p, const SolveLoop& loop, hipStream_t stream);
 int quattro_launch_solve_quad(const quattro_model_params& p, const SolveLoop& loop, float* coef, unsigned long long* stamps,
                               int stamp_rows, hipStream_t stream);
@@ -55,6 +57,17 @@ bool model_ok(const quattro_model_params* p) {
   if (p->model_id == QUATTRO_MODEL_USER) return p->n == QT_USER_NX && p->m == QT_USER_NU;
 #endif
   return false;
+}
+
+// The plant of a closed loop (NULL: the controller's own model): the same problem — model_id, n, m, dt — with an integrator and
+// physical parameters of its own; its cost fields are ignored.  QUATTRO_OK and *out filled, or the status to return.
+int plant_spec(const quattro_model_params* p, const quattro_model_params* plant, PlantSpec* out) {
+  if (plant == nullptr) plant = p;
+  if (plant->model_id != p->model_id || plant->n != p->n || plant->m != p->m || plant->dt != p->dt) return QUATTRO_ERR_BAD_ARG;
+  if (plant->integrator != QUATTRO_INTEGRATOR_EULER && plant->integrator != QUATTRO_INTEGRATOR_RK4) return QUATTRO_ERR_UNSUPPORTED;
+  out->integrator = plant->integrator;
+  for (int i = 0; i < 8; ++i) out->phys[i] = plant->phys[i];
+  return QUATTRO_OK;
 }
 }  // namespace
 
@@ -513,6 +526,51 @@ int quattro_mpc_run_f32(const quattro_model_params* p, float* x_cur, float* x_no
   loop.traj_iters = traj_iters;
   loop.disturbance = disturbance;
   return launch_device_loop(*p, loop, w, (char*)workspace, (hipStream_t)stream);
+}
+
+int quattro_mpc_run_plant_f32(const quattro_model_params* p, float* x_cur, float* x_nom, float* u_nom, int B, int N, float reg,
+                              const float* alphas, int n_alpha, double tol, int max_iter, int n_steps, float* traj_x,
+                              float* traj_u, int32_t* traj_iters, const float* disturbance, float* K, float* k, double* cost,
+                              int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status, void* workspace,
+                              size_t workspace_bytes, const quattro_model_params* plant, const float* plant_phys, int hold,
+                              int feedback, void* stream) {
+  const bool args_ok = x_cur && iters && traj_x && traj_u && traj_iters && max_iter >= 0 && n_steps > 0 && hold >= 1 && hold <= N &&
+                       n_steps % hold == 0 && !(feedback && max_iter < 1);
+  PlantSpec ps{};
+  int entry_rc = QUATTRO_ERR_BAD_ARG;
+  if (args_ok && model_ok(p)) {
+    entry_rc = plant_spec(p, plant, &ps);
+    if (entry_rc == QUATTRO_OK && !quattro_model_has_device_loop(p)) entry_rc = QUATTRO_ERR_UNSUPPORTED;
+  }
+  WorkspacePlan w;
+  const int rc = check_solve_args(p, x_nom, u_nom, B, N, alphas, n_alpha, K, k, cost, alpha_idx, active, entry_rc, workspace,
+                                  workspace_bytes, &w);
+  if (rc != QUATTRO_OK) return rc;
+  SolveLoop loop = solve_loop(*p, x_cur, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, 0, K, k, cost, alpha_idx,
+                              active, iters, status, nullptr);
+  loop.n_ctrl = n_steps / hold;
+  loop.x_cur = x_cur;
+  loop.traj_x = traj_x;
+  loop.traj_u = traj_u;
+  loop.traj_iters = traj_iters;
+  loop.disturbance = disturbance;
+  loop.plant = ps;
+  loop.plant_phys = plant_phys;
+  loop.hold = hold;
+  loop.feedback = feedback ? 1 : 0;
+  return launch_device_loop(*p, loop, w, (char*)workspace, (hipStream_t)stream);
+}
+
+int quattro_track_f32(const quattro_model_params* p, const quattro_model_params* plant, const float* plant_phys, const float* x0,
+                      const float* x_nom, const float* u_nom, const float* K, int feedback, int B, int N, int n_steps,
+                      const float* disturbance, float* x_out, float* u_out, void* stream) {
+  if (!model_ok(p)) return p ? QUATTRO_ERR_UNSUPPORTED : QUATTRO_ERR_BAD_ARG;
+  if (!x0 || !x_nom || !u_nom || !K || !x_out || !u_out || B <= 0 || N <= 0 || n_steps < 1 || n_steps > N) return QUATTRO_ERR_BAD_ARG;
+  PlantSpec ps{};
+  const int rc = plant_spec(p, plant, &ps);
+  if (rc != QUATTRO_OK) return rc;
+  return quattro_launch_track(*p, ps, plant_phys, x0, x_nom, u_nom, K, feedback ? 1 : 0, B, N, n_steps, disturbance, x_out, u_out,
+                              (hipStream_t)stream);
 }
 
 namespace {

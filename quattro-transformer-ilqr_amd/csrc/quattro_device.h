@@ -163,6 +163,15 @@ struct Tile16RRec {
   static QT_HD int lu(int a_) { return LZ + 12 + a_; }
 };
 
+// The plant of a closed loop where it is not the controller's own model (quattro_track_f32, quattro_mpc_run_plant_f32): the
+// same model_id, n, m and dt, its own integrator and physical parameters.  `phys` serves every controller unless the caller
+// passes a device array plant_phys [B][8], whose row b then replaces it for controller b.
+// (outside the anonymous namespace: the kernel launchers take it from capi.hip)
+struct PlantSpec {
+  int integrator;
+  float phys[8];
+};
+
 // the step sizes of a line search, by value (a kernel argument)
 namespace {
 struct AlphaList {

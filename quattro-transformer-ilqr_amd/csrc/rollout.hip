@@ -85,6 +85,28 @@ __global__ __launch_bounds__(64) void linesearch_kernel(const quattro_model_para
                                  blockIdx.x * blockDim.x + threadIdx.x, false);
 }
 
+// tracked plant steps (quattro_track_f32): one lane per trajectory; the steps themselves are track_body, the function the
+// persistent MPC loops run between their solves
+template <int MODEL>
+__global__ __launch_bounds__(64) void track_kernel(const quattro_model_params p, const PlantSpec plant,
+                                                   const float* __restrict__ plant_phys, const float* __restrict__ x0,
+                                                   const float* __restrict__ x_nom, const float* __restrict__ u_nom,
+                                                   const float* __restrict__ K, const int feedback, const int B, const int N,
+                                                   const int n_steps, const float* __restrict__ disturbance,
+                                                   float* __restrict__ x_out, float* __restrict__ u_out) {
+  constexpr int NX = ModelDims<MODEL>::NX, NU = ModelDims<MODEL>::NU;
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const size_t bb = b;
+  float xh[NX];
+  load_vec<NX>(x0 + bb * NX, xh);
+  float* xrows = x_out + bb * (size_t)(n_steps + 1) * NX;
+  store_vec<NX>(xrows, xh);
+  track_body<MODEL>(p, plant, plant_phys, feedback != 0, x_nom + bb * (N + 1) * NX, u_nom + bb * N * NU, K + bb * N * NU * NX, xh,
+                    n_steps, disturbance != nullptr ? disturbance + bb * NX : nullptr, (size_t)B * NX, xrows,
+                    u_out + bb * (size_t)n_steps * NU, bb);
+}
+
 }  // namespace
 
 // the one-lane-per-candidate kernels of this file serve the cart-pole; quadrotor calls were routed to rollout_quad.hip
@@ -116,6 +138,8 @@ int quattro_launch_rollout_quad(const quattro_model_params&, const float*, const
 int quattro_launch_linesearch_quad(const quattro_model_params&, float*, float*, const float*, const float*,
                                    const float*, int, int, int, double, double*, int32_t*, int32_t*, int32_t*, float*,
                                    hipStream_t);
+int quattro_launch_track_quad(const quattro_model_params&, const PlantSpec&, const float*, const float*, const float*,
+                              const float*, const float*, int, int, int, int, const float*, float*, float*, hipStream_t);
 
 size_t quattro_linesearch_scratch_bytes_impl(int n, int m, int B, int N) {
   const size_t cs = (size_t)((n + m + 3) / 4 * 4);
@@ -175,5 +199,26 @@ int quattro_launch_linesearch(const quattro_model_params& p, float* x_nom, float
   QT_DISPATCH_MODEL(p, hipLaunchKernelGGL((linesearch_kernel<MODEL, RK4>), dim3((unsigned)((tot + threads - 1) / threads)),
                                           dim3(threads), 0, stream, p, x_nom, u_nom, K, k, al, n_alpha, B, N, tol, cost,
                                           alpha_idx, active, iters, scratch));
+  return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;
+}
+
+int quattro_launch_track(const quattro_model_params& p, const PlantSpec& plant, const float* plant_phys, const float* x0,
+                         const float* x_nom, const float* u_nom, const float* K, int feedback, int B, int N, int n_steps,
+                         const float* disturbance, float* x_out, float* u_out, hipStream_t stream) {
+  if (p.model_id == QUATTRO_MODEL_QUADROTOR)
+    return quattro_launch_track_quad(p, plant, plant_phys, x0, x_nom, u_nom, K, feedback, B, N, n_steps, disturbance, x_out, u_out,
+                                     stream);
+  const int threads = 64;
+  const dim3 grid((B + threads - 1) / threads);
+  if (p.model_id == QUATTRO_MODEL_CARTPOLE)
+    hipLaunchKernelGGL((track_kernel<QUATTRO_MODEL_CARTPOLE>), grid, dim3(threads), 0, stream, p, plant, plant_phys, x0, x_nom, u_nom,
+                       K, feedback, B, N, n_steps, disturbance, x_out, u_out);
+#ifdef QT_USER_MODEL_HEADER
+  else if (p.model_id == QUATTRO_MODEL_USER)
+    hipLaunchKernelGGL((track_kernel<QUATTRO_MODEL_USER>), grid, dim3(threads), 0, stream, p, plant, plant_phys, x0, x_nom, u_nom, K,
+                       feedback, B, N, n_steps, disturbance, x_out, u_out);
+#endif
+  else
+    return QUATTRO_ERR_UNSUPPORTED;
   return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;
 }

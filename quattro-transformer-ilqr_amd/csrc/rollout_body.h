@@ -156,6 +156,71 @@ __device__ __forceinline__ void simulate_body(const quattro_model_params& p, con
   if (cost != nullptr) cost[b] = J;
 }
 
+// Tracked plant steps of trajectory b by ONE lane, stated once for this lane mapping: track_kernel (rollout.hip) and the
+// persistent loops' MPC epilogue (solve_cartpole.hip, solve_user.hip) both run this function, which is why they agree bit for
+// bit.  For j < steps:  u_app = u_nom[j] (+ K[j] (x - x_nom[j]) with feedback),  x <- f_plant(x, u_app) (+ disturbance[j]),
+// f_plant = qt_step on a copy of the controller's parameter block that carries the plant's integrator and physical parameters
+// (its own, or row b of plant_phys: values, chosen behind a branch).  xnom / unom / Kb: the trajectory's nominal rows; xh: its
+// state, in and out; xrows: row 0 of its output states (row j + 1 is written), urows: row 0 of its applied controls; dist (or
+// NULL): its disturbance row of the first step, the next step's dist_stride floats on.
+template <int MODEL>
+__device__ __forceinline__ void track_body(const quattro_model_params& p, const PlantSpec& plant,
+                                           const float* __restrict__ plant_phys, const bool feedback,
+                                           const float* __restrict__ xnom, const float* __restrict__ unom,
+                                           const float* __restrict__ Kb, float* xh, const int steps,
+                                           const float* __restrict__ dist, const size_t dist_stride, float* __restrict__ xrows,
+                                           float* __restrict__ urows, const size_t b) {
+#pragma clang fp contract(off)
+  constexpr int NX = ModelDims<MODEL>::NX, NU = ModelDims<MODEL>::NU;
+  float ph[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) ph[i] = plant.phys[i];
+  if (plant_phys != nullptr) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) ph[i] = plant_phys[b * 8 + i];
+  }
+  quattro_model_params pp = p;
+  pp.integrator = plant.integrator;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) pp.phys[i] = ph[i];
+  for (int j = 0; j < steps; ++j) {
+    float ua[NU], xn[NX];
+    load_vec<NU>(unom + (size_t)j * NU, ua);
+    if (feedback) {
+      float xr[NX], Kj[NU * NX];
+      load_vec<NX>(xnom + (size_t)j * NX, xr);
+      load_vec<NU * NX>(Kb + (size_t)j * NU * NX, Kj);
+#pragma unroll
+      for (int a = 0; a < NU; ++a) {
+#pragma unroll
+        for (int i = 0; i < NX; ++i) ua[a] = fmaf(Kj[a * NX + i], xh[i] - xr[i], ua[a]);
+      }
+    }
+    if (pp.integrator == QUATTRO_INTEGRATOR_RK4) qt_step<MODEL, true>(pp, xh, ua, xn);
+    else qt_step<MODEL, false>(pp, xh, ua, xn);
+    if (dist != nullptr) {
+#pragma unroll
+      for (int i = 0; i < NX; ++i) xn[i] += dist[(size_t)j * dist_stride + i];
+    }
+    store_vec<NU>(urows + (size_t)j * NU, ua);
+    store_vec<NX>(xrows + (size_t)(j + 1) * NX, xn);
+#pragma unroll
+    for (int i = 0; i < NX; ++i) xh[i] = xn[i];
+  }
+}
+
+// track_body for the plan of a persistent loop that starts at plant step s0 of the run (Loop = SolveLoop, solve_loop.h): on the
+// nominal and gains the solve left behind, into the run's trajectory arrays
+template <int MODEL, class Loop>
+__device__ __forceinline__ void track_plan(const quattro_model_params& p, const Loop& c, const size_t bb, float* xh, const size_t s0) {
+  constexpr int NX = ModelDims<MODEL>::NX, NU = ModelDims<MODEL>::NU;
+  const size_t n_tot = (size_t)c.n_ctrl * c.hold;
+  track_body<MODEL>(p, c.plant, c.plant_phys, c.feedback != 0, c.x + bb * (c.N + 1) * NX, c.u + bb * c.N * NU,
+                    c.K + bb * c.N * NU * NX, xh, c.hold,
+                    c.disturbance != nullptr ? c.disturbance + (s0 * c.B + bb) * NX : nullptr, (size_t)c.B * NX,
+                    c.traj_x + (bb * (n_tot + 1) + s0) * NX, c.traj_u + (bb * n_tot + s0) * NU, bb);
+}
+
 // Fused line search: LPT consecutive lanes per trajectory (8 in the stand-alone kernel, 16 inside the cart-pole's device-resident
 // loop, whose sweep owns a 16-lane row per trajectory, 64 inside a user model's, whose sweep owns the wave), lane ai < n_alpha <= 8 of them rolls candidate ai out.  Every candidate
 // leaves its (x', u') in the scratch; after the ballot the trajectory's LPT lanes copy the accepted candidate over the nominal.

@@ -88,7 +88,44 @@ __global__ __launch_bounds__(64) void linesearch_quad_kernel(const quattro_model
                                      blockIdx.x * blockDim.x + threadIdx.x, false);
 }
 
+// tracked plant steps (quattro_track_f32): quad per trajectory, 16 trajectories per wave, as simulate_quad_kernel maps them; the
+// steps themselves are quad_track_body, the function the persistent MPC loop runs between its solves
+__global__ __launch_bounds__(64) void track_quad_kernel(const float dt, const PlantSpec plant, const float* __restrict__ plant_phys,
+                                                        const float* __restrict__ x0, const float* __restrict__ x_nom,
+                                                        const float* __restrict__ u_nom, const float* __restrict__ K,
+                                                        const int feedback, const int B, const int N, const int n_steps,
+                                                        const float* __restrict__ disturbance, float* __restrict__ x_out,
+                                                        float* __restrict__ u_out) {
+  const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+  const int b = gid >> 2;
+  const bool live = b < B;
+  const size_t bb = live ? b : 0;
+  const LaneConst L = lane_const_plant(plant, plant_phys, bb, dt, gid & 3);
+  const int wb = __builtin_amdgcn_readfirstlane(b);         // the wave's first trajectory (gid grows with the lane; wb < B)
+  const NomSrc nom(L, x_nom, u_nom, K, u_nom, N, wb, live ? b - wb : 0, 16);      // (no feed-forward array: never loaded)
+  float xh[4];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) xh[g] = x0[bb * NX + 3 * g + L.a];
+  float* xrows = x_out + bb * (size_t)(n_steps + 1) * NX + L.a;
+  if (live && L.j < 3) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) xrows[3 * g] = xh[g];
+  }
+  quad_track_body(L, plant.integrator == QUATTRO_INTEGRATOR_RK4, feedback != 0, nom, xh, n_steps,
+                  disturbance != nullptr ? disturbance + bb * NX + L.a : nullptr, (size_t)B * NX, live, xrows,
+                  u_out + bb * (size_t)n_steps * NU + L.j);
+}
+
 }  // namespace
+
+int quattro_launch_track_quad(const quattro_model_params& p, const PlantSpec& plant, const float* plant_phys, const float* x0,
+                              const float* x_nom, const float* u_nom, const float* K, int feedback, int B, int N, int n_steps,
+                              const float* disturbance, float* x_out, float* u_out, hipStream_t stream) {
+  const long long tot = (long long)B * 4;
+  hipLaunchKernelGGL(track_quad_kernel, dim3((unsigned)((tot + 63) / 64)), dim3(64), 0, stream, p.dt, plant, plant_phys, x0, x_nom,
+                     u_nom, K, feedback, B, N, n_steps, disturbance, x_out, u_out);
+  return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;
+}
 
 int quattro_launch_simulate_quad(const quattro_model_params& p, const float* x0, const float* u, int B, int N, float* x,
                                  double* cost, hipStream_t stream) {

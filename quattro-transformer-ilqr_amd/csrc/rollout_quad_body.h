@@ -62,6 +62,37 @@ __device__ __forceinline__ LaneConst lane_const(const quattro_model_params& p, i
   return L;
 }
 
+// The lane constants of a PLANT (quattro_track_f32, quattro_mpc_run_plant_f32): lane_const's role and rate-function constants —
+// a plant has no cost, its weights stay zero and unused.  The parameters are the plant's own or, with plant_phys, row bb of that
+// array: chosen as VALUES behind a wave-uniform branch, never as a pointer into either block (lane_const's note on pointer phis).
+// (The formulas are lane_const's, restated: routing lane_const itself through a shared helper reorders its parameter loads, and
+//  the line-search kernels' register allocation follows that order — one more VGPR in rollout_quad_kernel.)
+__device__ __forceinline__ LaneConst lane_const_plant(const PlantSpec& plant, const float* __restrict__ plant_phys, size_t bb,
+                                                      float dt, int j) {
+  float ph[7];
+#pragma unroll
+  for (int i = 0; i < 7; ++i) ph[i] = plant.phys[i];
+  if (plant_phys != nullptr) {
+#pragma unroll
+    for (int i = 0; i < 7; ++i) ph[i] = plant_phys[bb * 8 + i];
+  }
+  const float mass = ph[0], Ix = ph[1], Iy = ph[2], Iz = ph[3], arm = ph[4], grav = ph[5], kyaw = ph[6];
+  LaneConst L{};
+  L.j = j;
+  L.a = j == 3 ? 0 : j;
+  L.is0 = L.a == 0;
+  L.is1 = L.a == 1;
+  const float s0 = L.sel(-1.0f, 1.0f, 1.0f), s1 = L.sel(1.0f, 1.0f, -1.0f), s2 = L.sel(1.0f, -1.0f, 1.0f),
+              s3 = L.sel(-1.0f, -1.0f, -1.0f);
+  const float gain = L.sel(arm / Ix, arm / Iy, kyaw / Iz);
+  L.tc[0] = s0 * gain; L.tc[1] = s1 * gain; L.tc[2] = s2 * gain; L.tc[3] = s3 * gain;
+  L.gy = L.sel((Iy - Iz) / Ix, (Iz - Ix) / Iy, (Ix - Iy) / Iz);
+  L.gz = L.sel(0.0f, 0.0f, -grav);
+  L.inv_mass = 1.0f / mass;
+  L.dt = dt;
+  return L;
+}
+
 // the four controls of the quad (lane j owns u_j), in every lane: broadcast ONCE per step and shared by the rate
 // function (four calls under RK4) and the store
 struct QuadU {
@@ -210,6 +241,17 @@ struct NomLane {
       K[i] = make_float4(__int_as_float(q[0]), __int_as_float(q[1]), __int_as_float(q[2]), __int_as_float(q[3]));
     }
   }
+  // the same without the feed-forward term (a tracked plant step follows the nominal itself: k plays no part, `k` stays unset)
+  __device__ __forceinline__ void load_track(const NomSrc& s, int t) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) x[g] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(s.rx, s.vx + 12 * g, t * (NX * 4), 0));
+    u = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(s.ru, s.vu, t * (NU * 4), 0));
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const auto q = __builtin_amdgcn_raw_buffer_load_b128(s.rK, s.vK + 16 * i, t * (NU * NX * 4), 0);
+      K[i] = make_float4(__int_as_float(q[0]), __int_as_float(q[1]), __int_as_float(q[2]), __int_as_float(q[3]));
+    }
+  }
 };
 
 // Stores.  One 16-byte store per lane per step: the x' row (12 floats, state 3g+a in lane a / register g) is transposed
@@ -271,6 +313,49 @@ __device__ __forceinline__ float gain_dot(const float4* K, const float* dx, floa
                  "v"(K[1].x), "v"(K[1].y), "v"(K[1].z), "v"(K[1].w), "v"(K[2].x), "v"(K[2].y), "v"(K[2].z), "v"(K[2].w));
 #undef QT_FD
   return acc;
+}
+
+// Tracked plant steps by a quad, stated ONCE for this lane mapping: track_quad_kernel (rollout_quad.hip) and the persistent loop's
+// mpc_advance (solve_quad.hip) both run this function, which is why they agree bit for bit.  For j < steps:
+//   u_app = u_nom[j] (+ K[j] (x - x_nom[j]) with feedback),   x <- f_plant(x, u_app) (+ disturbance[j])
+// with f_plant the quadrotor step of L (lane_const_plant) under the plant's integrator — a wave-uniform runtime branch, so the
+// callers need no template dimension for it.  xh: the quad's state, in and out.  Lane j stores u_app_j at urows[j * NU], an axis
+// lane its four states of row j + 1 at xrows[(j + 1) * NX + 3 g]; dist (or NULL): this lane's element of the first step's
+// disturbance row, the next step's dist_stride floats on.  Every quad of the wave runs along (the DPP exchanges need it); only
+// `live` ones store.  No implicit fma contraction: the two translation units must round alike.
+__device__ __forceinline__ void quad_track_body(const LaneConst& L, const bool rk4, const bool feedback, const NomSrc& nom,
+                                                float* xh, const int steps, const float* __restrict__ dist,
+                                                const size_t dist_stride, const bool live, float* __restrict__ xrows,
+                                                float* __restrict__ urows) {
+#pragma clang fp contract(off)
+  for (int j = 0; j < steps; ++j) {
+    NomLane nb;
+    nb.load_track(nom, j);
+    float ua = nb.u;
+    if (feedback) {
+      float dx[4];
+#pragma unroll
+      for (int g = 0; g < 4; ++g) dx[g] = xh[g] - nb.x[g];
+      ua = gain_dot(nb.K, dx, ua);
+    }
+    const QuadU U(ua);
+    float xn[4];
+    if (rk4) quad_step<true>(L, xh, U, xn);
+    else quad_step<false>(L, xh, U, xn);
+    if (dist != nullptr) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) xn[g] += dist[(size_t)j * dist_stride + 3 * g];
+    }
+    if (live) {
+      urows[(size_t)j * NU] = ua;
+      if (L.j < 3) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) xrows[(size_t)(j + 1) * NX + 3 * g] = xn[g];
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) xh[g] = xn[g];
+  }
 }
 
 // One closed-loop rollout by a quad.  Returns this LANE's partial of sum_t L + Lf (fp64); quad_sum() gives the total.

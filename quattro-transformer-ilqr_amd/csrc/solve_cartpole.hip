@@ -22,7 +22,9 @@ struct CpSolveArgs {
   SolveLoop c;          // x [B][N+1][4], u [B][N][1], K [B][N][1][4], k [B][N][1]
 };
 
-template <bool RK4>
+// PLANT: the loop of quattro_mpc_run_plant_f32 (a plant of its own, c.hold tracked steps per plan); the <RK4, false> code is the
+// loop as it always was
+template <bool RK4, bool PLANT>
 __global__ __launch_bounds__(QT_WAVE) void solve_cartpole_kernel(const CpSolveArgs a) {
   constexpr int MODEL = QUATTRO_MODEL_CARTPOLE, NX = 4;
   __shared__ __attribute__((aligned(16))) float s_stage[4 * cp16::STAGE_FLOATS];
@@ -37,7 +39,7 @@ __global__ __launch_bounds__(QT_WAVE) void solve_cartpole_kernel(const CpSolveAr
   float* stage = s_stage + (lane >> 4) * cp16::STAGE_FLOATS;
   const int n_ctrl = c.n_ctrl > 0 ? c.n_ctrl : 1;
   for (int cs = 0; cs < n_ctrl; ++cs) {
-    wave_step_prologue<NX>(c, bb, cs, have && sub == 0,
+    wave_step_prologue<NX, PLANT>(c, bb, cs, have && sub == 0,
                            [&] { simulate_body<MODEL, RK4>(a.p, c.x0, c.u, N, c.x, c.cost, b); });
     const bool logging = c.log.rec != nullptr && c.n_ctrl == 0;
     for (int it = 0; it < c.max_iter; ++it) {
@@ -60,8 +62,9 @@ __global__ __launch_bounds__(QT_WAVE) void solve_cartpole_kernel(const CpSolveAr
     // apply u_0, record, shift the warm start: CartPoleMPC._ilqr_step after optimize() (cartpole_mpc.py:331) and the
     // simulator's step around it
     if (c.n_ctrl > 0)
-      wave_mpc_epilogue<NX, 1, 16>(c, bb, cs, sub, have,
-                                   [&](const float* xo, const float* u0, float* xn) { qt_step<MODEL, RK4>(a.p, xo, u0, xn); });
+      wave_mpc_epilogue<NX, 1, 16, PLANT>(c, bb, cs, sub, have,
+                                          [&](const float* xo, const float* u0, float* xn) { qt_step<MODEL, RK4>(a.p, xo, u0, xn); },
+                                          [&](float* xh, const size_t s0) { track_plan<MODEL>(a.p, c, bb, xh, s0); });
   }
 }
 
@@ -70,11 +73,14 @@ __global__ __launch_bounds__(QT_WAVE) void solve_cartpole_kernel(const CpSolveAr
 int quattro_launch_solve_cartpole(const quattro_model_params& p, const SolveLoop& c, hipStream_t stream) {
   const CpSolveArgs a{p, c};
   const dim3 grid((unsigned)((c.B + 3) / 4));
-  if (p.integrator == QUATTRO_INTEGRATOR_EULER)
-    hipLaunchKernelGGL((solve_cartpole_kernel<false>), grid, dim3(QT_WAVE), 0, stream, a);
-  else if (p.integrator == QUATTRO_INTEGRATOR_RK4)
-    hipLaunchKernelGGL((solve_cartpole_kernel<true>), grid, dim3(QT_WAVE), 0, stream, a);
-  else
-    return QUATTRO_ERR_UNSUPPORTED;
+  if (p.integrator != QUATTRO_INTEGRATOR_EULER && p.integrator != QUATTRO_INTEGRATOR_RK4) return QUATTRO_ERR_UNSUPPORTED;
+  const bool rk4 = p.integrator == QUATTRO_INTEGRATOR_RK4;
+  if (c.hold > 0) {
+    if (rk4) hipLaunchKernelGGL((solve_cartpole_kernel<true, true>), grid, dim3(QT_WAVE), 0, stream, a);
+    else hipLaunchKernelGGL((solve_cartpole_kernel<false, true>), grid, dim3(QT_WAVE), 0, stream, a);
+  } else {
+    if (rk4) hipLaunchKernelGGL((solve_cartpole_kernel<true, false>), grid, dim3(QT_WAVE), 0, stream, a);
+    else hipLaunchKernelGGL((solve_cartpole_kernel<false, false>), grid, dim3(QT_WAVE), 0, stream, a);
+  }
   return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;
 }

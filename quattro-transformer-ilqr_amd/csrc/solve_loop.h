@@ -29,10 +29,23 @@ struct SolveLoop {
   float* traj_u;              // [B][n_ctrl][m]
   int32_t* traj_iters;        // [B][n_ctrl]
   const float* disturbance;   // [n_ctrl][B][n] or NULL
+  // a plant of its own and gain feedback between solves (quattro_mpc_run_plant_f32; the PLANT instantiations of the kernels).
+  // n_ctrl then counts PLANS: each is followed by `hold` tracked plant steps, the trajectory arrays hold n_ctrl * hold steps
+  // (traj_iters one entry per plan) and the warm start shifts by `hold`.  hold == 0: the loops above as they always were.
+  PlantSpec plant;            // the plant's integrator and physical parameters
+  const float* plant_phys;    // [B][8] per-controller physical parameters, or NULL
+  int hold, feedback;
   SolveLogDev log;            // per-iteration log ring (rec == nullptr: none); plain solves only (n_ctrl == 0)
 };
 
 namespace {
+
+// plant steps a run records (the trajectory arrays' row count)
+template <bool PLANT>
+__device__ __forceinline__ int traj_steps(const SolveLoop& c) {
+  if constexpr (PLANT) return c.n_ctrl * c.hold;
+  else return c.n_ctrl;
+}
 
 // every store of this wave has completed before its lanes read what other lanes of the wave wrote (the phases of a
 // wave-private loop hand trajectories over through global memory)
@@ -45,14 +58,14 @@ __device__ __forceinline__ void wave_handoff() {
 // Top of control step cs of a wave-private loop: the lane that leads trajectory bb (lead) records its start state (MPC),
 // resets the per-solve state (what a host caller resets before a solve; after the last control step it stays as that solve
 // left it) and rolls the nominal out from x0 (simulate(): the model's rollout body, run by that lane alone).
-template <int NX, class Simulate>
+template <int NX, bool PLANT, class Simulate>
 __device__ __forceinline__ void wave_step_prologue(const SolveLoop& c, const size_t bb, const int cs, const bool lead,
                                                    Simulate simulate) {
   if ((c.flags & (QUATTRO_SOLVE_SIMULATE | QUATTRO_SOLVE_RESET)) == 0 && c.n_ctrl == 0) return;
   if (lead) {
     if (c.n_ctrl > 0 && cs == 0) {
 #pragma unroll
-      for (int i = 0; i < NX; ++i) c.traj_x[(bb * (c.n_ctrl + 1)) * NX + i] = c.x0[bb * NX + i];
+      for (int i = 0; i < NX; ++i) c.traj_x[(bb * (traj_steps<PLANT>(c) + 1)) * NX + i] = c.x0[bb * NX + i];
     }
     if (c.n_ctrl > 0 || (c.flags & QUATTRO_SOLVE_RESET) != 0) {
       c.iters[bb] = 0;
@@ -69,27 +82,48 @@ __device__ __forceinline__ void wave_step_prologue(const SolveLoop& c, const siz
 // trajectory): apply u_0 to the plant (step(x, u, x_next): the device model itself), add the disturbance, record, and shift the
 // warm start u <- (u_1 .. u_{N-1}, u_{N-1}) in passes of a wave's worth of elements.  Every element of a pass is read before
 // any is written.
-template <int NX, int NU, int W, class Step>
+// PLANT (quattro_mpc_run_plant_f32): the lead lane first runs the plan's c.hold tracked steps on the plant (track(x, first step):
+// the model's track_body on the nominal and gains this solve left behind, writing the trajectory rows), then the warm start
+// shifts by c.hold: u <- (u_h .. u_{N-1}, u_{N-1} x h).  A pass reads rows at or above the ones it writes, and the rows above
+// belong to later passes (or to none: row N - 1), so "read before written" holds pass by pass as before.
+template <int NX, int NU, int W, bool PLANT, class Step, class Track>
 __device__ __forceinline__ void wave_mpc_epilogue(const SolveLoop& c, const size_t bb, const int cs, const int l, const bool have,
-                                                  Step step) {
+                                                  Step step, Track track) {
   constexpr int PER = QT_WAVE / W;                             // elements a lane moves per pass
   float* ub = c.u + bb * c.N * NU;
   const int tot = (c.N - 1) * NU;                              // elements that move
   const bool lead = have && l == 0;
-  for (int base = 0; base < tot || base == 0; base += W * PER) {    // (at least once: the plant step below rides on the first pass, also when N = 1 and nothing shifts)
+  if constexpr (PLANT) {
+    if (lead) {
+      float xh[NX];
+#pragma unroll
+      for (int i = 0; i < NX; ++i) xh[i] = c.x_cur[bb * NX + i];
+      track(xh, (size_t)cs * c.hold);
+#pragma unroll
+      for (int i = 0; i < NX; ++i) c.x_cur[bb * NX + i] = xh[i];
+      c.traj_iters[bb * c.n_ctrl + cs] = c.iters[bb];
+    }
+    wave_handoff();                                            // the tracked steps have read their controls before any moves
+  }
+  for (int base = 0; base < tot || (!PLANT && base == 0); base += W * PER) {    // (at least once: the plant step below rides on the first pass, also when N = 1 and nothing shifts)
     float v[PER];
 #pragma unroll
     for (int q = 0; q < PER; ++q) {
       const int e = base + l + W * q;
-      v[q] = (have && e < tot) ? ub[e + NU] : 0.0f;
+      int src = e + NU;
+      if constexpr (PLANT) {
+        const int row = e / NU + c.hold;                       // row t takes row min(t + h, N - 1)
+        src = row < c.N ? e + c.hold * NU : (c.N - 1) * NU + e % NU;
+      }
+      v[q] = (have && e < tot) ? ub[src] : 0.0f;
     }
     float u0[NU] = {};
-    if (base == 0 && lead) {
+    if (!PLANT && base == 0 && lead) {
 #pragma unroll
       for (int q = 0; q < NU; ++q) u0[q] = ub[q];
     }
     wave_handoff();                                            // every element of the pass is read before any is written
-    if (base == 0 && lead) {
+    if (!PLANT && base == 0 && lead) {
       float xo[NX], xn[NX];
 #pragma unroll
       for (int i = 0; i < NX; ++i) xo[i] = c.x_cur[bb * NX + i];

@@ -48,35 +48,58 @@ constexpr int LS_PRIO = 3;
 // QuadrotorMPC.control_step does after optimize() (quadrotor_mpc.py:121-122) plus the simulator's step around it.
 // Run by wave 0: quad q = lane >> 2 < 2 owns trajectory b0 + q for the plant step; the shift is spread over 32 lanes per
 // trajectory.
-template <bool RK4>
+// PLANT (quattro_mpc_run_plant_f32): cs counts plans.  The quad runs the plan's a.hold tracked steps on the plant — quad_track_body
+// on the nominal and gains this solve left behind, with the plant's lane constants — and the warm start shifts by a.hold:
+// u <- (u_h .. u_{N-1}, u_{N-1} x h).  A pass of the shift reads rows at or above the ones it writes, and the rows above belong to
+// later passes (or to none: row N - 1), so "read before written" holds pass by pass as before.
+template <bool RK4, bool PLANT>
 __device__ __forceinline__ void mpc_advance(const SolveArgs& args, const int b0, const int lane, const int cs) {
   const SolveLoop& a = args.c;
   const int q = lane >> 2, tb = b0 + q;
   const bool live = lane < 8 && tb < a.B;
   const size_t bb = live ? tb : 0;
-  const LaneConst L = lane_const(args.fa.p, lane & 3);
   const int N = a.N;
-  float xo[4], xn[4];
+  if constexpr (PLANT) {
+    const LaneConst L = lane_const_plant(a.plant, a.plant_phys, bb, args.fa.p.dt, lane & 3);
+    const NomSrc nom(L, a.x, a.u, a.K, a.k, N, b0, live ? q : 0, 2);
+    const size_t n_tot = (size_t)a.n_ctrl * a.hold, s0 = (size_t)cs * a.hold;
+    float xh[4];
 #pragma unroll
-  for (int g = 0; g < 4; ++g) xo[g] = a.x_cur[bb * NX + 3 * g + L.a];
-  const float u0 = a.u[bb * N * NU + L.j];
-  const QuadU U(u0);
-  quad_step<RK4>(L, xo, U, xn);
-  if (a.disturbance != nullptr) {
+    for (int g = 0; g < 4; ++g) xh[g] = a.x_cur[bb * NX + 3 * g + L.a];
+    quad_track_body(L, a.plant.integrator == QUATTRO_INTEGRATOR_RK4, a.feedback != 0, nom, xh, a.hold,
+                    a.disturbance != nullptr ? a.disturbance + (s0 * a.B + bb) * NX + L.a : nullptr, (size_t)a.B * NX, live,
+                    a.traj_x + (bb * (n_tot + 1) + s0) * NX + L.a, a.traj_u + (bb * n_tot + s0) * NU + L.j);
+    if (live) {
+      if (L.j < 3) {
 #pragma unroll
-    for (int g = 0; g < 4; ++g) xn[g] += a.disturbance[((size_t)cs * a.B + bb) * NX + 3 * g + L.a];
-  }
-  if (live) {
-    a.traj_u[(bb * a.n_ctrl + cs) * NU + L.j] = u0;
-    if (L.j < 3) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        a.x_cur[bb * NX + 3 * g + L.a] = xn[g];
-        a.traj_x[(bb * (a.n_ctrl + 1) + cs + 1) * NX + 3 * g + L.a] = xn[g];
+        for (int g = 0; g < 4; ++g) a.x_cur[bb * NX + 3 * g + L.a] = xh[g];
       }
+      if (L.j == 0) a.traj_iters[bb * a.n_ctrl + cs] = a.iters[bb];
     }
-    if (L.j == 0) {
-      a.traj_iters[bb * a.n_ctrl + cs] = a.iters[bb];
+  } else {
+    const LaneConst L = lane_const(args.fa.p, lane & 3);
+    float xo[4], xn[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) xo[g] = a.x_cur[bb * NX + 3 * g + L.a];
+    const float u0 = a.u[bb * N * NU + L.j];
+    const QuadU U(u0);
+    quad_step<RK4>(L, xo, U, xn);
+    if (a.disturbance != nullptr) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) xn[g] += a.disturbance[((size_t)cs * a.B + bb) * NX + 3 * g + L.a];
+    }
+    if (live) {
+      a.traj_u[(bb * a.n_ctrl + cs) * NU + L.j] = u0;
+      if (L.j < 3) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          a.x_cur[bb * NX + 3 * g + L.a] = xn[g];
+          a.traj_x[(bb * (a.n_ctrl + 1) + cs + 1) * NX + 3 * g + L.a] = xn[g];
+        }
+      }
+      if (L.j == 0) {
+        a.traj_iters[bb * a.n_ctrl + cs] = a.iters[bb];
+      }
     }
   }
   // warm start u <- (u_1, ..., u_{N-1}, u_{N-1}): every element is read before any is written (the loads below are
@@ -91,7 +114,9 @@ __device__ __forceinline__ void mpc_advance(const SolveArgs& args, const int b0,
 #pragma unroll
       for (int i = 0; i < MAXI; ++i) {
         const int e = base + l32 + 32 * i;
-        v[i] = e < tot ? ub[e + NU] : 0.0f;
+        int src = e + NU;
+        if constexpr (PLANT) src = e / NU + a.hold < N ? e + a.hold * NU : (N - 1) * NU + e % NU;    // row t takes row min(t + h, N - 1)
+        v[i] = e < tot ? ub[src] : 0.0f;
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 #pragma unroll
@@ -127,7 +152,9 @@ __device__ __forceinline__ void wg_sync() {
   __syncthreads();
 }
 
-template <bool RK4>
+// PLANT: the loop of quattro_mpc_run_plant_f32; the <RK4, false> code is the loop as it always was (quattro_ilqr_solve_f32,
+// quattro_mpc_run_f32)
+template <bool RK4, bool PLANT>
 __global__ __launch_bounds__(128, 4) void solve_quad_kernel(const SolveArgs) {
   const KernArgPtr kap = (KernArgPtr)__builtin_amdgcn_kernarg_segment_ptr();   // the one by-value argument sits at offset 0
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -163,7 +190,7 @@ __global__ __launch_bounds__(128, 4) void solve_quad_kernel(const SolveArgs) {
           if (a.n_ctrl > 0 && cs == 0 && (ln & 3) < 3) {
 #pragma unroll
             for (int g = 0; g < 4; ++g)
-              a.traj_x[(tb * (a.n_ctrl + 1)) * NX + 3 * g + (ln & 3)] = a.x0[tb * NX + 3 * g + (ln & 3)];
+              a.traj_x[(tb * (traj_steps<PLANT>(a) + 1)) * NX + 3 * g + (ln & 3)] = a.x0[tb * NX + 3 * g + (ln & 3)];
           }
           if ((ln & 3) == 0) {       // per-solve state of this control step (what a host caller resets before a solve); after
             a.iters[tb] = 0;         // the last control step it stays as that solve left it
@@ -235,7 +262,7 @@ __global__ __launch_bounds__(128, 4) void solve_quad_kernel(const SolveArgs) {
         const SolveArgs& args = fresh_args(kap);
         int ln = lane;
         asm volatile("" : "+v"(ln));
-        mpc_advance<RK4>(args, b0, ln, cs);
+        mpc_advance<RK4, PLANT>(args, b0, ln, cs);
       }
       wg_sync();
     }
@@ -270,9 +297,13 @@ int quattro_launch_solve_quad(const quattro_model_params& p, const SolveLoop& c,
   a.stamps = stamps;
   a.stamp_rows = stamp_rows;
   const dim3 grid((unsigned)((c.B + 1) / 2));
-  if (p.integrator == QUATTRO_INTEGRATOR_RK4)
-    hipLaunchKernelGGL((solve_quad_kernel<true>), grid, dim3(128), 0, stream, a);
-  else
-    hipLaunchKernelGGL((solve_quad_kernel<false>), grid, dim3(128), 0, stream, a);
+  const bool rk4 = p.integrator == QUATTRO_INTEGRATOR_RK4;
+  if (c.hold > 0) {      // (quattro_mpc_run_plant_f32 alone sets it)
+    if (rk4) hipLaunchKernelGGL((solve_quad_kernel<true, true>), grid, dim3(128), 0, stream, a);
+    else hipLaunchKernelGGL((solve_quad_kernel<false, true>), grid, dim3(128), 0, stream, a);
+  } else {
+    if (rk4) hipLaunchKernelGGL((solve_quad_kernel<true, false>), grid, dim3(128), 0, stream, a);
+    else hipLaunchKernelGGL((solve_quad_kernel<false, false>), grid, dim3(128), 0, stream, a);
+  }
   return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;
 }

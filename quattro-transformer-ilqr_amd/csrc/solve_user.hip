@@ -44,7 +44,9 @@ struct UserSolveArgs {
 
 // (two waves per SIMD: left to itself the allocator takes 300 registers for the dual-number linearisation next to the tile sweep —
 //  one wave per SIMD — and the loop runs 3x slower than with the 42 spilled registers this bound costs)
-template <bool RK4>
+// PLANT: the loop of quattro_mpc_run_plant_f32 (a plant of its own, c.hold tracked steps per plan); the <RK4, false> code is the
+// loop as it always was
+template <bool RK4, bool PLANT>
 __global__ __launch_bounds__(QT_WAVE, 2) void solve_user_kernel(const UserSolveArgs a) {
   constexpr int MODEL = QUATTRO_MODEL_USER, NX = QT_USER_NX, NU = QT_USER_NU, NZ = NX + NU;
   constexpr int LPI = NZ <= 8 ? 8 : (NZ <= 16 ? 16 : 32), IPP = QT_WAVE / LPI;      // lanes per item, items per pass
@@ -67,7 +69,7 @@ __global__ __launch_bounds__(QT_WAVE, 2) void solve_user_kernel(const UserSolveA
   volatile int32_t* act_flag = c.active + b;     // written by this wave's line search: always re-read from memory
   const int n_ctrl = c.n_ctrl > 0 ? c.n_ctrl : 1;
   for (int cs = 0; cs < n_ctrl; ++cs) {
-    wave_step_prologue<NX>(c, bb, cs, lane == 0, [&] { simulate_body<MODEL, RK4>(a.p, c.x0, c.u, N, c.x, c.cost, b); });
+    wave_step_prologue<NX, PLANT>(c, bb, cs, lane == 0, [&] { simulate_body<MODEL, RK4>(a.p, c.x0, c.u, N, c.x, c.cost, b); });
     const bool logging = c.log.rec != nullptr && c.n_ctrl == 0;
     for (int it = 0; it < c.max_iter; ++it) {
       if (!(force || *act_flag != 0)) break;       // wave-uniform: one trajectory per wave
@@ -114,8 +116,9 @@ __global__ __launch_bounds__(QT_WAVE, 2) void solve_user_kernel(const UserSolveA
                 *(volatile double*)(c.cost + b), lane, QT_WAVE);
     }
     if (c.n_ctrl > 0)            // apply u_0 to the plant (the device model itself), record, shift the warm start
-      wave_mpc_epilogue<NX, NU, QT_WAVE>(c, bb, cs, lane, true,
-                                         [&](const float* xo, const float* u0, float* xn) { qt_step<MODEL, RK4>(a.p, xo, u0, xn); });
+      wave_mpc_epilogue<NX, NU, QT_WAVE, PLANT>(c, bb, cs, lane, true,
+                                                [&](const float* xo, const float* u0, float* xn) { qt_step<MODEL, RK4>(a.p, xo, u0, xn); },
+                                                [&](float* xh, const size_t s0) { track_plan<MODEL>(a.p, c, bb, xh, s0); });
   }
 }
 
@@ -172,11 +175,14 @@ int quattro_launch_solve_user(const quattro_model_params& p, const SolveLoop& c,
                               hipStream_t stream) {
   const UserSolveArgs a{p, rec, VxN, VxxN, c};
   const dim3 grid((unsigned)c.B);
-  if (p.integrator == QUATTRO_INTEGRATOR_EULER)
-    hipLaunchKernelGGL((solve_user_kernel<false>), grid, dim3(QT_WAVE), 0, stream, a);
-  else if (p.integrator == QUATTRO_INTEGRATOR_RK4)
-    hipLaunchKernelGGL((solve_user_kernel<true>), grid, dim3(QT_WAVE), 0, stream, a);
-  else
-    return QUATTRO_ERR_UNSUPPORTED;
+  if (p.integrator != QUATTRO_INTEGRATOR_EULER && p.integrator != QUATTRO_INTEGRATOR_RK4) return QUATTRO_ERR_UNSUPPORTED;
+  const bool rk4 = p.integrator == QUATTRO_INTEGRATOR_RK4;
+  if (c.hold > 0) {
+    if (rk4) hipLaunchKernelGGL((solve_user_kernel<true, true>), grid, dim3(QT_WAVE), 0, stream, a);
+    else hipLaunchKernelGGL((solve_user_kernel<false, true>), grid, dim3(QT_WAVE), 0, stream, a);
+  } else {
+    if (rk4) hipLaunchKernelGGL((solve_user_kernel<true, false>), grid, dim3(QT_WAVE), 0, stream, a);
+    else hipLaunchKernelGGL((solve_user_kernel<false, false>), grid, dim3(QT_WAVE), 0, stream, a);
+  }
   return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;
 }

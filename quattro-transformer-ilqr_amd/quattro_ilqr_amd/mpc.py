@@ -236,7 +236,7 @@ class BatchedMPC:
         xs, _ = ops.simulate(self.model, x.contiguous(), u0.reshape(-1, 1, self.model.m).contiguous())
         return xs[:, 1].contiguous()
 
-    def run(self, x0, steps, disturbance=None, device_loop=True):
+    def run(self, x0, steps, disturbance=None, device_loop=True, *, plant=None, plant_phys=None, replan_every=1, feedback=False):
         """Closed loop for `steps` control steps from x0 (B,n); the plant is the device model itself (the reference's
         plant is MuJoCo, out of scope), plus an optional additive state disturbance tensor (steps, B, n).
         Returns dict(x (B,steps+1,n), u (B,steps,m), iters (B,steps)).
@@ -245,11 +245,37 @@ class BatchedMPC:
         wherever one exists, i.e. also for a user-compiled model): ALL `steps` control
         steps of all B controllers are ONE launch (quattro_mpc_run_f32) — no host call, synchronisation or tensor
         operation per control step; a controller that converges early goes on to its next control step at once.
-        Results are bit-identical to the host-driven loop below."""
+        Results are bit-identical to the host-driven loop below.
+
+        A plant of its own and gain feedback between solves (any of the four keywords off its default; `steps` are then PLANT
+        steps and `iters` is (B, steps // replan_every)):
+          plant         a DeviceModel like the controller's — same name, n, m, dt and, for a user model, library — whose integrator
+                        and phys are the plant's; its cost is ignored
+          plant_phys    (B, len(model.phys)): controller b's plant takes row b for its phys (B controllers, B plants)
+          replan_every  h: a solve every h plant steps; between solves u = u_nom[j] + (feedback ? K[j] (x - x_nom[j]) : 0) on the
+                        nominal and gains of the last solve (ops.track), and the warm start shifts by h
+          feedback      the gain term above on or off (open-loop hold against feedback hold); it is exactly zero for h = 1
+        The same one launch (quattro_mpc_run_plant_f32) where the plain loop has one; the host-driven form — solve, ops.track,
+        shift — otherwise, and always with a predictor.  ValueError, before anything touches the device: a plant that is not the
+        controller's problem, a plant_phys of the wrong shape, steps % replan_every != 0."""
+        h = int(replan_every)
+        plain = plant is None and plant_phys is None and h == 1 and not feedback
+        if not plain:
+            ops.check_plant(self.model, plant)
+            if h < 1 or h > self.horizon or steps % h != 0:
+                raise ValueError(f"steps ({steps}) must be a multiple of replan_every ({replan_every}) in 1..horizon")
+            if plant_phys is not None:
+                B0 = int(np.prod(tuple(np.shape(x0)))) // self.model.n
+                if tuple(plant_phys.shape) != (B0, len(self.model.phys)):
+                    raise ValueError(f"plant_phys must have shape {(B0, len(self.model.phys))} (got {tuple(plant_phys.shape)})")
+            if feedback and self.solver.max_iter < 1:
+                raise ValueError("feedback needs gains: max_iter >= 1")
         x = torch.as_tensor(x0, dtype=torch.float32, device=self.device).reshape(-1, self.model.n).contiguous()
         sv = self.solver
         use_kernel = (ops.model_can_device_loop(self.model) if device_loop == "always"
                       else bool(device_loop) and ops.model_has_device_loop(self.model))
+        if not plain:
+            plant_phys = ops.plant_phys_tensor(self.model, plant_phys, x.shape[0], self.device)
         if use_kernel and sv.tf is None:
             B, N, n, m = x.shape[0], self.horizon, self.model.n, self.model.m
             if self.u_warm is not None and self.u_warm.shape[0] != B:
@@ -264,15 +290,33 @@ class BatchedMPC:
             x_cur = x.clone()
             traj_x = torch.empty((B, steps + 1, n), dtype=torch.float32, device=self.device)
             traj_u = torch.empty((B, steps, m), dtype=torch.float32, device=self.device)
-            traj_it = torch.empty((B, steps), dtype=torch.int32, device=self.device)
+            traj_it = torch.empty((B, steps // h), dtype=torch.int32, device=self.device)
             dist_t = None
             if disturbance is not None:
                 dist_t = torch.as_tensor(disturbance, dtype=torch.float32, device=self.device).reshape(steps, B, n).contiguous()
+            extra = {} if plain else dict(plant=plant, plant_phys=plant_phys, hold=h, feedback=feedback)
             ops.mpc_run(self.model, x_cur, sv.x, sv.u, sv.K, sv.k, sv.cost, sv.tol, sv.max_iter, steps, sv._ws, traj_x,
                         traj_u, traj_it, disturbance=dist_t, alphas=sv.alphas, reg=sv.reg, alpha_idx=sv.alpha_idx,
-                        active=sv.active, iters=sv.iters, status=sv.status)
+                        active=sv.active, iters=sv.iters, status=sv.status, **extra)
             self.u_warm = sv.u.clone()
             return dict(x=traj_x, u=traj_u, iters=traj_it)
+        if not plain:
+            B, n = x.shape[0], self.model.n
+            if self.u_warm is not None and self.u_warm.shape[0] != B:
+                raise ValueError("batch size changed between control steps")
+            dist_t = None
+            if disturbance is not None:
+                dist_t = torch.as_tensor(disturbance, dtype=torch.float32, device=self.device).reshape(steps, B, n).contiguous()
+            xs, us, its = [x[:, None]], [], []
+            for c in range(steps // h):
+                out = sv.solve(x, self.u_warm)
+                xt, ut = ops.track(self.model, x, out["x"], out["u"], out["K"], h, plant=plant, plant_phys=plant_phys,
+                                   feedback=feedback, disturbance=None if dist_t is None else dist_t[c * h:(c + 1) * h])
+                u = out["u"]
+                self.u_warm = torch.cat([u[:, h:]] + [u[:, -1:]] * h, dim=1).contiguous()
+                x = xt[:, -1].contiguous()
+                xs.append(xt[:, 1:]); us.append(ut); its.append(out["iters"].clone())
+            return dict(x=torch.cat(xs, dim=1), u=torch.cat(us, dim=1), iters=torch.stack(its, dim=1))
         xs, us, its = [x], [], []
         for s in range(steps):
             _, u_seq, iters = self.control_step(x)

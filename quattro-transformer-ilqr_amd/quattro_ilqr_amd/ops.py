@@ -515,26 +515,98 @@ class PreparedSolve:
                       _stream() if stream is None else stream), "quattro_ilqr_solve_logged_f32")
 
 
+def check_plant(model, plant):
+    """A plant is the controller's own problem with other physical parameters and, if wanted, another integrator: the same name,
+    n, m, dt and, for a user model, the same library.  ValueError otherwise; host logic only."""
+    if plant is None:
+        return
+    same = (getattr(plant, "name", None) == model.name and getattr(plant, "model_id", None) == model.model_id
+            and (plant.n, plant.m) == (model.n, model.m) and float(plant.dt) == float(model.dt)
+            and getattr(plant, "lib_path", "") == getattr(model, "lib_path", ""))
+    if not same:
+        raise ValueError("plant must be the controller's model (name, n, m, dt and library) with its own phys / integrator")
+
+
+def plant_phys_tensor(model, plant_phys, B, device):
+    """(B, len(model.phys)) per-controller physical parameters -> the (B, 8) float32 device array the C ABI takes (None stays
+    None).  The shape is checked before anything touches the device."""
+    if plant_phys is None:
+        return None
+    shape = tuple(plant_phys.shape)
+    if shape != (B, len(model.phys)):
+        raise ValueError(f"plant_phys must have shape {(B, len(model.phys))} (got {shape})")
+    t = torch.as_tensor(plant_phys, dtype=torch.float32, device=device)
+    out = torch.zeros((B, 8), dtype=torch.float32, device=device)
+    out[:, :shape[1]] = t
+    return out
+
+
+def _plant_args(model, plant, plant_phys, B, device):
+    check_plant(model, plant)
+    pp = None if plant is None else plant.c_params()
+    if plant_phys is not None and not (isinstance(plant_phys, torch.Tensor) and tuple(plant_phys.shape) == (B, 8)
+                                       and plant_phys.is_cuda and plant_phys.dtype == torch.float32
+                                       and plant_phys.is_contiguous()):
+        plant_phys = plant_phys_tensor(model, plant_phys, B, device)
+    return (None if pp is None else ctypes.byref(pp)), pp, plant_phys
+
+
+def track(model, x0, x_nom, u_nom, K, steps, plant=None, plant_phys=None, feedback=True, disturbance=None):
+    """`steps` <= N plant steps from x0 (B,n) along the first rows of a nominal with its gains (quattro_track_f32):
+    u = u_nom[j] + (feedback ? K[j] (x - x_nom[j]) : 0), x <- f_plant(x, u) + disturbance[j].  plant: a DeviceModel like `model`
+    with the plant's integrator and phys (None = the model itself); plant_phys (B, len(model.phys)): per-controller phys.
+    -> x (B,steps+1,n), u (B,steps,m)."""
+    Bt, N, m = u_nom.shape
+    n = model.n
+    f32 = torch.float32
+    steps = int(steps)
+    if not 1 <= steps <= N:
+        raise ValueError("steps must be in 1..N")
+    _req(x0, (Bt, n), f32, "x0"); _req(x_nom, (Bt, N + 1, n), f32, "x_nom"); _req(u_nom, (Bt, N, model.m), f32, "u_nom")
+    _req(K, (Bt, N, m, n), f32, "K")
+    if disturbance is not None:
+        _req(disturbance, (steps, Bt, n), f32, "disturbance")
+    pref, keep, pphys = _plant_args(model, plant, plant_phys, Bt, u_nom.device)
+    x = torch.empty((Bt, steps + 1, n), dtype=f32, device=u_nom.device)
+    u = torch.empty((Bt, steps, m), dtype=f32, device=u_nom.device)
+    p = model.c_params()
+    check(_lib.load_for(model).quattro_track_f32(ctypes.byref(p), pref, _ptr(pphys), _ptr(x0), _ptr(x_nom), _ptr(u_nom), _ptr(K),
+                                                 int(bool(feedback)), Bt, N, steps, _ptr(disturbance), _ptr(x), _ptr(u), _stream()),
+          "quattro_track_f32")
+    return x, u
+
+
 def mpc_run(model, x_cur, x_nom, u_nom, K, k, cost, tol, max_iter, n_steps, workspace, traj_x, traj_u, traj_iters,
-            disturbance=None, alphas=ALPHAS, reg=QUU_REG, alpha_idx=None, active=None, iters=None, status=None):
+            disturbance=None, alphas=ALPHAS, reg=QUU_REG, alpha_idx=None, active=None, iters=None, status=None,
+            plant=None, plant_phys=None, hold=1, feedback=False):
     """B controllers x n_steps control steps (solve -> apply u_0 -> shift the warm start) in ONE launch
-    (quattro_mpc_run_f32); x_cur and u_nom advance in place, the closed-loop record goes to traj_x / traj_u / traj_iters."""
+    (quattro_mpc_run_f32); x_cur and u_nom advance in place, the closed-loop record goes to traj_x / traj_u / traj_iters.
+    plant / plant_phys / hold / feedback (any of them off its default: quattro_mpc_run_plant_f32): n_steps PLANT steps, a solve
+    every `hold` of them and the gain law of track() in between, on a plant of its own; traj_iters is then (B, n_steps / hold)."""
     Bt, N, m = u_nom.shape
     n = model.n
     f32, i32 = torch.float32, torch.int32
+    hold = int(hold)
+    plain = plant is None and plant_phys is None and hold == 1 and not feedback
+    if hold < 1 or n_steps % hold != 0:
+        raise ValueError("n_steps must be a multiple of hold >= 1")
     _req(x_cur, (Bt, n), f32, "x_cur"); _req(x_nom, (Bt, N + 1, n), f32, "x_nom"); _req(u_nom, (Bt, N, model.m), f32, "u_nom")
     _req(K, (Bt, N, m, n), f32, "K"); _req(k, (Bt, N, m), f32, "k"); _req(cost, (Bt,), torch.float64, "cost")
     _req(alpha_idx, (Bt,), i32, "alpha_idx"); _req(active, (Bt,), i32, "active"); _req(iters, (Bt,), i32, "iters")
     _req(traj_x, (Bt, n_steps + 1, n), f32, "traj_x"); _req(traj_u, (Bt, n_steps, m), f32, "traj_u")
-    _req(traj_iters, (Bt, n_steps), i32, "traj_iters")
+    _req(traj_iters, (Bt, n_steps // hold), i32, "traj_iters")
     if status is not None:
         _req(status, (Bt,), i32, "status")
     if disturbance is not None:
         _req(disturbance, (n_steps, Bt, n), f32, "disturbance")
     arr, na = _alphas(alphas)
     p = model.c_params()
-    check(_lib.load_for(model).quattro_mpc_run_f32(ctypes.byref(p), _ptr(x_cur), _ptr(x_nom), _ptr(u_nom), Bt, N, float(reg), arr, na,
-                                          float(tol), int(max_iter), int(n_steps), _ptr(traj_x), _ptr(traj_u),
-                                          _ptr(traj_iters), _ptr(disturbance), _ptr(K), _ptr(k), _ptr(cost), _ptr(alpha_idx),
-                                          _ptr(active), _ptr(iters), _ptr(status), _ptr(workspace),
-                                          workspace.numel() * workspace.element_size(), _stream()), "quattro_mpc_run_f32")
+    head = (ctypes.byref(p), _ptr(x_cur), _ptr(x_nom), _ptr(u_nom), Bt, N, float(reg), arr, na, float(tol), int(max_iter),
+            int(n_steps), _ptr(traj_x), _ptr(traj_u), _ptr(traj_iters), _ptr(disturbance), _ptr(K), _ptr(k), _ptr(cost),
+            _ptr(alpha_idx), _ptr(active), _ptr(iters), _ptr(status), _ptr(workspace), workspace.numel() * workspace.element_size())
+    if plain:
+        check(_lib.load_for(model).quattro_mpc_run_f32(*head, _stream()), "quattro_mpc_run_f32")
+        return
+    pref, keep, pphys = _plant_args(model, plant, plant_phys, Bt, u_nom.device)
+    check(_lib.load_for(model).quattro_mpc_run_plant_f32(*head, pref, _ptr(pphys), hold, int(bool(feedback)), _stream()),
+          "quattro_mpc_run_plant_f32")

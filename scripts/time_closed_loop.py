@@ -1,0 +1,119 @@
+"""Timing of the closed loop: the default forms (regression check against another build of the library) and the plant /
+gain-feedback forms (recorded, no target).  Quadrotor, B = 4096, N = 50, host clock around work that ends in a synchronise.
+
+  time_closed_loop.py                                   one process, the shipped library: every figure below, one JSON line
+  time_closed_loop.py --ab OLD.so [--rounds 5]          regression check on ONE box: alternates OLD.so (e.g. the parent commit's
+                                                        build, under build_ab/) and the shipped library, `rounds` child processes
+                                                        each (the QUATTRO_HIP_LIB mechanism of scripts/ab_lib.sh), default forms
+                                                        only, and prints both medians and the older build's own spread
+
+Default forms: BatchedMPC.run of 10 control steps (the README's 5.4 ms) and a converged QuattroILQR.solve (its 2.4 ms).
+New forms: 50 plant steps with replan_every = 1 and with replan_every = 5 + feedback + per-controller plants; ops.track of 5 steps.
+"""
+import argparse
+import ctypes
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "quattro-transformer-ilqr_amd")]
+
+
+def measure(defaults_only):
+    import numpy as np
+    import torch
+    from quattro_ilqr_amd import _lib
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    new_abi = hasattr(raw, "quattro_mpc_run_plant_f32")
+    if not new_abi:           # an older build of the library: bind what it has (the default forms need nothing newer)
+        for name in ("quattro_track_f32", "quattro_mpc_run_plant_f32"):
+            _lib.SIGNATURES.pop(name, None)
+    from quattro_ilqr_amd import BatchedMPC, QuattroILQR, ops, quadrotor_model
+    import bench
+    dev, B, N = "cuda:0", 4096, 50
+    md = quadrotor_model(dt=0.01, integrator="euler")
+    x0h, _ = bench.synthetic_batch(B, 0)
+    x0 = torch.as_tensor(x0h, dtype=torch.float32, device=dev)
+
+    def timed(fn, reps=7):
+        fn(); fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append(1e3 * (time.perf_counter() - t0))
+        return float(np.median(ts))
+
+    out = {"lib": os.path.basename(_lib.LIB_PATH), "new_abi": new_abi}
+    mpc = BatchedMPC(md, N, max_iter=100, tol=1e-3, device=dev)
+
+    def run(steps, **kw):
+        mpc.u_warm = None
+        return mpc.run(x0, steps, **kw)
+
+    sv = QuattroILQR(md, N, max_iter=100, tol=1e-3, device=dev)
+    for _ in range(10):
+        sv.solve(x0, max_iter=20, fixed_iters=True)                  # clocks
+    out["solve_default_ms"] = timed(lambda: sv.solve(x0, max_iter=100))
+    out["mpc_run_default_10_steps_ms"] = timed(lambda: run(10))
+    if not defaults_only and new_abi:
+        phys = np.tile(np.asarray(md.phys, dtype=np.float32), (B, 1))
+        phys[:, 0] *= 1.0 + 0.2 * np.sin(1.0 + np.arange(B))
+        phys[:, 1] *= 1.0 + 0.2 * np.cos(np.arange(B))
+        phys_t = ops.plant_phys_tensor(md, phys, B, dev)
+        plant = md.with_(integrator="rk4")
+        out["mpc_run_default_50_steps_ms"] = timed(lambda: run(50), reps=5)
+        out["mpc_run_plant_50_steps_replan_1_ms"] = timed(lambda: run(50, plant=plant, plant_phys=phys), reps=5)
+        out["mpc_run_plant_50_steps_replan_5_feedback_ms"] = timed(
+            lambda: run(50, plant=plant, plant_phys=phys, replan_every=5, feedback=True), reps=5)
+        out["mpc_run_plant_50_steps_replan_5_open_loop_ms"] = timed(
+            lambda: run(50, plant=plant, plant_phys=phys, replan_every=5, feedback=False), reps=5)
+        r = sv.solve(x0, max_iter=3, fixed_iters=True)
+        xn, un, K = r["x"].clone(), r["u"].clone(), r["K"].clone()
+        xs = xn[:, 0].contiguous()
+        out["track_5_steps_ms"] = timed(lambda: ops.track(md, xs, xn, un, K, 5, plant=plant, plant_phys=phys_t), reps=21)
+        out["track_50_steps_ms"] = timed(lambda: ops.track(md, xs, xn, un, K, 50, plant=plant, plant_phys=phys_t), reps=21)
+    print(json.dumps(out), flush=True)
+
+
+def ab(old, rounds):
+    import numpy as np
+    res = {"old": [], "new": []}
+    for r in range(rounds):
+        for tag in ("old", "new"):
+            env = dict(os.environ)
+            if tag == "old":
+                env["QUATTRO_HIP_LIB"] = os.path.realpath(old)
+            else:
+                env.pop("QUATTRO_HIP_LIB", None)
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--defaults-only"], env=env, capture_output=True,
+                               text=True, timeout=280)
+            if p.returncode != 0:
+                sys.exit(f"child ({tag}, round {r}) failed with status {p.returncode}:\n{p.stderr[-2000:]}")
+            d = json.loads(p.stdout.strip().splitlines()[-1])
+            res[tag].append(d)
+            print(f"round {r} {tag}: solve {d['solve_default_ms']:.3f} ms, run(10) {d['mpc_run_default_10_steps_ms']:.3f} ms", flush=True)
+    summary = {}
+    for key in ("solve_default_ms", "mpc_run_default_10_steps_ms"):
+        o, n = np.array([d[key] for d in res["old"]]), np.array([d[key] for d in res["new"]])
+        summary[key] = {"old_median": float(np.median(o)), "old_min": float(o.min()), "old_max": float(o.max()),
+                        "new_median": float(np.median(n)), "new_min": float(n.min()), "new_max": float(n.max()),
+                        "new_median_within_old_spread": bool(o.min() <= np.median(n) <= o.max())}
+    print(json.dumps(summary), flush=True)
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--ab", metavar="OLD.so")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--defaults-only", action="store_true")
+    a = ap.parse_args()
+    if a.ab:
+        ab(a.ab, a.rounds)
+    else:
+        measure(a.defaults_only)
