@@ -164,14 +164,14 @@ def softplus_beta(z, beta):
 
 
 def running_cost(spec, x, u):
-    """cartpole_mpc.py:255-256 / quadrotor_mpc.py:86-93."""
+    """cartpole_mpc.py:255-256 / quadrotor_mpc.py:86-93.  The barrier goes with barrier_alpha != 0 for either model, as in
+    include/quattro_hip.h and oracle/linearize.stage_cost (the reference's cart-pole has none: barrier_alpha = 0)."""
     dx = x - spec.x_ref
-    if spec.model_id == MODEL_CARTPOLE:
-        return float(dx @ spec.Q @ dx + u @ spec.R @ u)
     c = dx @ spec.Q @ dx + u @ spec.R @ u
-    barrier = np.sum(softplus_beta(-u, spec.barrier_beta) ** 2)
-    c += spec.barrier_alpha * barrier
-    return c
+    if spec.barrier_alpha != 0.0:
+        barrier = np.sum(softplus_beta(-u, spec.barrier_beta) ** 2)
+        c += spec.barrier_alpha * barrier
+    return float(c) if spec.model_id == MODEL_CARTPOLE else c
 
 
 def final_cost(spec, x):

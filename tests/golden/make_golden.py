@@ -36,8 +36,13 @@ Fixture families:
                                    the reference's np.linalg.inv pivots — Euler and RK4, four starts that are indefinite at
                                    every step or at some
 
+  G16    dyn_cost_params_<model>.npz  G1/G2 away from the defaults: the reference's MPC objects with Q, R, Qf, x_ref, dt (quadrotor:
+                                   alpha, beta too) set to the `skew` set of tests/param_cases.py and their dynamics object
+                                   re-instantiated with that set's physical parameters.  The reference's k_yaw is a constant
+                                   inside its rate function: it stays 0.01 here, and the fixture stores the parameters it used
+
 `--only dataset` regenerates G10 alone, `--only lqr` G11, `--only user_planar` G13, `--only mpc_objects` G14,
-`--only user_slack` G15.
+`--only user_slack` G15, `--only dyn_cost_params` G16.
 """
 import os
 import sys
@@ -109,6 +114,43 @@ def gen_dyn_cost(model):
         Lv[i] = mpc_e.running_cost(x, u)
         Lfv[i] = mpc_e.final_cost(x)
     save(f"dyn_cost_{model}.npz", x=X, u=U, f_euler=fe, f_rk4=fr, L=Lv, Lf=Lfv, dt=0.01)
+
+
+# ------------------------------------------------------------------ G16
+def gen_dyn_cost_params(model):
+    sys.path[:0] = [os.path.dirname(OUT), os.path.dirname(os.path.dirname(OUT))]
+    import param_cases as pc
+    p = pc.params(model, "skew")
+    phys = dict(p["phys"])
+    if model == "quadrotor":
+        phys["k_yaw"] = 0.01                       # quadrotor_dynamics.py:144: not a parameter of the reference
+    rng = np.random.default_rng(16)
+    n, m = pc.DIMS[model]
+    mpcs = {}
+    for method in ("euler", "rk4"):
+        mpc = make_mpc(model, 30, method)
+        mpc.Q, mpc.R, mpc.Qf = np.diag(p["q"]), np.diag(p["r"]), np.diag(p["qf"])
+        mpc.x_ref, mpc.dt = np.array(p["x_ref"]), p["dt"]
+        if model == "quadrotor":
+            mpc.alpha, mpc.beta = p["barrier_alpha"], p["barrier_beta"]
+            mpc.dynamics = type(mpc.dynamics)(mass=phys["mass"], Ix=phys["Ix"], Iy=phys["Iy"], Iz=phys["Iz"], arm=phys["arm"],
+                                              gravity=phys["gravity"])
+        else:
+            mpc.dynamics = type(mpc.dynamics)(m_cart=phys["m_cart"], m_pole=phys["m_pole"], length=phys["length"],
+                                              gravity=phys["gravity"])
+        mpcs[method] = mpc
+    P = 64
+    spread = pc.QUAD_SPREAD if model == "quadrotor" else pc.CART_SPREAD
+    hover = phys["mass"] * phys["gravity"] / 4.0 if model == "quadrotor" else 0.0
+    X = mpcs["euler"].x_ref + spread * rng.normal(size=(P, n))
+    U = hover + 2.0 * rng.normal(size=(P, m))      # a good share of the quadrotor's controls negative: barrier terms live
+    fe = np.array([mpcs["euler"].discrete_dynamics(x.copy(), u.copy()) for x, u in zip(X, U)])
+    fr = np.array([mpcs["rk4"].discrete_dynamics(x.copy(), u.copy()) for x, u in zip(X, U)])
+    Lv = np.array([float(mpcs["euler"].running_cost(x.copy(), u.copy())) for x, u in zip(X, U)])
+    Lfv = np.array([float(mpcs["euler"].final_cost(x.copy())) for x in X])
+    save(f"dyn_cost_params_{model}.npz", x=X, u=U, f_euler=fe, f_rk4=fr, L=Lv, Lf=Lfv, dt=p["dt"],
+         phys=np.array([phys[k] for k in pc.PHYS_NAMES[model]]), x_ref=np.array(p["x_ref"]), q=np.array(p["q"]),
+         r=np.array(p["r"]), qf=np.array(p["qf"]), barrier_alpha=p["barrier_alpha"], barrier_beta=p["barrier_beta"])
 
 
 # ------------------------------------------------------------------ G3/G4
@@ -586,6 +628,9 @@ if __name__ == "__main__":
     if sys.argv[1:] == ["--only", "hybrid_cartpole"]:
         gen_hybrid("cartpole", max_iter=6)
         sys.exit(0)
+    if sys.argv[1:] == ["--only", "dyn_cost_params"]:
+        gen_dyn_cost_params("quadrotor"); gen_dyn_cost_params("cartpole")
+        sys.exit(0)
     if sys.argv[1:] == ["--only", "dataset"]:
         gen_dataset("cartpole", 30, 3, 5, 5); gen_dataset("quadrotor", 50, 2, 3, 1)
         sys.exit(0)
@@ -609,3 +654,4 @@ if __name__ == "__main__":
     gen_user_planar()
     gen_mpc_objects("quadrotor"); gen_mpc_objects("cartpole")
     gen_user_slack()
+    gen_dyn_cost_params("quadrotor"); gen_dyn_cost_params("cartpole")
