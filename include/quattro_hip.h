@@ -385,6 +385,37 @@ int quattro_mpc_run_plant_f32(const quattro_model_params* p, float* x_cur, float
                               size_t workspace_bytes, const quattro_model_params* plant, const float* plant_phys, int hold,
                               int feedback, void* stream);
 
+/* PER-TRAJECTORY MODEL PARAMETERS.  A batch otherwise shares one quattro_model_params, so its trajectories can differ in x0 and
+ * warm start only.  model_phys [B][8] (device, fp32) lifts that for the physical parameters: row b replaces p->phys for trajectory
+ * (controller) b wherever the controller's model is evaluated — nominal rollout, linearisation, terminal pair, sweep, line-search
+ * rollouts and, in the closed loop, the default plant.  For a user-compiled model the row holds its eight free parameters
+ * P[0..7].  p->phys is ignored; every other field of p (dt, integrator, cost, barrier) stays shared.  Rows are used as given,
+ * with no host validation of their values: a non-physical row shows up as QUATTRO_TRAJ_NONFINITE / QUATTRO_TRAJ_SINGULAR for that
+ * trajectory alone.  Results are those of B separate calls with B = 1 and p->phys = row b, bit for bit.
+ *
+ * quattro_ilqr_solve_phys_f32: the arguments of quattro_ilqr_solve_logged_f32 in their order (the log ring works as there), then
+ * model_phys.  quattro_mpc_run_phys_f32: the arguments of quattro_mpc_run_plant_f32 in their order up to `feedback`, then
+ * model_phys; the plant of controller b is plant_phys[b] if that array is given, else plant->phys if a plant is given, else
+ * model_phys[b] (the default plant is the controller's own model); its integrator is the plant's, else p's.
+ *   model_phys == NULL : exactly the entry each extends (the same call, the same kernels, the same results).
+ *   model_phys != NULL : always the model's persistent kernel (csrc/solve_*.hip, their PHYS instantiations), whether or not that
+ *                        is the model's fastest form.  Before any launch: QUATTRO_ERR_UNSUPPORTED for a model without one
+ *                        (quattro_model_has_device_loop(p) == 0), QUATTRO_ERR_BAD_ARG for QUATTRO_SOLVE_ENQUEUE together with
+ *                        model_phys; every other argument is checked as by the entry each extends.
+ * The stand-alone entries (quattro_simulate_f32, quattro_linearize*_f32, quattro_rollout_f32, quattro_linesearch_f32,
+ * quattro_ilqr_iterate_f32, quattro_track_f32) and the other fields of p (cost, dt, integrator) have no per-trajectory form. */
+int quattro_ilqr_solve_phys_f32(const quattro_model_params* p, const float* x0, float* x_nom, float* u_nom, int B, int N,
+                                float reg, const float* alphas, int n_alpha, double tol, int max_iter, int flags, float* K,
+                                float* k, double* cost, int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status,
+                                void* workspace, size_t workspace_bytes, const quattro_solve_log* log, const float* model_phys,
+                                void* stream);
+int quattro_mpc_run_phys_f32(const quattro_model_params* p, float* x_cur, float* x_nom, float* u_nom, int B, int N, float reg,
+                             const float* alphas, int n_alpha, double tol, int max_iter, int n_steps, float* traj_x,
+                             float* traj_u, int32_t* traj_iters, const float* disturbance, float* K, float* k, double* cost,
+                             int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status, void* workspace,
+                             size_t workspace_bytes, const quattro_model_params* plant, const float* plant_phys, int hold,
+                             int feedback, const float* model_phys, void* stream);
+
 /* Transformer gain predictor: weights of the reference's TransformerPredictor (quattro_ilqr_tf/transformer_model.py:85-138)
  * as DEVICE pointers, plus the DataNormalizer vectors (:15-50).  Matrices are PyTorch Linear layout [out][in];
  * the `w_*` matrices are 16-bit (raw uint16 bit patterns: bf16, or IEEE half when `precision` says so), everything else

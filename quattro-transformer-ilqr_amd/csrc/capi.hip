@@ -497,6 +497,29 @@ int quattro_ilqr_solve_logged_f32(const quattro_model_params* p, const float* x0
   return QUATTRO_OK;
 }
 
+int quattro_ilqr_solve_phys_f32(const quattro_model_params* p, const float* x0, float* x_nom, float* u_nom, int B, int N,
+                                float reg, const float* alphas, int n_alpha, double tol, int max_iter, int flags, float* K,
+                                float* k, double* cost, int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status,
+                                void* workspace, size_t workspace_bytes, const quattro_solve_log* log, const float* model_phys,
+                                void* stream) {
+  if (model_phys == nullptr)
+    return quattro_ilqr_solve_logged_f32(p, x0, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, flags, K, k, cost,
+                                         alpha_idx, active, iters, status, workspace, workspace_bytes, log, stream);
+  // the logged entry's checks in its order, then the two refusals of this one: the rows are read by the persistent kernels alone
+  const bool args_ok = iters && max_iter >= 0 && !((flags & QUATTRO_SOLVE_SIMULATE) && !x0) && log_ok(log);
+  int entry_rc = QUATTRO_ERR_BAD_ARG;
+  if (args_ok && !(flags & QUATTRO_SOLVE_ENQUEUE)) entry_rc = quattro_model_has_device_loop(p) ? QUATTRO_OK : QUATTRO_ERR_UNSUPPORTED;
+  WorkspacePlan w;
+  const int rc = check_solve_args(p, x_nom, u_nom, B, N, alphas, n_alpha, K, k, cost, alpha_idx, active, entry_rc, workspace,
+                                  workspace_bytes, &w);
+  if (rc != QUATTRO_OK) return rc;
+  if (log != nullptr && log->records == nullptr) log = nullptr;
+  SolveLoop loop = solve_loop(*p, x0, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, flags, K, k, cost, alpha_idx, active,
+                              iters, status, log);
+  loop.model_phys = model_phys;
+  return launch_device_loop(*p, loop, w, (char*)workspace, (hipStream_t)stream);
+}
+
 int quattro_ilqr_solve_f32(const quattro_model_params* p, const float* x0, float* x_nom, float* u_nom, int B, int N,
                            float reg, const float* alphas, int n_alpha, double tol, int max_iter, int flags, float* K,
                            float* k, double* cost, int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status,
@@ -528,12 +551,13 @@ int quattro_mpc_run_f32(const quattro_model_params* p, float* x_cur, float* x_no
   return launch_device_loop(*p, loop, w, (char*)workspace, (hipStream_t)stream);
 }
 
-int quattro_mpc_run_plant_f32(const quattro_model_params* p, float* x_cur, float* x_nom, float* u_nom, int B, int N, float reg,
-                              const float* alphas, int n_alpha, double tol, int max_iter, int n_steps, float* traj_x,
-                              float* traj_u, int32_t* traj_iters, const float* disturbance, float* K, float* k, double* cost,
-                              int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status, void* workspace,
-                              size_t workspace_bytes, const quattro_model_params* plant, const float* plant_phys, int hold,
-                              int feedback, void* stream) {
+// quattro_mpc_run_plant_f32 (model_phys == NULL: the run as it always was) and quattro_mpc_run_phys_f32
+static int mpc_run_plant(const quattro_model_params* p, float* x_cur, float* x_nom, float* u_nom, int B, int N, float reg,
+                         const float* alphas, int n_alpha, double tol, int max_iter, int n_steps, float* traj_x, float* traj_u,
+                         int32_t* traj_iters, const float* disturbance, float* K, float* k, double* cost, int32_t* alpha_idx,
+                         int32_t* active, int32_t* iters, int32_t* status, void* workspace, size_t workspace_bytes,
+                         const quattro_model_params* plant, const float* plant_phys, int hold, int feedback,
+                         const float* model_phys, void* stream) {
   const bool args_ok = x_cur && iters && traj_x && traj_u && traj_iters && max_iter >= 0 && n_steps > 0 && hold >= 1 && hold <= N &&
                        n_steps % hold == 0 && !(feedback && max_iter < 1);
   PlantSpec ps{};
@@ -558,7 +582,37 @@ int quattro_mpc_run_plant_f32(const quattro_model_params* p, float* x_cur, float
   loop.plant_phys = plant_phys;
   loop.hold = hold;
   loop.feedback = feedback ? 1 : 0;
+  loop.model_phys = model_phys;
+  // the default plant is the controller's own model: with a model of its own per controller, that controller's row (the plant's
+  // integrator is p's then: plant_spec)
+  if (model_phys != nullptr && plant == nullptr && plant_phys == nullptr) loop.plant_phys = model_phys;
   return launch_device_loop(*p, loop, w, (char*)workspace, (hipStream_t)stream);
+}
+
+int quattro_mpc_run_plant_f32(const quattro_model_params* p, float* x_cur, float* x_nom, float* u_nom, int B, int N, float reg,
+                              const float* alphas, int n_alpha, double tol, int max_iter, int n_steps, float* traj_x,
+                              float* traj_u, int32_t* traj_iters, const float* disturbance, float* K, float* k, double* cost,
+                              int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status, void* workspace,
+                              size_t workspace_bytes, const quattro_model_params* plant, const float* plant_phys, int hold,
+                              int feedback, void* stream) {
+  return mpc_run_plant(p, x_cur, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, n_steps, traj_x, traj_u, traj_iters,
+                       disturbance, K, k, cost, alpha_idx, active, iters, status, workspace, workspace_bytes, plant, plant_phys, hold,
+                       feedback, nullptr, stream);
+}
+
+int quattro_mpc_run_phys_f32(const quattro_model_params* p, float* x_cur, float* x_nom, float* u_nom, int B, int N, float reg,
+                             const float* alphas, int n_alpha, double tol, int max_iter, int n_steps, float* traj_x,
+                             float* traj_u, int32_t* traj_iters, const float* disturbance, float* K, float* k, double* cost,
+                             int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status, void* workspace,
+                             size_t workspace_bytes, const quattro_model_params* plant, const float* plant_phys, int hold,
+                             int feedback, const float* model_phys, void* stream) {
+  if (model_phys == nullptr)
+    return quattro_mpc_run_plant_f32(p, x_cur, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, n_steps, traj_x, traj_u,
+                                     traj_iters, disturbance, K, k, cost, alpha_idx, active, iters, status, workspace,
+                                     workspace_bytes, plant, plant_phys, hold, feedback, stream);
+  return mpc_run_plant(p, x_cur, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, n_steps, traj_x, traj_u, traj_iters,
+                       disturbance, K, k, cost, alpha_idx, active, iters, status, workspace, workspace_bytes, plant, plant_phys, hold,
+                       feedback, model_phys, stream);
 }
 
 int quattro_track_f32(const quattro_model_params* p, const quattro_model_params* plant, const float* plant_phys, const float* x0,

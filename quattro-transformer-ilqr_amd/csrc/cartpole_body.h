@@ -118,12 +118,16 @@ struct LaneRec {
 // be swept — idle rows run along on trajectory 0 without storing, so that every row of the wave stays on one path),
 // `stage` = this row's LDS stage (cp16::STAGE_FLOATS floats, 16-byte aligned).  Steps t_start .. N-1; outputs indexed
 // t - t_start.  status may be NULL.
-template <bool RK4>
+// OWN (the persistent loop with per-trajectory parameters): p is this row's private block — the kernel's with the row's phys — and
+// `shared` the kernel-argument block it was copied from.  The one lane-indexed read of the sweep (the terminal weight qf[i]) goes
+// to `shared`, whose cost fields are the same: a private block indexed by lane is kept whole in scratch memory (292 B per lane).
+template <bool RK4, bool OWN = false>
 __device__ __forceinline__ void sweep16_cartpole_body(const quattro_model_params& p, const float* __restrict__ x,
                                                       const float* __restrict__ u, int N, int t_start, float reg,
                                                       float* __restrict__ Kout, float* __restrict__ kout,
                                                       int32_t* __restrict__ status, const int b, const bool live,
-                                                      const int lane, float* stage, const int k_rows = 0) {
+                                                      const int lane, float* stage, const int k_rows = 0,
+                                                      const quattro_model_params* shared = nullptr) {
   using namespace cp16;
   constexpr int NX = 4;
   const int sub = lane & 15, i = sub >> 2, j = sub & 3, row0 = lane & 48;
@@ -144,7 +148,8 @@ __device__ __forceinline__ void sweep16_cartpole_body(const quattro_model_params
     const float xn[NX] = {xN.x, xN.y, xN.z, xN.w};
 #pragma unroll
     for (int c = 0; c < NX; ++c) vx[c] = qt_terminal_vx(p, c, xn[c]);
-    Vij = (i == j) ? qt_terminal_vxx(p, i) : 0.0f;
+    if constexpr (OWN) Vij = (i == j) ? qt_terminal_vxx(*shared, i) : 0.0f;
+    else Vij = (i == j) ? qt_terminal_vxx(p, i) : 0.0f;
   }
   bool bad = false, singular = false;
 

@@ -324,8 +324,11 @@ struct EulerRecord<QUATTRO_MODEL_CARTPOLE, L> {
 
 template <class L>
 struct EulerRecord<QUATTRO_MODEL_QUADROTOR, L> {
-  static __device__ __forceinline__ void fill_const(float* rec, const quattro_model_params& p) {
-    const float Ix = p.phys[1], Iy = p.phys[2], Iz = p.phys[3], arm = p.phys[4], kyaw = p.phys[6];
+  // (`ph`: the seven physical parameters as this trajectory has them -- p.phys, or a row of per-trajectory values the caller holds
+  //  as VALUES (solve_loop.h: model_phys); the two-argument forms below are the shared-parameter case)
+  static __device__ __forceinline__ void fill_const(float* rec, const quattro_model_params& p) { fill_const(rec, p, p.phys); }
+  static __device__ __forceinline__ void fill_const(float* rec, const quattro_model_params& p, const float* ph) {
+    const float Ix = ph[1], Iy = ph[2], Iz = ph[3], arm = ph[4], kyaw = ph[6];
     const float dt = p.dt;
     for (int i = 0; i < 12; ++i) {
       rec[L::a(i, i)] = 1.0f;
@@ -355,8 +358,12 @@ struct EulerRecord<QUATTRO_MODEL_QUADROTOR, L> {
   // TILE16C, ROWMAJOR) in different kernels, and they must come out bit-identical (explicit fmaf calls stay fused).
   static __device__ __forceinline__ void fill_dynamics(float* rec, const quattro_model_params& p, const QuadTrig& t,
                                                        const float* x, const float* u) {
+    fill_dynamics(rec, p, p.phys, t, x, u);
+  }
+  static __device__ __forceinline__ void fill_dynamics(float* rec, const quattro_model_params& p, const float* ph,
+                                                       const QuadTrig& t, const float* x, const float* u) {
 #pragma clang fp contract(off)
-    const float mass = p.phys[0], Ix = p.phys[1], Iy = p.phys[2], Iz = p.phys[3];
+    const float mass = ph[0], Ix = ph[1], Iy = ph[2], Iz = ph[3];
     const float dt = p.dt;
     const float wp = x[9], wq = x[10], wr = x[11];
     const float tm = (u[0] + u[1] + u[2] + u[3]) / mass;
@@ -442,13 +449,13 @@ struct QuadStage {
   QuadTrig t;
   float wp, wq, wr, tm, rx, ry, rz, mix, dmix, sec2;
 };
-__device__ __forceinline__ QuadStage quad_stage(const quattro_model_params& p, const float* x, const float* u) {
+__device__ __forceinline__ QuadStage quad_stage(const float* ph, const float* x, const float* u) {
   QuadStage s;
   s.t = quad_trig(x[6], x[7], x[8]);
   s.wp = x[9];
   s.wq = x[10];
   s.wr = x[11];
-  s.tm = (u[0] + u[1] + u[2] + u[3]) / p.phys[0];
+  s.tm = (u[0] + u[1] + u[2] + u[3]) / ph[0];
   s.rx = s.t.sps * s.t.sph + s.t.cps * s.t.sth * s.t.cph;
   s.ry = s.t.cps * s.t.sph - s.t.sps * s.t.sth * s.t.cph;
   s.rz = s.t.cth * s.t.cph;
@@ -457,11 +464,13 @@ __device__ __forceinline__ QuadStage quad_stage(const quattro_model_params& p, c
   s.sec2 = s.t.sec * s.t.sec;
   return s;
 }
+__device__ __forceinline__ QuadStage quad_stage(const quattro_model_params& p, const float* x, const float* u) {
+  return quad_stage(p.phys, x, u);
+}
 // xd = rate(x, u) at the stage point.  NOT qt_rate<QUADROTOR>'s bits: that one multiplies by reciprocals hoisted out of the rollout
 // loop (* inv_mass, tau * inv_Ix), this one divides (/ mass, (arm / Ix) *); merging them would move rollouts or records in the last bit.
-__device__ __forceinline__ void quad_rate_at(const QuadStage& s, const quattro_model_params& p, const float* x,
-                                             const float* u, float* xd) {
-  const float Ix = p.phys[1], Iy = p.phys[2], Iz = p.phys[3], arm = p.phys[4], grav = p.phys[5], kyaw = p.phys[6];
+__device__ __forceinline__ void quad_rate_at(const QuadStage& s, const float* ph, const float* x, const float* u, float* xd) {
+  const float Ix = ph[1], Iy = ph[2], Iz = ph[3], arm = ph[4], grav = ph[5], kyaw = ph[6];
   xd[0] = x[3];
   xd[1] = x[4];
   xd[2] = x[5];
@@ -474,6 +483,10 @@ __device__ __forceinline__ void quad_rate_at(const QuadStage& s, const quattro_m
   xd[9] = ((Iy - Iz) / Ix) * (s.wq * s.wr) + (arm / Ix) * ((u[1] + u[2]) - (u[0] + u[3]));
   xd[10] = ((Iz - Ix) / Iy) * (s.wp * s.wr) + (arm / Iy) * ((u[0] + u[1]) - (u[2] + u[3]));
   xd[11] = ((Ix - Iy) / Iz) * (s.wp * s.wq) + (kyaw / Iz) * (u[0] - u[1] + u[2] - u[3]);
+}
+__device__ __forceinline__ void quad_rate_at(const QuadStage& s, const quattro_model_params& p, const float* x,
+                                             const float* u, float* xd) {
+  quad_rate_at(s, p.phys, x, u, xd);
 }
 // out = (d rate / d x) dx + (d rate / d u) du at the stage point
 __device__ __forceinline__ void quad_jvp_at(const QuadStage& s, const quattro_model_params& p, const float* dx,
@@ -506,27 +519,33 @@ __device__ __forceinline__ void qt_rate_jvp<QUATTRO_MODEL_QUADROTOR>(const quatt
 // The four RK4 stage points of one quadrotor step (rk4.h's value chain with quad_rate_at as the rate function): visit(s, stage)
 // runs as soon as point s = 0..3 is known, before the next one is computed, so a caller that only needs a stage's coefficients
 // (rk4_step_coefs) can emit them and let the stage die.  Shared by linearize_rk4_quad_kernel and the fused RK4 sweep.
+// (`ph`: the physical parameters of this trajectory, see EulerRecord<QUADROTOR>::fill_const)
 template <class Visit>
-__device__ __forceinline__ void quad_rk4_stages(const quattro_model_params& p, const float* xs, const float* us, Visit visit) {
+__device__ __forceinline__ void quad_rk4_stages(const quattro_model_params& p, const float* ph, const float* xs, const float* us,
+                                                Visit visit) {
   constexpr int NX = 12;
   const float dt = p.dt;
   float k[NX], xst[NX];
-  const QuadStage s1 = quad_stage(p, xs, us);
+  const QuadStage s1 = quad_stage(ph, xs, us);
   visit(0, s1);
-  quad_rate_at(s1, p, xs, us, k);
+  quad_rate_at(s1, ph, xs, us, k);
 #pragma unroll
   for (int i = 0; i < NX; ++i) xst[i] = fmaf(0.5f * dt, k[i], xs[i]);
-  const QuadStage s2 = quad_stage(p, xst, us);
+  const QuadStage s2 = quad_stage(ph, xst, us);
   visit(1, s2);
-  quad_rate_at(s2, p, xst, us, k);
+  quad_rate_at(s2, ph, xst, us, k);
 #pragma unroll
   for (int i = 0; i < NX; ++i) xst[i] = fmaf(0.5f * dt, k[i], xs[i]);
-  const QuadStage s3 = quad_stage(p, xst, us);
+  const QuadStage s3 = quad_stage(ph, xst, us);
   visit(2, s3);
-  quad_rate_at(s3, p, xst, us, k);
+  quad_rate_at(s3, ph, xst, us, k);
 #pragma unroll
   for (int i = 0; i < NX; ++i) xst[i] = fmaf(dt, k[i], xs[i]);
-  visit(3, quad_stage(p, xst, us));
+  visit(3, quad_stage(ph, xst, us));
+}
+template <class Visit>
+__device__ __forceinline__ void quad_rk4_stages(const quattro_model_params& p, const float* xs, const float* us, Visit visit) {
+  quad_rk4_stages(p, p.phys, xs, us, visit);
 }
 
 // cost derivative entries of a record (independent of the integrator): l_x, l_u, diag(l_xx), diag(l_uu); l_ux = 0

@@ -93,6 +93,35 @@ __device__ __forceinline__ LaneConst lane_const_plant(const PlantSpec& plant, co
   return L;
 }
 
+// The lane constants of a trajectory with parameters of its own (quattro_ilqr_solve_phys_f32, quattro_mpc_run_phys_f32): the cost
+// weights and dt are p's, as lane_const selects them; the rate-function constants come from row bb of model_phys [B][8], read as
+// values -- the quads of a wave work on different trajectories, so these are vector loads.  lane_const's formulas restated on the
+// row, like lane_const_plant's and for its reason: lane_const itself, and with it every kernel that calls it, stays as it is (what it
+// derives from p.phys is dead here and removed).
+__device__ __forceinline__ LaneConst lane_const_phys(const quattro_model_params& p, const float* __restrict__ model_phys, size_t bb,
+                                                     int j) {
+  LaneConst L = lane_const(p, j);
+  float ph[7];
+#pragma unroll
+  for (int i = 0; i < 7; ++i) ph[i] = model_phys[bb * 8 + i];
+  const float mass = ph[0], Ix = ph[1], Iy = ph[2], Iz = ph[3], arm = ph[4], grav = ph[5], kyaw = ph[6];
+  const float s0 = L.sel(-1.0f, 1.0f, 1.0f), s1 = L.sel(1.0f, 1.0f, -1.0f), s2 = L.sel(1.0f, -1.0f, 1.0f),
+              s3 = L.sel(-1.0f, -1.0f, -1.0f);
+  const float gain = L.sel(arm / Ix, arm / Iy, kyaw / Iz);
+  L.tc[0] = s0 * gain; L.tc[1] = s1 * gain; L.tc[2] = s2 * gain; L.tc[3] = s3 * gain;
+  L.gy = L.sel((Iy - Iz) / Ix, (Iz - Ix) / Iy, (Ix - Iy) / Iz);
+  L.gz = L.sel(0.0f, 0.0f, -grav);
+  L.inv_mass = 1.0f / mass;
+  return L;
+}
+
+template <bool PHYS>
+__device__ __forceinline__ LaneConst lane_const_of(const quattro_model_params& p, const float* __restrict__ model_phys, size_t bb,
+                                                   int j) {
+  if constexpr (PHYS) return lane_const_phys(p, model_phys, bb, j);
+  else return lane_const(p, j);
+}
+
 // the four controls of the quad (lane j owns u_j), in every lane: broadcast ONCE per step and shared by the rate
 // function (four calls under RK4) and the store
 struct QuadU {
@@ -413,13 +442,15 @@ __device__ __forceinline__ double quad_rollout_closed(const quattro_model_params
 // simulate: quad per trajectory, 16 trajectories per wave
 // `gid` = 4 * trajectory + lane-in-quad; `live` = this quad has a trajectory to roll out (idle quads run along on
 // trajectory 0 without storing: the DPP exchanges and the wave-uniform barrier shortcut need every quad on the same path)
-template <bool RK4>
+// PHYS: the quad's physical parameters are row b of model_phys (lane_const_phys); the cost stays p's
+template <bool RK4, bool PHYS = false>
 __device__ __forceinline__ void simulate_quad_body(const quattro_model_params& p, const float* __restrict__ x0,
                                                    const float* __restrict__ u, int N, float* __restrict__ x,
-                                                   double* __restrict__ cost, const int gid, const bool live) {
+                                                   double* __restrict__ cost, const int gid, const bool live,
+                                                   const float* __restrict__ model_phys = nullptr) {
   const int b = gid >> 2;
   const size_t bb = live ? b : 0;
-  const LaneConst L = lane_const(p, gid & 3);
+  const LaneConst L = lane_const_of<PHYS>(p, model_phys, bb, gid & 3);
   const float* ub = u + bb * N * NU + L.j;
   float* xo = x + bb * (N + 1) * NX + L.a;
   float xh[4];
@@ -481,13 +512,14 @@ __device__ __forceinline__ void simulate_quad_body(const quattro_model_params& p
 // (x', u') in the scratch; after the ballot the trajectory's 32 lanes copy the accepted candidate over the nominal.
 // `gid` = 32 * trajectory + lane-in-trajectory for this lane (the 64 lanes of a wave hold two consecutive trajectories);
 // `force` treats every trajectory as active whatever its flag says (fixed-iteration benchmarking runs).
-template <bool RK4, int PF, bool PRIO>
+// PHYS: the candidates of trajectory b roll out under row b of model_phys (lane_const_phys); the cost stays p's
+template <bool RK4, int PF, bool PRIO, bool PHYS = false>
 __device__ __forceinline__ void linesearch_quad_body(const quattro_model_params& p, float* x_nom, float* u_nom,
                                                      const float* __restrict__ K, const float* __restrict__ k,
                                                      const AlphaList& al, int n_alpha, int B, int N, double tol,
                                                      double* cost, int32_t* __restrict__ alpha_idx, int32_t* active,
                                                      int32_t* iters, float* __restrict__ scratch, const int gid,
-                                                     const bool force) {
+                                                     const bool force, const float* __restrict__ model_phys = nullptr) {
   const int b = gid >> 5, ai = (gid >> 2) & 7, l32 = gid & 31;
   const bool live = (b < B) && (force || active == nullptr || active[b < B ? b : 0] != 0);
   if (!__any(live)) return;   // both trajectories of the wave converged / out of range: nothing to do (late iterations
@@ -495,7 +527,7 @@ __device__ __forceinline__ void linesearch_quad_body(const quattro_model_params&
   const bool mine = live && ai < n_alpha;
   const size_t bb = live ? b : 0;
   const int aa = mine ? ai : 0;
-  const LaneConst L = lane_const(p, gid & 3);
+  const LaneConst L = lane_const_of<PHYS>(p, model_phys, bb, gid & 3);
   float* xn = x_nom + bb * (N + 1) * NX;
   float* un = u_nom + bb * N * NU;
   const int wb = __builtin_amdgcn_readfirstlane(b);    // the wave's first trajectory (gid grows with the lane; wb < B: a lane is live)

@@ -24,7 +24,9 @@ struct CpSolveArgs {
 
 // PLANT: the loop of quattro_mpc_run_plant_f32 (a plant of its own, c.hold tracked steps per plan); the <RK4, false> code is the
 // loop as it always was
-template <bool RK4, bool PLANT>
+// PHYS (with PLANT only: quattro_ilqr_solve_phys_f32 has n_ctrl == 0 and never reaches the MPC code): every row evaluates its
+// trajectory's model — nominal rollout, records, terminal pair, line search — on a block whose phys is its row of c.model_phys
+template <bool RK4, bool PLANT, bool PHYS>
 __global__ __launch_bounds__(QT_WAVE) void solve_cartpole_kernel(const CpSolveArgs a) {
   constexpr int MODEL = QUATTRO_MODEL_CARTPOLE, NX = 4;
   __shared__ __attribute__((aligned(16))) float s_stage[4 * cp16::STAGE_FLOATS];
@@ -37,10 +39,12 @@ __global__ __launch_bounds__(QT_WAVE) void solve_cartpole_kernel(const CpSolveAr
   const bool force = (c.flags & QUATTRO_SOLVE_FIXED_ITERS) != 0;
   const int N = c.N;
   float* stage = s_stage + (lane >> 4) * cp16::STAGE_FLOATS;
+  quattro_model_params own;
+  const quattro_model_params& mp = trajectory_params<PHYS>(a.p, c, bb, own);
   const int n_ctrl = c.n_ctrl > 0 ? c.n_ctrl : 1;
   for (int cs = 0; cs < n_ctrl; ++cs) {
     wave_step_prologue<NX, PLANT>(c, bb, cs, have && sub == 0,
-                           [&] { simulate_body<MODEL, RK4>(a.p, c.x0, c.u, N, c.x, c.cost, b); });
+                           [&] { simulate_body<MODEL, RK4>(mp, c.x0, c.u, N, c.x, c.cost, b); });
     const bool logging = c.log.rec != nullptr && c.n_ctrl == 0;
     for (int it = 0; it < c.max_iter; ++it) {
       const bool act = have && (force || c.active[bb] != 0);
@@ -50,10 +54,10 @@ __global__ __launch_bounds__(QT_WAVE) void solve_cartpole_kernel(const CpSolveAr
         log_it = c.iters[bb];
         log_begin(c.log, b, log_it, c.x + bb * (N + 1) * NX, c.u + bb * N, c.cost[bb], sub, 16);
       }
-      sweep16_cartpole_body<RK4>(a.p, c.x, c.u, N, 0, c.reg, c.K, c.k, c.status, b, act, lane, stage);
+      sweep16_cartpole_body<RK4, PHYS>(mp, c.x, c.u, N, 0, c.reg, c.K, c.k, c.status, b, act, lane, stage, 0, &a.p);
       if (logging && act && sub == 0) log_stamp(c.log, b, log_it, 1, 2);
       wave_handoff();
-      linesearch_body<MODEL, RK4, 16>(a.p, c.x, c.u, c.K, c.k, c.al, c.n_alpha, c.B, N, c.tol, c.cost, c.alpha_idx, c.active,
+      linesearch_body<MODEL, RK4, 16>(mp, c.x, c.u, c.K, c.k, c.al, c.n_alpha, c.B, N, c.tol, c.cost, c.alpha_idx, c.active,
                                       c.iters, c.scratch, 16 * b + sub, force);
       wave_handoff();
       if (logging && act)        // gains, accepted step, cost after the iteration, end stamp
@@ -63,7 +67,7 @@ __global__ __launch_bounds__(QT_WAVE) void solve_cartpole_kernel(const CpSolveAr
     // simulator's step around it
     if (c.n_ctrl > 0)
       wave_mpc_epilogue<NX, 1, 16, PLANT>(c, bb, cs, sub, have,
-                                          [&](const float* xo, const float* u0, float* xn) { qt_step<MODEL, RK4>(a.p, xo, u0, xn); },
+                                          [&](const float* xo, const float* u0, float* xn) { qt_step<MODEL, RK4>(mp, xo, u0, xn); },
                                           [&](float* xh, const size_t s0) { track_plan<MODEL>(a.p, c, bb, xh, s0); });
   }
 }
@@ -75,12 +79,15 @@ int quattro_launch_solve_cartpole(const quattro_model_params& p, const SolveLoop
   const dim3 grid((unsigned)((c.B + 3) / 4));
   if (p.integrator != QUATTRO_INTEGRATOR_EULER && p.integrator != QUATTRO_INTEGRATOR_RK4) return QUATTRO_ERR_UNSUPPORTED;
   const bool rk4 = p.integrator == QUATTRO_INTEGRATOR_RK4;
-  if (c.hold > 0) {
-    if (rk4) hipLaunchKernelGGL((solve_cartpole_kernel<true, true>), grid, dim3(QT_WAVE), 0, stream, a);
-    else hipLaunchKernelGGL((solve_cartpole_kernel<false, true>), grid, dim3(QT_WAVE), 0, stream, a);
+  if (c.model_phys != nullptr) {      // (the two phys entries alone set it)
+    if (rk4) hipLaunchKernelGGL((solve_cartpole_kernel<true, true, true>), grid, dim3(QT_WAVE), 0, stream, a);
+    else hipLaunchKernelGGL((solve_cartpole_kernel<false, true, true>), grid, dim3(QT_WAVE), 0, stream, a);
+  } else if (c.hold > 0) {
+    if (rk4) hipLaunchKernelGGL((solve_cartpole_kernel<true, true, false>), grid, dim3(QT_WAVE), 0, stream, a);
+    else hipLaunchKernelGGL((solve_cartpole_kernel<false, true, false>), grid, dim3(QT_WAVE), 0, stream, a);
   } else {
-    if (rk4) hipLaunchKernelGGL((solve_cartpole_kernel<true, false>), grid, dim3(QT_WAVE), 0, stream, a);
-    else hipLaunchKernelGGL((solve_cartpole_kernel<false, false>), grid, dim3(QT_WAVE), 0, stream, a);
+    if (rk4) hipLaunchKernelGGL((solve_cartpole_kernel<true, false, false>), grid, dim3(QT_WAVE), 0, stream, a);
+    else hipLaunchKernelGGL((solve_cartpole_kernel<false, false, false>), grid, dim3(QT_WAVE), 0, stream, a);
   }
   return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;
 }

@@ -36,6 +36,9 @@ struct SolveLoop {
   const float* plant_phys;    // [B][8] per-controller physical parameters, or NULL
   int hold, feedback;
   SolveLogDev log;            // per-iteration log ring (rec == nullptr: none); plain solves only (n_ctrl == 0)
+  // per-trajectory model parameters (quattro_ilqr_solve_phys_f32, quattro_mpc_run_phys_f32; the PHYS instantiations of the kernels):
+  // row b replaces the parameter block's phys wherever the controller's model of trajectory b is evaluated.  NULL: none.
+  const float* model_phys;    // [B][8]
 };
 
 namespace {
@@ -45,6 +48,25 @@ template <bool PLANT>
 __device__ __forceinline__ int traj_steps(const SolveLoop& c) {
   if constexpr (PLANT) return c.n_ctrl * c.hold;
   else return c.n_ctrl;
+}
+
+// The parameter block a lane evaluates the model of trajectory bb with.  PHYS: `own`, a copy of the kernel's block whose phys is row
+// bb of c.model_phys, taken as values (the cart-pole's four rows of a wave hold four different sets; a user model's wave one);
+// otherwise the kernel's block itself, and `own` is never touched.
+template <bool PHYS>
+__device__ __forceinline__ const quattro_model_params& trajectory_params(const quattro_model_params& p, const SolveLoop& c,
+                                                                         const size_t bb, quattro_model_params& own) {
+  if constexpr (PHYS) {
+    float ph[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) ph[i] = c.model_phys[bb * 8 + i];
+    own = p;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) own.phys[i] = ph[i];
+    return own;
+  } else {
+    return p;
+  }
 }
 
 // every store of this wave has completed before its lanes read what other lanes of the wave wrote (the phases of a

@@ -46,7 +46,10 @@ struct UserSolveArgs {
 //  one wave per SIMD — and the loop runs 3x slower than with the 42 spilled registers this bound costs)
 // PLANT: the loop of quattro_mpc_run_plant_f32 (a plant of its own, c.hold tracked steps per plan); the <RK4, false> code is the
 // loop as it always was
-template <bool RK4, bool PLANT>
+// PHYS (with PLANT only: quattro_ilqr_solve_phys_f32 has n_ctrl == 0 and never reaches the MPC code): the wave evaluates its
+// trajectory's model — nominal rollout, linearisation, terminal pair, line search — on a block whose phys (the model's free
+// parameters P[0..7]) is its row of c.model_phys
+template <bool RK4, bool PLANT, bool PHYS>
 __global__ __launch_bounds__(QT_WAVE, 2) void solve_user_kernel(const UserSolveArgs a) {
   constexpr int MODEL = QUATTRO_MODEL_USER, NX = QT_USER_NX, NU = QT_USER_NU, NZ = NX + NU;
   constexpr int LPI = NZ <= 8 ? 8 : (NZ <= 16 ? 16 : 32), IPP = QT_WAVE / LPI;      // lanes per item, items per pass
@@ -67,9 +70,11 @@ __global__ __launch_bounds__(QT_WAVE, 2) void solve_user_kernel(const UserSolveA
   float* ub = c.u + bb * N * NU;
   float* recb = a.rec + bb * N * R::STRIDE;
   volatile int32_t* act_flag = c.active + b;     // written by this wave's line search: always re-read from memory
+  quattro_model_params own;
+  const quattro_model_params& mp = trajectory_params<PHYS>(a.p, c, bb, own);
   const int n_ctrl = c.n_ctrl > 0 ? c.n_ctrl : 1;
   for (int cs = 0; cs < n_ctrl; ++cs) {
-    wave_step_prologue<NX, PLANT>(c, bb, cs, lane == 0, [&] { simulate_body<MODEL, RK4>(a.p, c.x0, c.u, N, c.x, c.cost, b); });
+    wave_step_prologue<NX, PLANT>(c, bb, cs, lane == 0, [&] { simulate_body<MODEL, RK4>(mp, c.x0, c.u, N, c.x, c.cost, b); });
     const bool logging = c.log.rec != nullptr && c.n_ctrl == 0;
     for (int it = 0; it < c.max_iter; ++it) {
       if (!(force || *act_flag != 0)) break;       // wave-uniform: one trajectory per wave
@@ -86,9 +91,9 @@ __global__ __launch_bounds__(QT_WAVE, 2) void solve_user_kernel(const UserSolveA
         for (int t0 = 0; t0 < N; t0 += IPP) {
           const int t = t0 + lane / LPI;
           if (t < N && j < NZ)
-            user_linearize_item<R, RK4>(a.p, xb + (size_t)t * NX, ub + (size_t)t * NU, recb + (size_t)t * R::STRIDE, j);
+            user_linearize_item<R, RK4>(mp, xb + (size_t)t * NX, ub + (size_t)t * NU, recb + (size_t)t * R::STRIDE, j);
         }
-        if (lane < NX) user_terminal_row(a.p, xb + (size_t)N * NX, lane, a.VxN + bb * NX, a.VxxN + bb * NX * NX);
+        if (lane < NX) user_terminal_row(mp, xb + (size_t)N * NX, lane, a.VxN + bb * NX, a.VxxN + bb * NX * NX);
       }
       wave_handoff();
       if constexpr (TILE) {
@@ -108,7 +113,7 @@ __global__ __launch_bounds__(QT_WAVE, 2) void solve_user_kernel(const UserSolveA
       }
       if (logging && lane == 0) log_stamp(c.log, b, log_it, 1, 2);
       wave_handoff();
-      linesearch_body<MODEL, RK4, 64>(a.p, c.x, c.u, c.K, c.k, c.al, c.n_alpha, c.B, N, c.tol, c.cost, c.alpha_idx, c.active,
+      linesearch_body<MODEL, RK4, 64>(mp, c.x, c.u, c.K, c.k, c.al, c.n_alpha, c.B, N, c.tol, c.cost, c.alpha_idx, c.active,
                                       c.iters, c.scratch, 64 * b + lane, force);
       wave_handoff();
       if (logging)               // gains, accepted step, cost after the iteration, end stamp
@@ -117,7 +122,7 @@ __global__ __launch_bounds__(QT_WAVE, 2) void solve_user_kernel(const UserSolveA
     }
     if (c.n_ctrl > 0)            // apply u_0 to the plant (the device model itself), record, shift the warm start
       wave_mpc_epilogue<NX, NU, QT_WAVE, PLANT>(c, bb, cs, lane, true,
-                                                [&](const float* xo, const float* u0, float* xn) { qt_step<MODEL, RK4>(a.p, xo, u0, xn); },
+                                                [&](const float* xo, const float* u0, float* xn) { qt_step<MODEL, RK4>(mp, xo, u0, xn); },
                                                 [&](float* xh, const size_t s0) { track_plan<MODEL>(a.p, c, bb, xh, s0); });
   }
 }
@@ -177,12 +182,15 @@ int quattro_launch_solve_user(const quattro_model_params& p, const SolveLoop& c,
   const dim3 grid((unsigned)c.B);
   if (p.integrator != QUATTRO_INTEGRATOR_EULER && p.integrator != QUATTRO_INTEGRATOR_RK4) return QUATTRO_ERR_UNSUPPORTED;
   const bool rk4 = p.integrator == QUATTRO_INTEGRATOR_RK4;
-  if (c.hold > 0) {
-    if (rk4) hipLaunchKernelGGL((solve_user_kernel<true, true>), grid, dim3(QT_WAVE), 0, stream, a);
-    else hipLaunchKernelGGL((solve_user_kernel<false, true>), grid, dim3(QT_WAVE), 0, stream, a);
+  if (c.model_phys != nullptr) {      // (the two phys entries alone set it)
+    if (rk4) hipLaunchKernelGGL((solve_user_kernel<true, true, true>), grid, dim3(QT_WAVE), 0, stream, a);
+    else hipLaunchKernelGGL((solve_user_kernel<false, true, true>), grid, dim3(QT_WAVE), 0, stream, a);
+  } else if (c.hold > 0) {
+    if (rk4) hipLaunchKernelGGL((solve_user_kernel<true, true, false>), grid, dim3(QT_WAVE), 0, stream, a);
+    else hipLaunchKernelGGL((solve_user_kernel<false, true, false>), grid, dim3(QT_WAVE), 0, stream, a);
   } else {
-    if (rk4) hipLaunchKernelGGL((solve_user_kernel<true, false>), grid, dim3(QT_WAVE), 0, stream, a);
-    else hipLaunchKernelGGL((solve_user_kernel<false, false>), grid, dim3(QT_WAVE), 0, stream, a);
+    if (rk4) hipLaunchKernelGGL((solve_user_kernel<true, false, false>), grid, dim3(QT_WAVE), 0, stream, a);
+    else hipLaunchKernelGGL((solve_user_kernel<false, false, false>), grid, dim3(QT_WAVE), 0, stream, a);
   }
   return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;
 }

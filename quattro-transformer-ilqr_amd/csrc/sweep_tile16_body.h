@@ -190,10 +190,11 @@ constexpr int sweep_lin_floats() {
 // ---- MODE_FUSED_RK4, stage (1): the four stage points of one step -> Rk4Coef record (132 floats)
 // (tm * ... here against fill_dynamics' (dt * tm) * ... under contract(off): the same Jacobian entries, rounded differently; merging
 // them would change Euler or RK4 records in the last bit)
-__device__ __forceinline__ void rk4_stage_entries(const QuadStage& s, const quattro_model_params& p, float* c) {
+// (`ph`, here and below: the physical parameters of the trajectory -- fa.p.phys, or its row of model_phys held as values)
+__device__ __forceinline__ void rk4_stage_entries(const QuadStage& s, const float* ph, float* c) {
   const QuadTrig& t = s.t;
-  const float inv_mass = 1.0f / p.phys[0];
-  const float c1 = (p.phys[2] - p.phys[3]) / p.phys[1], c2 = (p.phys[3] - p.phys[1]) / p.phys[2], c3 = (p.phys[1] - p.phys[2]) / p.phys[3];
+  const float inv_mass = 1.0f / ph[0];
+  const float c1 = (ph[2] - ph[3]) / ph[1], c2 = (ph[3] - ph[1]) / ph[2], c3 = (ph[1] - ph[2]) / ph[3];
   c[0] = s.tm * (t.sps * t.cph - t.cps * t.sth * t.sph);     // d v_x' / d phi, theta, psi, thrust
   c[1] = s.tm * (t.cps * t.cth * t.cph);
   c[2] = s.tm * s.ry;
@@ -225,12 +226,13 @@ __device__ __forceinline__ void rk4_stage_entries(const QuadStage& s, const quat
 }
 
 template <class Emit>
-__device__ __forceinline__ void rk4_step_coefs(const quattro_model_params& p, const float* xs, const float* us, Emit emit) {
+__device__ __forceinline__ void rk4_step_coefs(const quattro_model_params& p, const float* ph, const float* xs, const float* us,
+                                               Emit emit) {
   constexpr int NX = 12;
   // each stage's 28 coefficients leave before the next stage point is computed
   float c[Rk4Coef::PER_STAGE];
-  quad_rk4_stages(p, xs, us, [&](int stage, const QuadStage& s) __attribute__((always_inline)) {
-    rk4_stage_entries(s, p, c);
+  quad_rk4_stages(p, ph, xs, us, [&](int stage, const QuadStage& s) __attribute__((always_inline)) {
+    rk4_stage_entries(s, ph, c);
 #pragma unroll
     for (int q = 0; q < Rk4Coef::PER_STAGE / 4; ++q) emit(stage * (Rk4Coef::PER_STAGE / 4) + q, make_float4(c[4 * q], c[4 * q + 1], c[4 * q + 2], c[4 * q + 3]));
   });
@@ -264,7 +266,7 @@ struct Rk4Entry {
   int idx;
   float cst;
 };
-__device__ __forceinline__ Rk4Entry rk4_m_entry(const quattro_model_params& p, int row_tile, int col_tile) {
+__device__ __forceinline__ Rk4Entry rk4_m_entry(const float* ph, int row_tile, int col_tile) {
   Rk4Entry e{Rk4Tab::ZERO, 0.0f};
   if ((row_tile & 3) == 3) return e;
   const int i = 3 * (row_tile >> 2) + (row_tile & 3);
@@ -274,9 +276,9 @@ __device__ __forceinline__ Rk4Entry rk4_m_entry(const quattro_model_params& p, i
     if (i == 3) e.idx = 3;
     else if (i == 4) e.idx = 7;
     else if (i == 5) e.idx = 10;
-    else if (i == 9) e.cst = ((g == 1 || g == 2) ? 1.0f : -1.0f) * (p.phys[4] / p.phys[1]);
-    else if (i == 10) e.cst = (g < 2 ? 1.0f : -1.0f) * (p.phys[4] / p.phys[2]);
-    else if (i == 11) e.cst = ((g & 1) ? -1.0f : 1.0f) * (p.phys[6] / p.phys[3]);
+    else if (i == 9) e.cst = ((g == 1 || g == 2) ? 1.0f : -1.0f) * (ph[4] / ph[1]);
+    else if (i == 10) e.cst = (g < 2 ? 1.0f : -1.0f) * (ph[4] / ph[2]);
+    else if (i == 11) e.cst = ((g & 1) ? -1.0f : 1.0f) * (ph[6] / ph[3]);
     return e;
   }
   if (i < 3) { if (j == i + 3) e.cst = 1.0f; return e; }
@@ -293,12 +295,26 @@ __device__ __forceinline__ Rk4Entry rk4_m_entry(const quattro_model_params& p, i
 }
 
 // -> the ILLCOND verdict of this trajectory (wave-uniform; also written to status[b] when there is a status array)
-template <int MODE>
+// PHYS (the fused modes of the persistent loop, quattro_ilqr_solve_phys_f32 / quattro_mpc_run_phys_f32): row b of model_phys [B][8]
+// replaces fa.p.phys.  The wave owns the trajectory, so the row is wave-uniform: its values are read ONCE, through a uniform
+// address in the constant address space (scalar loads; the array is never written while the kernel runs), and handed as values to
+// the code that reads phys.  Everything else of the problem (dt, the lane-indexed q, qf, x_ref, r) stays in the argument block.
+template <int MODE, bool PHYS = false>
 __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec, const float* __restrict__ VxN,
                                                   const float* __restrict__ VxxN, int S, float reg,
                                                   float* __restrict__ Kout, float* __restrict__ kout,
                                                   int32_t* __restrict__ status, const FusedArgs& fa, const int b,
-                                                  const int lane, float* s_t, float* s_vx, float* s_lin) {
+                                                  const int lane, float* s_t, float* s_vx, float* s_lin,
+                                                  const float* model_phys = nullptr) {
+  static_assert(!PHYS || MODE == MODE_FUSED || MODE == MODE_FUSED_RK4, "per-trajectory parameters: the fused modes only");
+  float phv[8];
+  if constexpr (PHYS) {
+    typedef const float __attribute__((address_space(4))) * ConstRow;
+    const ConstRow row = (ConstRow)model_phys + 8 * (size_t)__builtin_amdgcn_readfirstlane(b);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) phv[i] = row[i];
+  }
+  const float* const ph = PHYS ? phv : fa.p.phys;
   constexpr bool ROWPAD = MODE == MODE_ROWPAD;
   constexpr bool COMPACT = MODE != MODE_TILE16 && !ROWPAD;   // constants of the problem in a header record
   constexpr int REC_STRIDE = MODE == MODE_TILE16 ? Tile16Rec::STRIDE : MODE == MODE_DENSEF ? Tile16RRec::STRIDE : Tile16CRec::STRIDE;
@@ -333,9 +349,9 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
       static_assert(sweep_lin_floats<MODE>() % 4 == 0, "the LDS slice is zeroed in 16-byte pieces");
       for (int i = lane; i < sweep_lin_floats<MODE>() / 4; i += QT_WAVE) reinterpret_cast<f32x4*>(s_lin)[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
       wave_sync();
-      if (lane == 0) EulerRecord<QUATTRO_MODEL_QUADROTOR, Tile16Rec>::fill_const(s_lin, fa.p);
+      if (lane == 0) EulerRecord<QUATTRO_MODEL_QUADROTOR, Tile16Rec>::fill_const(s_lin, fa.p, ph);
       if (lane < FUSED_BATCH)
-        EulerRecord<QUATTRO_MODEL_QUADROTOR, Tile16FRec>::fill_const(s_lin + Tile16Rec::STRIDE + lane * Tile16FRec::STRIDE, fa.p);
+        EulerRecord<QUATTRO_MODEL_QUADROTOR, Tile16FRec>::fill_const(s_lin + Tile16Rec::STRIDE + lane * Tile16FRec::STRIDE, fa.p, ph);
       wave_sync();
     }
   } else if constexpr (ROWPAD) {
@@ -462,7 +478,7 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
     rk_dt = fa.p.dt;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const Rk4Entry ea = rk4_m_entry(fa.p, c, 4 * r + q), ec = rk4_m_entry(fa.p, 4 * r + q, c);
+      const Rk4Entry ea = rk4_m_entry(ph, c, 4 * r + q), ec = rk4_m_entry(ph, 4 * r + q, c);
       rk_aidx[q] = ea.idx;
       rk_acst[q] = ea.cst;
       rk_cidx[q] = ec.idx;
@@ -670,7 +686,7 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
         const float xs[12] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w, xc.x, xc.y, xc.z, xc.w};
         const float us[4] = {ua.x, ua.y, ua.z, ua.w};
         float4* dst = reinterpret_cast<float4*>(coef) + ls;
-        rk4_step_coefs(fa.p, xs, us, [&](int q, float4 v) __attribute__((always_inline)) { dst[(size_t)q * S] = v; });
+        rk4_step_coefs(fa.p, ph, xs, us, [&](int q, float4 v) __attribute__((always_inline)) { dst[(size_t)q * S] = v; });
       }
     }
     // the records are read back by other lanes of this same wave: complete (written through to L2) before any is loaded
@@ -740,7 +756,7 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
           float* mine = stage + sl * Tile16FRec::STRIDE;
           if (dynl) {
             quad_trig_finish(tr);
-            ER::fill_dynamics(mine, fa.p, tr, xs, us);
+            ER::fill_dynamics(mine, fa.p, ph, tr, xs, us);
           } else {
             ER::fill_lx(mine, fa.p, xs);
           }

@@ -219,14 +219,16 @@ class BatchedMPC:
         self.device = self.solver.device
         self.u_warm = None                      # (B, N, m) warm start for the next control step
 
-    def control_step(self, x_current, x_ref=None):
+    def control_step(self, x_current, x_ref=None, model_phys=None):
         """x_current (B, n) -> (x_seq (B,N+1,n), u_seq (B,N,m), iters (B,)) as fresh device tensors; keeps the shifted
-        control sequence as the next warm start."""
+        control sequence as the next warm start.  model_phys: per-controller model parameters, as in QuattroILQR.solve."""
+        if model_phys is not None:
+            self.solver._check_model_phys(model_phys, int(np.prod(tuple(np.shape(x_current)))) // self.model.n)
         x_current = torch.as_tensor(x_current, dtype=torch.float32, device=self.device).reshape(-1, self.model.n)
         B = x_current.shape[0]
         if self.u_warm is not None and self.u_warm.shape[0] != B:
             raise ValueError("batch size changed between control steps")
-        out = self.solver.solve(x_current, self.u_warm, x_ref=x_ref)
+        out = self.solver.solve(x_current, self.u_warm, x_ref=x_ref, model_phys=model_phys)
         u = out["u"]
         self.u_warm = torch.cat([u[:, 1:], u[:, -1:]], dim=1).contiguous()
         return out["x"].clone(), u.clone(), out["iters"].clone()
@@ -236,7 +238,8 @@ class BatchedMPC:
         xs, _ = ops.simulate(self.model, x.contiguous(), u0.reshape(-1, 1, self.model.m).contiguous())
         return xs[:, 1].contiguous()
 
-    def run(self, x0, steps, disturbance=None, device_loop=True, *, plant=None, plant_phys=None, replan_every=1, feedback=False):
+    def run(self, x0, steps, disturbance=None, device_loop=True, *, plant=None, plant_phys=None, replan_every=1, feedback=False,
+            model_phys=None):
         """Closed loop for `steps` control steps from x0 (B,n); the plant is the device model itself (the reference's
         plant is MuJoCo, out of scope), plus an optional additive state disturbance tensor (steps, B, n).
         Returns dict(x (B,steps+1,n), u (B,steps,m), iters (B,steps)).
@@ -257,9 +260,20 @@ class BatchedMPC:
           feedback      the gain term above on or off (open-loop hold against feedback hold); it is exactly zero for h = 1
         The same one launch (quattro_mpc_run_plant_f32) where the plain loop has one; the host-driven form — solve, ops.track,
         shift — otherwise, and always with a predictor.  ValueError, before anything touches the device: a plant that is not the
-        controller's problem, a plant_phys of the wrong shape, steps % replan_every != 0."""
+        controller's problem, a plant_phys of the wrong shape, steps % replan_every != 0.
+
+        model_phys (B, len(model.phys)), or the (B, 8) float32 device tensor of ops.model_phys_tensor: controller b PLANS with row
+        b in place of model.phys (B controllers that each know their own vehicle, or each hold a different belief about one
+        plant).  Its plant is plant_phys[b] if given, else plant.phys if a plant is given, else the same row — the default plant
+        is the controller's own model; the other plant keywords work as above.  One launch (quattro_mpc_run_phys_f32), always
+        the model's persistent kernel (a user model's too, as with device_loop="always"); NotImplementedError with a predictor,
+        device_loop=False or a model without such a kernel, ValueError for a wrong shape, before anything touches the device."""
         h = int(replan_every)
-        plain = plant is None and plant_phys is None and h == 1 and not feedback
+        if model_phys is not None:
+            if not device_loop:
+                raise NotImplementedError("model_phys runs only in the device-resident loop: device_loop=False is the host-driven loop")
+            self.solver._check_model_phys(model_phys, int(np.prod(tuple(np.shape(x0)))) // self.model.n)
+        plain = plant is None and plant_phys is None and h == 1 and not feedback and model_phys is None
         if not plain:
             ops.check_plant(self.model, plant)
             if h < 1 or h > self.horizon or steps % h != 0:
@@ -272,7 +286,7 @@ class BatchedMPC:
                 raise ValueError("feedback needs gains: max_iter >= 1")
         x = torch.as_tensor(x0, dtype=torch.float32, device=self.device).reshape(-1, self.model.n).contiguous()
         sv = self.solver
-        use_kernel = (ops.model_can_device_loop(self.model) if device_loop == "always"
+        use_kernel = (ops.model_can_device_loop(self.model) if device_loop == "always" or model_phys is not None
                       else bool(device_loop) and ops.model_has_device_loop(self.model))
         if not plain:
             plant_phys = ops.plant_phys_tensor(self.model, plant_phys, x.shape[0], self.device)
@@ -294,7 +308,8 @@ class BatchedMPC:
             dist_t = None
             if disturbance is not None:
                 dist_t = torch.as_tensor(disturbance, dtype=torch.float32, device=self.device).reshape(steps, B, n).contiguous()
-            extra = {} if plain else dict(plant=plant, plant_phys=plant_phys, hold=h, feedback=feedback)
+            extra = {} if plain else dict(plant=plant, plant_phys=plant_phys, hold=h, feedback=feedback,
+                                          model_phys=ops.model_phys_tensor(self.model, model_phys, B, self.device))
             ops.mpc_run(self.model, x_cur, sv.x, sv.u, sv.K, sv.k, sv.cost, sv.tol, sv.max_iter, steps, sv._ws, traj_x,
                         traj_u, traj_it, disturbance=dist_t, alphas=sv.alphas, reg=sv.reg, alpha_idx=sv.alpha_idx,
                         active=sv.active, iters=sv.iters, status=sv.status, **extra)

@@ -454,13 +454,17 @@ def solve_log_record(model, log, phase, x_nom, u_nom, K, k, cost, alpha_idx, act
 
 def ilqr_solve(model, x_nom, u_nom, K, k, cost, tol, max_iter, workspace, alphas=ALPHAS, reg=QUU_REG, x0=None,
                alpha_idx=None, active=None, iters=None, status=None, fixed_iters=False, reset=False, log=None,
-               persistent=False, enqueue=False):
+               persistent=False, enqueue=False, model_phys=None):
     """The whole solve from ONE C call with no host involvement: up to max_iter iterations, every trajectory stopping on
     its own test; x0 given = roll the nominal out from it first.  Everything in place (quattro_ilqr_solve_logged_f32).
     reset: the call sets active / iters / alpha_idx / status itself; log: a SolveLog ring filled by the device;
     persistent: take a persistent kernel that exists but is not the model's fastest form (a user model's); enqueue: never
-    the persistent kernel."""
+    the persistent kernel.
+    model_phys (B, len(model.phys)), or the (B, 8) float32 device tensor of model_phys_tensor: trajectory b is solved with row b
+    for the model's phys (quattro_ilqr_solve_phys_f32: always the model's persistent kernel; NotImplementedError where there is
+    none, ValueError together with enqueue)."""
     Bt, N, m = u_nom.shape
+    model_phys = model_phys_tensor(model, model_phys, Bt, u_nom.device)
     n = model.n
     f32, i32 = torch.float32, torch.int32
     _req(x_nom, (Bt, N + 1, n), f32, "x_nom"); _req(u_nom, (Bt, N, model.m), f32, "u_nom")
@@ -477,11 +481,13 @@ def ilqr_solve(model, x_nom, u_nom, K, k, cost, tol, max_iter, workspace, alphas
         raise ValueError("log ring was built for another problem size")
     arr, na = _alphas(alphas)
     p = model.c_params()
-    check(_lib.load_for(model).quattro_ilqr_solve_logged_f32(
-        ctypes.byref(p), _ptr(x0), _ptr(x_nom), _ptr(u_nom), Bt, N, float(reg), arr, na, float(tol), int(max_iter), flags,
-        _ptr(K), _ptr(k), _ptr(cost), _ptr(alpha_idx), _ptr(active), _ptr(iters), _ptr(status), _ptr(workspace),
-        workspace.numel() * workspace.element_size(), None if log is None else log.byref(), _stream()),
-        "quattro_ilqr_solve_logged_f32")
+    args = (ctypes.byref(p), _ptr(x0), _ptr(x_nom), _ptr(u_nom), Bt, N, float(reg), arr, na, float(tol), int(max_iter), flags,
+            _ptr(K), _ptr(k), _ptr(cost), _ptr(alpha_idx), _ptr(active), _ptr(iters), _ptr(status), _ptr(workspace),
+            workspace.numel() * workspace.element_size(), None if log is None else log.byref())
+    if model_phys is not None:
+        check(_lib.load_for(model).quattro_ilqr_solve_phys_f32(*args, _ptr(model_phys), _stream()), "quattro_ilqr_solve_phys_f32")
+        return
+    check(_lib.load_for(model).quattro_ilqr_solve_logged_f32(*args, _stream()), "quattro_ilqr_solve_logged_f32")
 
 
 class PreparedSolve:
@@ -501,18 +507,28 @@ class PreparedSolve:
         self.arr, self.na = _alphas(alphas)
         self.p = model.c_params()
         self.fn = _lib.load_for(model).quattro_ilqr_solve_logged_f32
+        self.model = model
         self.dims = (Bt, N, n, m)
         self.head = (ctypes.byref(self.p), _ptr(x0), _ptr(x_nom), _ptr(u_nom), Bt, N, float(reg), self.arr, self.na)
         self.tail = (_ptr(K), _ptr(k), _ptr(cost), _ptr(alpha_idx), _ptr(active), _ptr(iters), _ptr(status), _ptr(workspace),
                      workspace.numel() * workspace.element_size())
 
-    def __call__(self, tol, max_iter, fixed_iters=False, log=None, persistent=False, stream=None):
+    def __call__(self, tol, max_iter, fixed_iters=False, log=None, persistent=False, stream=None, model_phys=None):
+        """model_phys: per-trajectory phys rows (ilqr_solve).  Nothing of it is prepared or kept: whether the call goes to the
+        phys entry, and with which pointer, is decided by THIS call's argument, so a later call without it is the plain solve."""
         flags = _lib.SOLVE_SIMULATE | _lib.SOLVE_RESET | (_lib.SOLVE_FIXED_ITERS if fixed_iters else 0) | \
             (_lib.SOLVE_PERSISTENT if persistent else 0)
         if log is not None and (log.B, log.N, log.n, log.m) != self.dims:
             raise ValueError("log ring was built for another problem size")
-        check(self.fn(*self.head, float(tol), int(max_iter), flags, *self.tail, None if log is None else log.byref(),
-                      _stream() if stream is None else stream), "quattro_ilqr_solve_logged_f32")
+        st = _stream() if stream is None else stream
+        if model_phys is not None:
+            model_phys = model_phys_tensor(self.model, model_phys, self.dims[0], self.keep[0].device)
+            fn = _lib.load_for(self.model).quattro_ilqr_solve_phys_f32
+            check(fn(*self.head, float(tol), int(max_iter), flags, *self.tail, None if log is None else log.byref(),
+                     _ptr(model_phys), st), "quattro_ilqr_solve_phys_f32")
+            return
+        check(self.fn(*self.head, float(tol), int(max_iter), flags, *self.tail, None if log is None else log.byref(), st),
+              "quattro_ilqr_solve_logged_f32")
 
 
 def check_plant(model, plant):
@@ -527,18 +543,43 @@ def check_plant(model, plant):
         raise ValueError("plant must be the controller's model (name, n, m, dt and library) with its own phys / integrator")
 
 
-def plant_phys_tensor(model, plant_phys, B, device):
+def plant_phys_tensor(model, plant_phys, B, device, name="plant_phys"):
     """(B, len(model.phys)) per-controller physical parameters -> the (B, 8) float32 device array the C ABI takes (None stays
     None).  The shape is checked before anything touches the device."""
     if plant_phys is None:
         return None
-    shape = tuple(plant_phys.shape)
+    shape = tuple(np.shape(plant_phys))
     if shape != (B, len(model.phys)):
-        raise ValueError(f"plant_phys must have shape {(B, len(model.phys))} (got {shape})")
+        raise ValueError(f"{name} must have shape {(B, len(model.phys))} (got {shape})")
     t = torch.as_tensor(plant_phys, dtype=torch.float32, device=device)
     out = torch.zeros((B, 8), dtype=torch.float32, device=device)
     out[:, :shape[1]] = t
     return out
+
+
+def _is_phys_rows(t, B):
+    """A (B, 8) contiguous float32 device tensor: what the C ABI takes, passed through as it is."""
+    return (isinstance(t, torch.Tensor) and tuple(t.shape) == (B, 8) and t.is_cuda and t.dtype == torch.float32
+            and t.is_contiguous())
+
+
+def check_model_phys(model, model_phys, B):
+    """ValueError unless model_phys is None, (B, len(model.phys)) or a (B, 8) device tensor; host logic only."""
+    if model_phys is None or _is_phys_rows(model_phys, B):
+        return
+    shape = tuple(np.shape(model_phys))
+    if shape != (B, len(model.phys)):
+        raise ValueError(f"model_phys must have shape {(B, len(model.phys))} (got {shape})")
+
+
+def model_phys_tensor(model, model_phys, B, device):
+    """Per-trajectory model parameters (B, len(model.phys)) -> the (B, 8) float32 device array the C ABI takes, by
+    plant_phys_tensor's conversion; such an array is passed through as it is, None stays None.  The shape is checked before
+    anything touches the device."""
+    check_model_phys(model, model_phys, B)
+    if model_phys is None or _is_phys_rows(model_phys, B):
+        return model_phys
+    return plant_phys_tensor(model, model_phys, B, device, name="model_phys")
 
 
 def _plant_args(model, plant, plant_phys, B, device):
@@ -578,16 +619,19 @@ def track(model, x0, x_nom, u_nom, K, steps, plant=None, plant_phys=None, feedba
 
 def mpc_run(model, x_cur, x_nom, u_nom, K, k, cost, tol, max_iter, n_steps, workspace, traj_x, traj_u, traj_iters,
             disturbance=None, alphas=ALPHAS, reg=QUU_REG, alpha_idx=None, active=None, iters=None, status=None,
-            plant=None, plant_phys=None, hold=1, feedback=False):
+            plant=None, plant_phys=None, hold=1, feedback=False, model_phys=None):
     """B controllers x n_steps control steps (solve -> apply u_0 -> shift the warm start) in ONE launch
     (quattro_mpc_run_f32); x_cur and u_nom advance in place, the closed-loop record goes to traj_x / traj_u / traj_iters.
     plant / plant_phys / hold / feedback (any of them off its default: quattro_mpc_run_plant_f32): n_steps PLANT steps, a solve
-    every `hold` of them and the gain law of track() in between, on a plant of its own; traj_iters is then (B, n_steps / hold)."""
+    every `hold` of them and the gain law of track() in between, on a plant of its own; traj_iters is then (B, n_steps / hold).
+    model_phys (as in ilqr_solve; quattro_mpc_run_phys_f32, the plant entry's arguments and these rows): controller b plans with
+    row b for its model's phys, and its plant is plant_phys[b], else plant.phys, else that same row."""
     Bt, N, m = u_nom.shape
     n = model.n
     f32, i32 = torch.float32, torch.int32
     hold = int(hold)
-    plain = plant is None and plant_phys is None and hold == 1 and not feedback
+    check_model_phys(model, model_phys, Bt)
+    plain = plant is None and plant_phys is None and hold == 1 and not feedback and model_phys is None
     if hold < 1 or n_steps % hold != 0:
         raise ValueError("n_steps must be a multiple of hold >= 1")
     _req(x_cur, (Bt, n), f32, "x_cur"); _req(x_nom, (Bt, N + 1, n), f32, "x_nom"); _req(u_nom, (Bt, N, model.m), f32, "u_nom")
@@ -608,5 +652,10 @@ def mpc_run(model, x_cur, x_nom, u_nom, K, k, cost, tol, max_iter, n_steps, work
         check(_lib.load_for(model).quattro_mpc_run_f32(*head, _stream()), "quattro_mpc_run_f32")
         return
     pref, keep, pphys = _plant_args(model, plant, plant_phys, Bt, u_nom.device)
+    if model_phys is not None:
+        model_phys = model_phys_tensor(model, model_phys, Bt, u_nom.device)
+        check(_lib.load_for(model).quattro_mpc_run_phys_f32(*head, pref, _ptr(pphys), hold, int(bool(feedback)), _ptr(model_phys),
+                                                            _stream()), "quattro_mpc_run_phys_f32")
+        return
     check(_lib.load_for(model).quattro_mpc_run_plant_f32(*head, pref, _ptr(pphys), hold, int(bool(feedback)), _stream()),
           "quattro_mpc_run_plant_f32")

@@ -354,18 +354,42 @@ class QuattroILQR:
             return bool(self._active_host.numpy().any())
         return int(self.active.sum().item()) != 0
 
+    def _check_model_phys(self, model_phys, B):
+        """model_phys runs in the device-resident loop alone: NotImplementedError for every mode that has none, ValueError for a
+        wrong shape, both before anything touches the device."""
+        why = None
+        if self.tf is not None:
+            why = "a predictor (tf) makes the solve a host-driven hybrid loop"
+        elif self.use_graph:
+            why = "use_graph=True replays host-enqueued iterations"
+        elif not self.device_loop:
+            why = "device_loop=False is the host-driven loop"
+        elif not ops.model_can_device_loop(self.model):
+            why = f"model {self.model.name} ({self.model.integrator}) has no persistent kernel"
+        if why is not None:
+            raise NotImplementedError(f"model_phys runs only in the device-resident loop: {why}")
+        ops.check_model_phys(self.model, model_phys, B)
+
     def solve(self, x0, u_init=None, x_ref=None, max_iter=None, fixed_iters=False, log=None, want_alpha=True,
-              upload_guard=True):
+              upload_guard=True, model_phys=None):
         """x0 (B,n), u_init (B,N,m) (zeros if None).  Returns a dict of device tensors:
         K (B,N,m,n), k (B,N,m), x (B,N+1,n), u (B,N,m), cost (B,) fp64, iters (B,), alpha (B,) last accepted step
         (-1: none), status (B,).  fixed_iters=True runs exactly max_iter iterations (benchmarking: stop flags off).
         log: an ops.SolveLog ring the DEVICE fills with one record per trajectory and iteration (the reference's log dict
         and timing samples) — by the persistent kernel between its phases, or by one small launch per phase of a hybrid
-        iteration; no host involvement either way."""
+        iteration; no host involvement either way.
+        model_phys (B, len(model.phys)), or the (B, 8) float32 device tensor of ops.model_phys_tensor: trajectory b is solved with
+        row b in place of model.phys (a user model's free parameters likewise) — what B solvers, each built on
+        model.with_(phys=row b), return for their one trajectory, bit for bit.  Always the model's persistent kernel (a user
+        model's too, as with device_loop="always"); NotImplementedError with a predictor, use_graph=True, device_loop=False or
+        a model without such a kernel, ValueError for a wrong shape, both before anything touches the device.  A later call
+        without it is the plain solve."""
         n, m, N, dev = self.model.n, self.model.m, self.horizon, self.device
         if not isinstance(x0, torch.Tensor):
             x0 = np.asarray(x0)
         B = int(np.prod(tuple(x0.shape))) // n
+        if model_phys is not None:
+            self._check_model_phys(model_phys, B)
         self._alloc(B)
         self._upload(x0, u_init, guard=upload_guard)
         x0 = self._x0
@@ -383,7 +407,7 @@ class QuattroILQR:
                     self.tf.shifted_mean(xr - off, out=self._tf_mean)
                 self._ref_key = key
             x_ref_t = self._x_ref_t
-        if self.tf is None and not self.use_graph and self._wants_device_loop():
+        if self.tf is None and not self.use_graph and (self._wants_device_loop() or model_phys is not None):
             # the whole loop on the device: per-solve state reset, nominal rollout, iterations, per-trajectory stop tests —
             # one launch, no synchronisation
             if self._ws is None:
@@ -391,7 +415,10 @@ class QuattroILQR:
             if self._solve_call is None:        # shapes and pointers are fixed for this batch size: checked once
                 self._solve_call = ops.PreparedSolve(self.model, self.x, self.u, self.K, self.k, self.cost, self._ws, self.alphas,
                                                      self.reg, x0, self.alpha_idx, self.active, self.iters, self.status)
-            self._solve_call(self.tol, max_iter, fixed_iters=fixed_iters, log=log, persistent=self.device_loop == "always")
+            # (the rows stay referenced until the next solve: the launch is asynchronous)
+            self._model_phys = ops.model_phys_tensor(self.model, model_phys, B, dev)
+            self._solve_call(self.tol, max_iter, fixed_iters=fixed_iters, log=log, persistent=self.device_loop == "always",
+                             model_phys=self._model_phys)
             max_iter = 0
         else:
             self._ints.copy_(self._ints_init)          # active = 1, iters = 0, alpha_idx = -1, status = 0

@@ -8,7 +8,10 @@ gain-feedback forms (recorded, no target).  Quadrotor, B = 4096, N = 50, host cl
                                                         only, and prints both medians and the older build's own spread
 
 Default forms: BatchedMPC.run of 10 control steps (the README's 5.4 ms) and a converged QuattroILQR.solve (its 2.4 ms).
-New forms: 50 plant steps with replan_every = 1 and with replan_every = 5 + feedback + per-controller plants; ops.track of 5 steps.
+New forms: 50 plant steps with replan_every = 1 and with replan_every = 5 + feedback + per-controller plants; ops.track of 5 steps;
+the converged solve and the 10 control steps with per-trajectory model parameters (model_phys: every parameter of every
+trajectory within 12 % of the model's) next to the same calls without, and with neutral rows (the PHYS kernels on the default
+problem: same work, same iteration counts).
 """
 import argparse
 import ctypes
@@ -28,8 +31,10 @@ def measure(defaults_only):
     from quattro_ilqr_amd import _lib
     raw = ctypes.CDLL(_lib.LIB_PATH)
     new_abi = hasattr(raw, "quattro_mpc_run_plant_f32")
-    if not new_abi:           # an older build of the library: bind what it has (the default forms need nothing newer)
-        for name in ("quattro_track_f32", "quattro_mpc_run_plant_f32"):
+    phys_abi = hasattr(raw, "quattro_mpc_run_phys_f32")
+    # an older build of the library: bind what it has (the default forms need nothing newer)
+    for name in ("quattro_track_f32", "quattro_mpc_run_plant_f32", "quattro_ilqr_solve_phys_f32", "quattro_mpc_run_phys_f32"):
+        if not hasattr(raw, name):
             _lib.SIGNATURES.pop(name, None)
     from quattro_ilqr_amd import BatchedMPC, QuattroILQR, ops, quadrotor_model
     import bench
@@ -49,7 +54,7 @@ def measure(defaults_only):
             ts.append(1e3 * (time.perf_counter() - t0))
         return float(np.median(ts))
 
-    out = {"lib": os.path.basename(_lib.LIB_PATH), "new_abi": new_abi}
+    out = {"lib": os.path.basename(_lib.LIB_PATH), "new_abi": new_abi, "phys_abi": phys_abi}
     mpc = BatchedMPC(md, N, max_iter=100, tol=1e-3, device=dev)
 
     def run(steps, **kw):
@@ -78,6 +83,18 @@ def measure(defaults_only):
         xs = xn[:, 0].contiguous()
         out["track_5_steps_ms"] = timed(lambda: ops.track(md, xs, xn, un, K, 5, plant=plant, plant_phys=phys_t), reps=21)
         out["track_50_steps_ms"] = timed(lambda: ops.track(md, xs, xn, un, K, 50, plant=plant, plant_phys=phys_t), reps=21)
+    if not defaults_only and phys_abi:
+        base = np.asarray(md.phys, dtype=np.float64)
+        b_, j_ = np.arange(B)[:, None], np.arange(base.size)[None, :]
+        rows = ops.model_phys_tensor(md, (base * (1.0 + 0.12 * np.sin(1.0 + b_ + 1.7 * j_))).astype(np.float32), B, dev)
+        neutral = ops.model_phys_tensor(md, np.tile(base.astype(np.float32), (B, 1)), B, dev)
+        # the three forms of each call alternate, so that clocks and caches treat them alike
+        for rnd in range(3):
+            for tag, kw in (("shared", {}), ("neutral_rows", dict(model_phys=neutral)), ("model_phys", dict(model_phys=rows))):
+                out.setdefault(f"solve_{tag}_ms", []).append(timed(lambda: sv.solve(x0, max_iter=100, **kw), reps=5))
+                out.setdefault(f"mpc_run_10_steps_{tag}_ms", []).append(timed(lambda: run(10, **kw), reps=5))
+                if rnd == 0:
+                    out[f"solve_{tag}_mean_iters"] = float(sv.solve(x0, max_iter=100, **kw)["iters"].float().mean())
     print(json.dumps(out), flush=True)
 
 
