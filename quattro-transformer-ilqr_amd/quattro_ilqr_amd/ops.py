@@ -456,13 +456,13 @@ def ilqr_solve(model, x_nom, u_nom, K, k, cost, tol, max_iter, workspace, alphas
                alpha_idx=None, active=None, iters=None, status=None, fixed_iters=False, reset=False, log=None,
                persistent=False, enqueue=False, model_phys=None):
     """The whole solve from ONE C call with no host involvement: up to max_iter iterations, every trajectory stopping on
-    its own test; x0 given = roll the nominal out from it first.  Everything in place (quattro_ilqr_solve_logged_f32).
+    its own test; x0 given = roll the nominal out from it first.  Everything in place (quattro_ilqr_solve_phys_f32).
     reset: the call sets active / iters / alpha_idx / status itself; log: a SolveLog ring filled by the device;
     persistent: take a persistent kernel that exists but is not the model's fastest form (a user model's); enqueue: never
     the persistent kernel.
     model_phys (B, len(model.phys)), or the (B, 8) float32 device tensor of model_phys_tensor: trajectory b is solved with row b
-    for the model's phys (quattro_ilqr_solve_phys_f32: always the model's persistent kernel; NotImplementedError where there is
-    none, ValueError together with enqueue)."""
+    for the model's phys (always the model's persistent kernel; NotImplementedError where there is none, ValueError together
+    with enqueue).  None: the solve with model.phys for every trajectory."""
     Bt, N, m = u_nom.shape
     model_phys = model_phys_tensor(model, model_phys, Bt, u_nom.device)
     n = model.n
@@ -484,10 +484,7 @@ def ilqr_solve(model, x_nom, u_nom, K, k, cost, tol, max_iter, workspace, alphas
     args = (ctypes.byref(p), _ptr(x0), _ptr(x_nom), _ptr(u_nom), Bt, N, float(reg), arr, na, float(tol), int(max_iter), flags,
             _ptr(K), _ptr(k), _ptr(cost), _ptr(alpha_idx), _ptr(active), _ptr(iters), _ptr(status), _ptr(workspace),
             workspace.numel() * workspace.element_size(), None if log is None else log.byref())
-    if model_phys is not None:
-        check(_lib.load_for(model).quattro_ilqr_solve_phys_f32(*args, _ptr(model_phys), _stream()), "quattro_ilqr_solve_phys_f32")
-        return
-    check(_lib.load_for(model).quattro_ilqr_solve_logged_f32(*args, _stream()), "quattro_ilqr_solve_logged_f32")
+    check(_lib.load_for(model).quattro_ilqr_solve_phys_f32(*args, _ptr(model_phys), _stream()), "quattro_ilqr_solve_phys_f32")
 
 
 class PreparedSolve:
@@ -506,7 +503,7 @@ class PreparedSolve:
         self.keep = (x_nom, u_nom, K, k, cost, workspace, x0, alpha_idx, active, iters, status)     # the pointers stay valid
         self.arr, self.na = _alphas(alphas)
         self.p = model.c_params()
-        self.fn = _lib.load_for(model).quattro_ilqr_solve_logged_f32
+        self.fn = _lib.load_for(model).quattro_ilqr_solve_phys_f32
         self.model = model
         self.dims = (Bt, N, n, m)
         self.head = (ctypes.byref(self.p), _ptr(x0), _ptr(x_nom), _ptr(u_nom), Bt, N, float(reg), self.arr, self.na)
@@ -514,21 +511,15 @@ class PreparedSolve:
                      workspace.numel() * workspace.element_size())
 
     def __call__(self, tol, max_iter, fixed_iters=False, log=None, persistent=False, stream=None, model_phys=None):
-        """model_phys: per-trajectory phys rows (ilqr_solve).  Nothing of it is prepared or kept: whether the call goes to the
-        phys entry, and with which pointer, is decided by THIS call's argument, so a later call without it is the plain solve."""
+        """model_phys: per-trajectory phys rows (ilqr_solve).  Nothing of it is prepared or kept: the rows are THIS call's argument,
+        so a later call without it is the plain solve."""
         flags = _lib.SOLVE_SIMULATE | _lib.SOLVE_RESET | (_lib.SOLVE_FIXED_ITERS if fixed_iters else 0) | \
             (_lib.SOLVE_PERSISTENT if persistent else 0)
         if log is not None and (log.B, log.N, log.n, log.m) != self.dims:
             raise ValueError("log ring was built for another problem size")
-        st = _stream() if stream is None else stream
-        if model_phys is not None:
-            model_phys = model_phys_tensor(self.model, model_phys, self.dims[0], self.keep[0].device)
-            fn = _lib.load_for(self.model).quattro_ilqr_solve_phys_f32
-            check(fn(*self.head, float(tol), int(max_iter), flags, *self.tail, None if log is None else log.byref(),
-                     _ptr(model_phys), st), "quattro_ilqr_solve_phys_f32")
-            return
-        check(self.fn(*self.head, float(tol), int(max_iter), flags, *self.tail, None if log is None else log.byref(), st),
-              "quattro_ilqr_solve_logged_f32")
+        model_phys = model_phys_tensor(self.model, model_phys, self.dims[0], self.keep[0].device)
+        check(self.fn(*self.head, float(tol), int(max_iter), flags, *self.tail, None if log is None else log.byref(),
+                      _ptr(model_phys), _stream() if stream is None else stream), "quattro_ilqr_solve_phys_f32")
 
 
 def check_plant(model, plant):
@@ -543,53 +534,32 @@ def check_plant(model, plant):
         raise ValueError("plant must be the controller's model (name, n, m, dt and library) with its own phys / integrator")
 
 
-def plant_phys_tensor(model, plant_phys, B, device, name="plant_phys"):
-    """(B, len(model.phys)) per-controller physical parameters -> the (B, 8) float32 device array the C ABI takes (None stays
-    None).  The shape is checked before anything touches the device."""
-    if plant_phys is None:
-        return None
-    shape = tuple(np.shape(plant_phys))
+def check_phys_rows(model, rows, B, name):
+    """Per-controller physical parameters, a plant's or a model's: None, (B, len(model.phys)), or the (B, 8) float32 device tensor the
+    C ABI takes.  ValueError otherwise; host logic only.  -> True where the rows need no conversion (None or such a tensor)."""
+    if rows is None or (isinstance(rows, torch.Tensor) and tuple(rows.shape) == (B, 8) and rows.is_cuda
+                        and rows.dtype == torch.float32 and rows.is_contiguous()):
+        return True
+    shape = tuple(np.shape(rows))
     if shape != (B, len(model.phys)):
         raise ValueError(f"{name} must have shape {(B, len(model.phys))} (got {shape})")
-    t = torch.as_tensor(plant_phys, dtype=torch.float32, device=device)
+    return False
+
+
+def plant_phys_tensor(model, plant_phys, B, device, name="plant_phys"):
+    """(B, len(model.phys)) rows -> the (B, 8) float32 device array the C ABI takes: the one conversion of both kinds of rows (a
+    plant's, a model's).  Such an array is passed through as it is, None stays None; the shape is checked (check_phys_rows) before
+    anything touches the device."""
+    if check_phys_rows(model, plant_phys, B, name):
+        return plant_phys
     out = torch.zeros((B, 8), dtype=torch.float32, device=device)
-    out[:, :shape[1]] = t
+    out[:, :len(model.phys)] = torch.as_tensor(plant_phys, dtype=torch.float32, device=device)
     return out
 
 
-def _is_phys_rows(t, B):
-    """A (B, 8) contiguous float32 device tensor: what the C ABI takes, passed through as it is."""
-    return (isinstance(t, torch.Tensor) and tuple(t.shape) == (B, 8) and t.is_cuda and t.dtype == torch.float32
-            and t.is_contiguous())
-
-
-def check_model_phys(model, model_phys, B):
-    """ValueError unless model_phys is None, (B, len(model.phys)) or a (B, 8) device tensor; host logic only."""
-    if model_phys is None or _is_phys_rows(model_phys, B):
-        return
-    shape = tuple(np.shape(model_phys))
-    if shape != (B, len(model.phys)):
-        raise ValueError(f"model_phys must have shape {(B, len(model.phys))} (got {shape})")
-
-
 def model_phys_tensor(model, model_phys, B, device):
-    """Per-trajectory model parameters (B, len(model.phys)) -> the (B, 8) float32 device array the C ABI takes, by
-    plant_phys_tensor's conversion; such an array is passed through as it is, None stays None.  The shape is checked before
-    anything touches the device."""
-    check_model_phys(model, model_phys, B)
-    if model_phys is None or _is_phys_rows(model_phys, B):
-        return model_phys
+    """Per-trajectory model parameters: plant_phys_tensor under the name the errors use."""
     return plant_phys_tensor(model, model_phys, B, device, name="model_phys")
-
-
-def _plant_args(model, plant, plant_phys, B, device):
-    check_plant(model, plant)
-    pp = None if plant is None else plant.c_params()
-    if plant_phys is not None and not (isinstance(plant_phys, torch.Tensor) and tuple(plant_phys.shape) == (B, 8)
-                                       and plant_phys.is_cuda and plant_phys.dtype == torch.float32
-                                       and plant_phys.is_contiguous()):
-        plant_phys = plant_phys_tensor(model, plant_phys, B, device)
-    return (None if pp is None else ctypes.byref(pp)), pp, plant_phys
 
 
 def track(model, x0, x_nom, u_nom, K, steps, plant=None, plant_phys=None, feedback=True, disturbance=None):
@@ -607,14 +577,30 @@ def track(model, x0, x_nom, u_nom, K, steps, plant=None, plant_phys=None, feedba
     _req(K, (Bt, N, m, n), f32, "K")
     if disturbance is not None:
         _req(disturbance, (steps, Bt, n), f32, "disturbance")
-    pref, keep, pphys = _plant_args(model, plant, plant_phys, Bt, u_nom.device)
+    check_plant(model, plant)
+    pp = None if plant is None else plant.c_params()
+    pphys = plant_phys_tensor(model, plant_phys, Bt, u_nom.device)
     x = torch.empty((Bt, steps + 1, n), dtype=f32, device=u_nom.device)
     u = torch.empty((Bt, steps, m), dtype=f32, device=u_nom.device)
     p = model.c_params()
+    pref = None if pp is None else ctypes.byref(pp)
     check(_lib.load_for(model).quattro_track_f32(ctypes.byref(p), pref, _ptr(pphys), _ptr(x0), _ptr(x_nom), _ptr(u_nom), _ptr(K),
                                                  int(bool(feedback)), Bt, N, steps, _ptr(disturbance), _ptr(x), _ptr(u), _stream()),
           "quattro_track_f32")
     return x, u
+
+
+def _mpc_args(model, x_cur, x_nom, u_nom, K, k, cost, tol, max_iter, n_steps, workspace, traj_x, traj_u, traj_iters, disturbance,
+              alphas, reg, alpha_idx, active, iters, status):
+    """-> (the arguments the three MPC entries share, in the order of quattro_mpc_run_f32 without its stream; what they point to,
+    to be kept until the call has returned)."""
+    Bt, N, _ = u_nom.shape
+    arr, na = _alphas(alphas)
+    p = model.c_params()
+    return (ctypes.byref(p), _ptr(x_cur), _ptr(x_nom), _ptr(u_nom), Bt, N, float(reg), arr, na, float(tol), int(max_iter),
+            int(n_steps), _ptr(traj_x), _ptr(traj_u), _ptr(traj_iters), _ptr(disturbance), _ptr(K), _ptr(k), _ptr(cost),
+            _ptr(alpha_idx), _ptr(active), _ptr(iters), _ptr(status), _ptr(workspace),
+            workspace.numel() * workspace.element_size()), (p, arr)
 
 
 def mpc_run(model, x_cur, x_nom, u_nom, K, k, cost, tol, max_iter, n_steps, workspace, traj_x, traj_u, traj_iters,
@@ -630,7 +616,7 @@ def mpc_run(model, x_cur, x_nom, u_nom, K, k, cost, tol, max_iter, n_steps, work
     n = model.n
     f32, i32 = torch.float32, torch.int32
     hold = int(hold)
-    check_model_phys(model, model_phys, Bt)
+    check_phys_rows(model, model_phys, Bt, "model_phys")
     plain = plant is None and plant_phys is None and hold == 1 and not feedback and model_phys is None
     if hold < 1 or n_steps % hold != 0:
         raise ValueError("n_steps must be a multiple of hold >= 1")
@@ -643,15 +629,15 @@ def mpc_run(model, x_cur, x_nom, u_nom, K, k, cost, tol, max_iter, n_steps, work
         _req(status, (Bt,), i32, "status")
     if disturbance is not None:
         _req(disturbance, (n_steps, Bt, n), f32, "disturbance")
-    arr, na = _alphas(alphas)
-    p = model.c_params()
-    head = (ctypes.byref(p), _ptr(x_cur), _ptr(x_nom), _ptr(u_nom), Bt, N, float(reg), arr, na, float(tol), int(max_iter),
-            int(n_steps), _ptr(traj_x), _ptr(traj_u), _ptr(traj_iters), _ptr(disturbance), _ptr(K), _ptr(k), _ptr(cost),
-            _ptr(alpha_idx), _ptr(active), _ptr(iters), _ptr(status), _ptr(workspace), workspace.numel() * workspace.element_size())
+    head, keep = _mpc_args(model, x_cur, x_nom, u_nom, K, k, cost, tol, max_iter, n_steps, workspace, traj_x, traj_u, traj_iters,
+                           disturbance, alphas, reg, alpha_idx, active, iters, status)
     if plain:
         check(_lib.load_for(model).quattro_mpc_run_f32(*head, _stream()), "quattro_mpc_run_f32")
         return
-    pref, keep, pphys = _plant_args(model, plant, plant_phys, Bt, u_nom.device)
+    check_plant(model, plant)
+    pp = None if plant is None else plant.c_params()
+    pref = None if pp is None else ctypes.byref(pp)
+    pphys = plant_phys_tensor(model, plant_phys, Bt, u_nom.device)
     if model_phys is not None:
         model_phys = model_phys_tensor(model, model_phys, Bt, u_nom.device)
         check(_lib.load_for(model).quattro_mpc_run_phys_f32(*head, pref, _ptr(pphys), hold, int(bool(feedback)), _ptr(model_phys),

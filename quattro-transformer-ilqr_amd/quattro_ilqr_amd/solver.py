@@ -368,7 +368,7 @@ class QuattroILQR:
             why = f"model {self.model.name} ({self.model.integrator}) has no persistent kernel"
         if why is not None:
             raise NotImplementedError(f"model_phys runs only in the device-resident loop: {why}")
-        ops.check_model_phys(self.model, model_phys, B)
+        ops.check_phys_rows(self.model, model_phys, B, "model_phys")
 
     def solve(self, x0, u_init=None, x_ref=None, max_iter=None, fixed_iters=False, log=None, want_alpha=True,
               upload_guard=True, model_phys=None):

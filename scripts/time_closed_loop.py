@@ -3,11 +3,17 @@ gain-feedback forms (recorded, no target).  Quadrotor, B = 4096, N = 50, host cl
 
   time_closed_loop.py                                   one process, the shipped library: every figure below, one JSON line
   time_closed_loop.py --ab OLD.so [--rounds 5]          regression check on ONE box: alternates OLD.so (e.g. the parent commit's
-                                                        build, under build_ab/) and the shipped library, `rounds` child processes
-                                                        each (the QUATTRO_HIP_LIB mechanism of scripts/ab_lib.sh), default forms
-                                                        only, and prints both medians and the older build's own spread
+                                                        build, under build_ab/; it must export the phys entries ops calls) and the
+                                                        shipped library, `rounds` child processes each (the QUATTRO_HIP_LIB
+                                                        mechanism of scripts/ab_lib.sh), default forms only.  Prints both medians
+                                                        and the older build's own spread, and FAILS (exit status 1) if the two
+                                                        builds do not compute the same bits, or if a median of the shipped library
+                                                        lies above the maximum of the older build's own rounds.
 
-Default forms: BatchedMPC.run of 10 control steps (the README's 5.4 ms) and a converged QuattroILQR.solve (its 2.4 ms).
+Default forms: BatchedMPC.run of 10 control steps (the README's 5.4 ms) and a converged QuattroILQR.solve (its 2.4 ms); for the
+cart-pole the same two at BASELINE configs[1]'s shape (Euler, B = 1024, N = 50).  Bits: a SHA-256 per model and integrator over
+a converged solve (K, k, cost, alpha_idx, status) and 3 control steps with a seeded disturbance after it (x, u, iters of the run
+and K, k, cost, alpha_idx, status of the solver), quadrotor B = 5, N = 26, cart-pole B = 9, N = 30.
 New forms: 50 plant steps with replan_every = 1 and with replan_every = 5 + feedback + per-controller plants; ops.track of 5 steps;
 the converged solve and the 10 control steps with per-trajectory model parameters (model_phys: every parameter of every
 trajectory within 12 % of the model's) next to the same calls without, and with neutral rows (the PHYS kernels on the default
@@ -25,6 +31,38 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "quattro-transformer-ilqr_amd")]
 
 
+def output_hashes(dev):
+    """-> {"quadrotor/euler": sha256, ...}: what a build computes on a small fixed problem per model and integrator."""
+    import hashlib
+
+    import numpy as np
+    import torch
+    from quattro_ilqr_amd import BatchedMPC, models
+    out = {}
+    for model, B, N in (("quadrotor", 5, 26), ("cartpole", 9, 30)):
+        for integ in ("euler", "rk4"):
+            md = models.model_by_name(model, dt=0.01, integrator=integ)
+            rng = np.random.default_rng(B + N + (integ == "rk4"))
+            if model == "quadrotor":
+                x0 = np.asarray(md.x_ref) + rng.uniform(-1, 1, (B, 12)) * np.array([0.5, 0.5, 0.01, 0, 0, 0, 0.2, 0.2, 0.5, 0, 0, 0])
+            else:
+                x0 = np.zeros((B, 4))
+                x0[:, 0], x0[:, 2] = rng.uniform(-0.5, 0.5, B), rng.uniform(-0.5, 0.5, B)
+            x0 = x0.astype(np.float32)
+            dist = torch.as_tensor(1e-3 * rng.standard_normal((3, B, md.n)), dtype=torch.float32, device=dev)
+            mpc = BatchedMPC(md, N, max_iter=100, tol=1e-3, device=dev)
+            sv = mpc.solver
+            h = hashlib.sha256()
+            solved = sv.solve(x0)
+            for t in [solved[k_] for k_ in ("K", "k", "cost", "status")] + [sv.alpha_idx]:
+                h.update(t.cpu().numpy().tobytes())
+            ran = mpc.run(x0, 3, disturbance=dist)
+            for t in [ran[k_] for k_ in ("x", "u", "iters")] + [sv.K, sv.k, sv.cost, sv.alpha_idx, sv.status]:
+                h.update(t.cpu().numpy().tobytes())
+            out[f"{model}/{integ}"] = h.hexdigest()
+    return out
+
+
 def measure(defaults_only):
     import numpy as np
     import torch
@@ -36,7 +74,7 @@ def measure(defaults_only):
     for name in ("quattro_track_f32", "quattro_mpc_run_plant_f32", "quattro_ilqr_solve_phys_f32", "quattro_mpc_run_phys_f32"):
         if not hasattr(raw, name):
             _lib.SIGNATURES.pop(name, None)
-    from quattro_ilqr_amd import BatchedMPC, QuattroILQR, ops, quadrotor_model
+    from quattro_ilqr_amd import BatchedMPC, QuattroILQR, cartpole_model, ops, quadrotor_model
     import bench
     dev, B, N = "cuda:0", 4096, 50
     md = quadrotor_model(dt=0.01, integrator="euler")
@@ -66,6 +104,20 @@ def measure(defaults_only):
         sv.solve(x0, max_iter=20, fixed_iters=True)                  # clocks
     out["solve_default_ms"] = timed(lambda: sv.solve(x0, max_iter=100))
     out["mpc_run_default_10_steps_ms"] = timed(lambda: run(10))
+    # the cart-pole's default forms at BASELINE configs[1]'s shape, as bench.py sets that problem up
+    cp = cartpole_model(dt=0.01, integrator="euler")
+    cx0 = torch.as_tensor(bench.synthetic_cartpole(1024, 0)[0], dtype=torch.float32, device=dev)
+    cp_sv = QuattroILQR(cp, 50, max_iter=100, tol=1e-1, device=dev)
+    cp_mpc = BatchedMPC(cp, 50, max_iter=100, tol=1e-1, device=dev)
+
+    def cp_run(steps):
+        cp_mpc.u_warm = None
+        return cp_mpc.run(cx0, steps)
+
+    out["cartpole_solve_default_ms"] = timed(lambda: cp_sv.solve(cx0, max_iter=100))
+    out["cartpole_mpc_run_default_10_steps_ms"] = timed(lambda: cp_run(10))
+    if defaults_only:
+        out["sha256"] = output_hashes(dev)
     if not defaults_only and new_abi:
         phys = np.tile(np.asarray(md.phys, dtype=np.float32), (B, 1))
         phys[:, 0] *= 1.0 + 0.2 * np.sin(1.0 + np.arange(B))
@@ -109,19 +161,29 @@ def ab(old, rounds):
             else:
                 env.pop("QUATTRO_HIP_LIB", None)
             p = subprocess.run([sys.executable, os.path.abspath(__file__), "--defaults-only"], env=env, capture_output=True,
-                               text=True, timeout=280)
+                               text=True, timeout=400)
             if p.returncode != 0:
                 sys.exit(f"child ({tag}, round {r}) failed with status {p.returncode}:\n{p.stderr[-2000:]}")
             d = json.loads(p.stdout.strip().splitlines()[-1])
             res[tag].append(d)
-            print(f"round {r} {tag}: solve {d['solve_default_ms']:.3f} ms, run(10) {d['mpc_run_default_10_steps_ms']:.3f} ms", flush=True)
+            print(f"round {r} {tag}: solve {d['solve_default_ms']:.3f} ms, run(10) {d['mpc_run_default_10_steps_ms']:.3f} ms; "
+                  f"cart-pole solve {d['cartpole_solve_default_ms']:.3f} ms, run(10) {d['cartpole_mpc_run_default_10_steps_ms']:.3f} ms",
+                  flush=True)
     summary = {}
-    for key in ("solve_default_ms", "mpc_run_default_10_steps_ms"):
+    for key in ("solve_default_ms", "mpc_run_default_10_steps_ms", "cartpole_solve_default_ms", "cartpole_mpc_run_default_10_steps_ms"):
         o, n = np.array([d[key] for d in res["old"]]), np.array([d[key] for d in res["new"]])
         summary[key] = {"old_median": float(np.median(o)), "old_min": float(o.min()), "old_max": float(o.max()),
                         "new_median": float(np.median(n)), "new_min": float(n.min()), "new_max": float(n.max()),
-                        "new_median_within_old_spread": bool(o.min() <= np.median(n) <= o.max())}
+                        "new_median_at_or_below_old_max": bool(np.median(n) <= o.max())}
+    hashes = {tag: [d["sha256"] for d in res[tag]] for tag in res}
+    summary["sha256"] = hashes["new"][0]
+    summary["sha256_equal"] = all(h == hashes["new"][0] for tag in hashes for h in hashes[tag])
     print(json.dumps(summary), flush=True)
+    if not summary["sha256_equal"]:
+        sys.exit(f"the two builds compute different bits: {json.dumps(hashes)}")
+    slow = [key for key, v in summary.items() if isinstance(v, dict) and not v.get("new_median_at_or_below_old_max", True)]
+    if slow:
+        sys.exit(f"slower than the older build's own spread allows: {slow}")
 
 
 if __name__ == "__main__":

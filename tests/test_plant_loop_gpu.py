@@ -3,8 +3,10 @@ ops.track, BatchedMPC.run(plant=, plant_phys=, replan_every=, feedback=)) on the
   1. the tracked steps against the fp64 oracle's closed-loop rollout, one plant per controller;
   2. the persistent loops against the host-driven loop (solve, ops.track, shift), bit for bit;
   3. neutral options through the new kernels against the old path, bit for bit;
-  4. a hybrid controller through the host loop.
+  4. the three C entries of a run, and of a solve, with neutral arguments against each other, bit for bit;
+  5. a hybrid controller through the host loop.
 """
+import ctypes
 import dataclasses
 import os
 
@@ -296,6 +298,79 @@ def test_neutral_plant_options_through_the_new_kernel_equal_the_old_path(model, 
     oc = c.run(x0, steps, disturbance=dist, feedback=True)
     od = q.BatchedMPC(md, N, max_iter=4, tol=1e-3, device=DEV).run(x0, steps, disturbance=dist)
     assert torch.equal(oc["x"], od["x"]) and torch.equal(oc["u"], od["u"])
+
+
+# ------------------------------------------------------------------------------------------------ the entries against each other
+class _LoopState:
+    """Every array a device-resident run reads or writes, freshly zeroed but for the start: three of these, one per C entry, must
+    hold the same bits afterwards."""
+    OUTPUTS = ("x_cur", "x", "u", "K", "k", "cost", "alpha_idx", "active", "iters", "status", "traj_x", "traj_u", "traj_it")
+
+    def __init__(self, md, x0, u0, steps):
+        from quattro_ilqr_amd import ops
+        B, N, n, m = x0.shape[0], u0.shape[1], md.n, md.m
+        z = lambda shape, dtype=torch.float32: torch.zeros(shape, dtype=dtype, device=DEV)
+        self.x0, self.x_cur, self.u = dev32(x0), dev32(x0), dev32(u0)
+        self.x, self.K, self.k = z((B, N + 1, n)), z((B, N, m, n)), z((B, N, m))
+        self.cost = z((B,), torch.float64)
+        self.alpha_idx, self.active, self.iters, self.status = (z((B,), torch.int32) for _ in range(4))
+        self.traj_x, self.traj_u, self.traj_it = z((B, steps + 1, n)), z((B, steps, m)), z((B, steps), torch.int32)
+        self.ws = ops.workspace(md, B, N, DEV)
+
+    def same_as(self, other):
+        return [name for name in self.OUTPUTS if not torch.equal(getattr(self, name), getattr(other, name))]
+
+
+ENTRY_CASES = [("quadrotor", "euler", 3, 6), ("quadrotor", "rk4", 3, 6), ("cartpole", "euler", 5, 3), ("cartpole", "rk4", 5, 3)]
+
+
+@pytest.mark.parametrize("model,integ,B,N", ENTRY_CASES)
+def test_the_three_entries_of_a_run_and_of_a_solve_leave_the_same_bits(model, integ, B, N):
+    """The C entries themselves, below ops: quattro_mpc_run_f32, quattro_mpc_run_plant_f32
+    with the neutral arguments (no plant, no rows, hold 1, no feedback) and quattro_mpc_run_phys_f32 with NULL rows on top run
+    2 control steps of at most 3 iterations with a disturbance; quattro_ilqr_solve_f32, quattro_ilqr_solve_logged_f32 with a NULL
+    log and quattro_ilqr_solve_phys_f32 with NULL rows solve the same start.  Every output of the three must be equal, bit for
+    bit.  B = 3 quadrotors leave a half-empty workgroup, B = 5 cart-poles a wave of four rows and a wave of one."""
+    from quattro_ilqr_amd import _lib, models, ops
+    md = models.model_by_name(model, integrator=integ)
+    lib = _lib.load_for(md)
+    steps, max_iter, tol = 2, 3, 1e-3
+    rng = np.random.default_rng(B + N + (integ == "rk4"))
+    x0, u0 = _start(model, md, B, N, rng)
+    dist = dev32(1e-3 * rng.standard_normal((steps, B, md.n)))
+
+    def run(entry, *extra):
+        t = _LoopState(md, x0, u0, steps)
+        head, keep = ops._mpc_args(md, t.x_cur, t.x, t.u, t.K, t.k, t.cost, tol, max_iter, steps, t.ws, t.traj_x, t.traj_u,
+                                   t.traj_it, dist, ops.ALPHAS, ops.QUU_REG, t.alpha_idx, t.active, t.iters, t.status)
+        assert getattr(lib, entry)(*head, *extra, ops._stream()) == _lib.QUATTRO_OK, entry
+        torch.cuda.synchronize()
+        return t
+
+    plain = run("quattro_mpc_run_f32")
+    assert bool(torch.isfinite(plain.traj_x).all()) and int(plain.traj_it.min()) >= 1      # the run ran
+    assert torch.equal(plain.traj_x[:, 0], plain.x0) and torch.equal(plain.traj_x[:, -1], plain.x_cur)
+    assert not torch.equal(plain.traj_x[:, 1], plain.traj_x[:, 0]) and not torch.equal(plain.u, dev32(u0))
+    assert plain.same_as(run("quattro_mpc_run_plant_f32", None, None, 1, 0)) == []
+    assert plain.same_as(run("quattro_mpc_run_phys_f32", None, None, 1, 0, None)) == []
+
+    def solve(entry, *extra):
+        t = _LoopState(md, x0, u0, steps)
+        arr, na = ops._alphas(ops.ALPHAS)
+        p = md.c_params()
+        flags = _lib.SOLVE_SIMULATE | _lib.SOLVE_RESET
+        rc = getattr(lib, entry)(ctypes.byref(p), ops._ptr(t.x0), ops._ptr(t.x), ops._ptr(t.u), B, N, ops.QUU_REG, arr, na, tol,
+                                 max_iter, flags, ops._ptr(t.K), ops._ptr(t.k), ops._ptr(t.cost), ops._ptr(t.alpha_idx),
+                                 ops._ptr(t.active), ops._ptr(t.iters), ops._ptr(t.status), ops._ptr(t.ws),
+                                 t.ws.numel() * t.ws.element_size(), *extra, ops._stream())
+        assert rc == _lib.QUATTRO_OK, entry
+        torch.cuda.synchronize()
+        return t
+
+    plain = solve("quattro_ilqr_solve_f32")
+    assert bool(torch.isfinite(plain.K).all()) and int(plain.iters.min()) >= 1 and float(plain.cost.min()) > 0.0
+    assert plain.same_as(solve("quattro_ilqr_solve_logged_f32", None)) == []
+    assert plain.same_as(solve("quattro_ilqr_solve_phys_f32", None, None)) == []
 
 
 # ------------------------------------------------------------------------------------------------ hybrid controller
