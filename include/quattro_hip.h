@@ -403,7 +403,8 @@ int quattro_mpc_run_plant_f32(const quattro_model_params* p, float* x_cur, float
  *                        (quattro_model_has_device_loop(p) == 0), QUATTRO_ERR_BAD_ARG for QUATTRO_SOLVE_ENQUEUE together with
  *                        model_phys; every other argument is checked as by the entry each extends.
  * The stand-alone entries (quattro_simulate_f32, quattro_linearize*_f32, quattro_rollout_f32, quattro_linesearch_f32,
- * quattro_ilqr_iterate_f32, quattro_track_f32) and the other fields of p (cost, dt, integrator) have no per-trajectory form. */
+ * quattro_ilqr_iterate_f32, quattro_track_f32) and the other fields of p (cost, dt, integrator) have no per-trajectory form
+ * (x_ref has one of its own: REFERENCE ROWS below). */
 int quattro_ilqr_solve_phys_f32(const quattro_model_params* p, const float* x0, float* x_nom, float* u_nom, int B, int N,
                                 float reg, const float* alphas, int n_alpha, double tol, int max_iter, int flags, float* K,
                                 float* k, double* cost, int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status,
@@ -415,6 +416,46 @@ int quattro_mpc_run_phys_f32(const quattro_model_params* p, float* x_cur, float*
                              int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status, void* workspace,
                              size_t workspace_bytes, const quattro_model_params* plant, const float* plant_phys, int hold,
                              int feedback, const float* model_phys, void* stream);
+
+/* REFERENCE ROWS: per-trajectory, per-step state targets.  The cost is otherwise taken against the one p->x_ref of the batch, constant
+ * over the horizon and over a closed-loop run.  x_ref_rows [B][ref_rows][n] (device, fp32, 16-byte aligned, ref_rows >= 1) lifts that:
+ * for trajectory (controller) b a row of it replaces p->x_ref wherever the cost is evaluated — stage cost and total cost of the
+ * nominal rollout and of every line-search rollout, l_x of the linearisation, and the terminal gradient V_x(N).  l_xx, V_xx(N), q,
+ * qf, r, the barrier, dt and the integrator stay shared; p->x_ref is ignored.  A user-compiled model's stage_cost / final_cost see
+ * the row as p.x_ref.  Which row, with R = ref_rows:
+ *   plain solve : horizon step t in [0, N] (t = N: the terminal cost) reads row min(t, R - 1);
+ *   closed loop : plan c starts at plant step s = c * hold; horizon step t of that plan reads row min(s + preview * t, R - 1),
+ *                 preview in {0, 1}.
+ * Running past the last row holds the last row.  R = 1: every trajectory its own constant goal.  preview = 0, R = n_steps: a
+ * set-point schedule as the reference's simulator drives one (examples/quadrotor/quadrotor_sim.py:135-145 moves mpc_controller.x_ref
+ * between control steps: known at replan time only, constant inside a solve).  preview = 1, R >= n_steps + N + 1: tracking along a
+ * sliding window of a path — nothing is shifted or copied, only the offset moves.  The tracked steps between solves (hold,
+ * feedback) follow x_nom, u_nom and K as ever; they have no cost and read no rows.
+ *
+ * quattro_ilqr_solve_ref_f32: the arguments of quattro_ilqr_solve_phys_f32 in their order (log ring and model_phys as there), then
+ * x_ref_rows, ref_rows.  quattro_mpc_run_ref_f32: the arguments of quattro_mpc_run_phys_f32 in their order up to model_phys, then
+ * x_ref_rows, ref_rows, preview.  Rows work with and without model_phys, with and without a plant.
+ *   x_ref_rows == NULL : exactly the entry each extends (the same call, the same kernels, the same results); ref_rows and preview
+ *                        are not looked at.
+ *   x_ref_rows != NULL : always the model's persistent kernel (csrc/solve_*.hip, their REF instantiations), as with model_phys.
+ *                        Before any launch: QUATTRO_ERR_UNSUPPORTED for a model without one, QUATTRO_ERR_BAD_ARG for ref_rows < 1 or
+ *                        > 2^20 (the kernels address the rows with 32-bit byte offsets), preview outside {0, 1}, or
+ *                        QUATTRO_SOLVE_ENQUEUE together with rows; every other argument is checked as by the entry each extends.
+ * The library still allocates nothing and quattro_model_workspace_bytes keeps its values.  The stand-alone entries
+ * (quattro_simulate_f32, quattro_linearize*_f32, quattro_rollout_f32, quattro_linesearch_f32, quattro_ilqr_iterate_f32,
+ * quattro_track_f32) have no row form, and neither have the cost weights. */
+int quattro_ilqr_solve_ref_f32(const quattro_model_params* p, const float* x0, float* x_nom, float* u_nom, int B, int N,
+                               float reg, const float* alphas, int n_alpha, double tol, int max_iter, int flags, float* K,
+                               float* k, double* cost, int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status,
+                               void* workspace, size_t workspace_bytes, const quattro_solve_log* log, const float* model_phys,
+                               const float* x_ref_rows, int ref_rows, void* stream);
+int quattro_mpc_run_ref_f32(const quattro_model_params* p, float* x_cur, float* x_nom, float* u_nom, int B, int N, float reg,
+                            const float* alphas, int n_alpha, double tol, int max_iter, int n_steps, float* traj_x,
+                            float* traj_u, int32_t* traj_iters, const float* disturbance, float* K, float* k, double* cost,
+                            int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status, void* workspace,
+                            size_t workspace_bytes, const quattro_model_params* plant, const float* plant_phys, int hold,
+                            int feedback, const float* model_phys, const float* x_ref_rows, int ref_rows, int preview,
+                            void* stream);
 
 /* Transformer gain predictor: weights of the reference's TransformerPredictor (quattro_ilqr_tf/transformer_model.py:85-138)
  * as DEVICE pointers, plus the DataNormalizer vectors (:15-50).  Matrices are PyTorch Linear layout [out][in];

@@ -497,16 +497,22 @@ int quattro_ilqr_solve_logged_f32(const quattro_model_params* p, const float* x0
   return QUATTRO_OK;
 }
 
-int quattro_ilqr_solve_phys_f32(const quattro_model_params* p, const float* x0, float* x_nom, float* u_nom, int B, int N,
-                                float reg, const float* alphas, int n_alpha, double tol, int max_iter, int flags, float* K,
-                                float* k, double* cost, int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status,
-                                void* workspace, size_t workspace_bytes, const quattro_solve_log* log, const float* model_phys,
-                                void* stream) {
-  if (model_phys == nullptr)
-    return quattro_ilqr_solve_logged_f32(p, x0, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, flags, K, k, cost,
-                                         alpha_idx, active, iters, status, workspace, workspace_bytes, log, stream);
-  // the logged entry's checks in its order, then the two refusals of this one: the rows are read by the persistent kernels alone
-  const bool args_ok = iters && max_iter >= 0 && !((flags & QUATTRO_SOLVE_SIMULATE) && !x0) && log_ok(log);
+namespace {
+// reference rows are addressed with 32-bit byte offsets (rollout_quad_body.h: RefSrc, 16 trajectories of rows per resource)
+constexpr int MAX_REF_ROWS = 1 << 20;
+bool ref_ok(const float* x_ref_rows, int ref_rows, int preview) {
+  return x_ref_rows == nullptr || (ref_rows >= 1 && ref_rows <= MAX_REF_ROWS && (preview == 0 || preview == 1));
+}
+}  // namespace
+
+// quattro_ilqr_solve_phys_f32 and quattro_ilqr_solve_ref_f32 with at least one of their arrays: always the persistent kernel
+static int solve_rows(const quattro_model_params* p, const float* x0, float* x_nom, float* u_nom, int B, int N, float reg,
+                      const float* alphas, int n_alpha, double tol, int max_iter, int flags, float* K, float* k, double* cost,
+                      int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status, void* workspace, size_t workspace_bytes,
+                      const quattro_solve_log* log, const float* model_phys, const float* x_ref_rows, int ref_rows, void* stream) {
+  // the logged entry's checks in its order, then the refusals of these two: the rows are read by the persistent kernels alone
+  const bool args_ok = iters && max_iter >= 0 && !((flags & QUATTRO_SOLVE_SIMULATE) && !x0) && log_ok(log) &&
+                       ref_ok(x_ref_rows, ref_rows, 1);
   int entry_rc = QUATTRO_ERR_BAD_ARG;
   if (args_ok && !(flags & QUATTRO_SOLVE_ENQUEUE)) entry_rc = quattro_model_has_device_loop(p) ? QUATTRO_OK : QUATTRO_ERR_UNSUPPORTED;
   WorkspacePlan w;
@@ -517,7 +523,34 @@ int quattro_ilqr_solve_phys_f32(const quattro_model_params* p, const float* x0, 
   SolveLoop loop = solve_loop(*p, x0, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, flags, K, k, cost, alpha_idx, active,
                               iters, status, log);
   loop.model_phys = model_phys;
+  loop.x_ref_rows = x_ref_rows;      // (a plain solve is one plan from step 0 that looks ahead: row min(t, ref_rows - 1))
+  loop.ref_rows = ref_rows;
+  loop.preview = 1;
   return launch_device_loop(*p, loop, w, (char*)workspace, (hipStream_t)stream);
+}
+
+int quattro_ilqr_solve_phys_f32(const quattro_model_params* p, const float* x0, float* x_nom, float* u_nom, int B, int N,
+                                float reg, const float* alphas, int n_alpha, double tol, int max_iter, int flags, float* K,
+                                float* k, double* cost, int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status,
+                                void* workspace, size_t workspace_bytes, const quattro_solve_log* log, const float* model_phys,
+                                void* stream) {
+  if (model_phys == nullptr)
+    return quattro_ilqr_solve_logged_f32(p, x0, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, flags, K, k, cost,
+                                         alpha_idx, active, iters, status, workspace, workspace_bytes, log, stream);
+  return solve_rows(p, x0, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, flags, K, k, cost, alpha_idx, active, iters,
+                    status, workspace, workspace_bytes, log, model_phys, nullptr, 0, stream);
+}
+
+int quattro_ilqr_solve_ref_f32(const quattro_model_params* p, const float* x0, float* x_nom, float* u_nom, int B, int N,
+                               float reg, const float* alphas, int n_alpha, double tol, int max_iter, int flags, float* K,
+                               float* k, double* cost, int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status,
+                               void* workspace, size_t workspace_bytes, const quattro_solve_log* log, const float* model_phys,
+                               const float* x_ref_rows, int ref_rows, void* stream) {
+  if (x_ref_rows == nullptr)
+    return quattro_ilqr_solve_phys_f32(p, x0, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, flags, K, k, cost,
+                                       alpha_idx, active, iters, status, workspace, workspace_bytes, log, model_phys, stream);
+  return solve_rows(p, x0, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, flags, K, k, cost, alpha_idx, active, iters,
+                    status, workspace, workspace_bytes, log, model_phys, x_ref_rows, ref_rows, stream);
 }
 
 int quattro_ilqr_solve_f32(const quattro_model_params* p, const float* x0, float* x_nom, float* u_nom, int B, int N,
@@ -551,15 +584,16 @@ int quattro_mpc_run_f32(const quattro_model_params* p, float* x_cur, float* x_no
   return launch_device_loop(*p, loop, w, (char*)workspace, (hipStream_t)stream);
 }
 
-// quattro_mpc_run_plant_f32 (model_phys == NULL: the run as it always was) and quattro_mpc_run_phys_f32
+// quattro_mpc_run_plant_f32 (model_phys == NULL, x_ref_rows == NULL: the run as it always was), quattro_mpc_run_phys_f32 and
+// quattro_mpc_run_ref_f32
 static int mpc_run_plant(const quattro_model_params* p, float* x_cur, float* x_nom, float* u_nom, int B, int N, float reg,
                          const float* alphas, int n_alpha, double tol, int max_iter, int n_steps, float* traj_x, float* traj_u,
                          int32_t* traj_iters, const float* disturbance, float* K, float* k, double* cost, int32_t* alpha_idx,
                          int32_t* active, int32_t* iters, int32_t* status, void* workspace, size_t workspace_bytes,
                          const quattro_model_params* plant, const float* plant_phys, int hold, int feedback,
-                         const float* model_phys, void* stream) {
+                         const float* model_phys, const float* x_ref_rows, int ref_rows, int preview, void* stream) {
   const bool args_ok = x_cur && iters && traj_x && traj_u && traj_iters && max_iter >= 0 && n_steps > 0 && hold >= 1 && hold <= N &&
-                       n_steps % hold == 0 && !(feedback && max_iter < 1);
+                       n_steps % hold == 0 && !(feedback && max_iter < 1) && ref_ok(x_ref_rows, ref_rows, preview);
   PlantSpec ps{};
   int entry_rc = QUATTRO_ERR_BAD_ARG;
   if (args_ok && model_ok(p)) {
@@ -586,6 +620,9 @@ static int mpc_run_plant(const quattro_model_params* p, float* x_cur, float* x_n
   // the default plant is the controller's own model: with a model of its own per controller, that controller's row (the plant's
   // integrator is p's then: plant_spec)
   if (model_phys != nullptr && plant == nullptr && plant_phys == nullptr) loop.plant_phys = model_phys;
+  loop.x_ref_rows = x_ref_rows;
+  loop.ref_rows = ref_rows;
+  loop.preview = preview;
   return launch_device_loop(*p, loop, w, (char*)workspace, (hipStream_t)stream);
 }
 
@@ -597,7 +634,7 @@ int quattro_mpc_run_plant_f32(const quattro_model_params* p, float* x_cur, float
                               int feedback, void* stream) {
   return mpc_run_plant(p, x_cur, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, n_steps, traj_x, traj_u, traj_iters,
                        disturbance, K, k, cost, alpha_idx, active, iters, status, workspace, workspace_bytes, plant, plant_phys, hold,
-                       feedback, nullptr, stream);
+                       feedback, nullptr, nullptr, 0, 0, stream);
 }
 
 int quattro_mpc_run_phys_f32(const quattro_model_params* p, float* x_cur, float* x_nom, float* u_nom, int B, int N, float reg,
@@ -612,7 +649,23 @@ int quattro_mpc_run_phys_f32(const quattro_model_params* p, float* x_cur, float*
                                      workspace_bytes, plant, plant_phys, hold, feedback, stream);
   return mpc_run_plant(p, x_cur, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, n_steps, traj_x, traj_u, traj_iters,
                        disturbance, K, k, cost, alpha_idx, active, iters, status, workspace, workspace_bytes, plant, plant_phys, hold,
-                       feedback, model_phys, stream);
+                       feedback, model_phys, nullptr, 0, 0, stream);
+}
+
+int quattro_mpc_run_ref_f32(const quattro_model_params* p, float* x_cur, float* x_nom, float* u_nom, int B, int N, float reg,
+                            const float* alphas, int n_alpha, double tol, int max_iter, int n_steps, float* traj_x,
+                            float* traj_u, int32_t* traj_iters, const float* disturbance, float* K, float* k, double* cost,
+                            int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status, void* workspace,
+                            size_t workspace_bytes, const quattro_model_params* plant, const float* plant_phys, int hold,
+                            int feedback, const float* model_phys, const float* x_ref_rows, int ref_rows, int preview,
+                            void* stream) {
+  if (x_ref_rows == nullptr)
+    return quattro_mpc_run_phys_f32(p, x_cur, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, n_steps, traj_x, traj_u,
+                                    traj_iters, disturbance, K, k, cost, alpha_idx, active, iters, status, workspace,
+                                    workspace_bytes, plant, plant_phys, hold, feedback, model_phys, stream);
+  return mpc_run_plant(p, x_cur, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, n_steps, traj_x, traj_u, traj_iters,
+                       disturbance, K, k, cost, alpha_idx, active, iters, status, workspace, workspace_bytes, plant, plant_phys, hold,
+                       feedback, model_phys, x_ref_rows, ref_rows, preview, stream);
 }
 
 int quattro_track_f32(const quattro_model_params* p, const quattro_model_params* plant, const float* plant_phys, const float* x0,

@@ -121,13 +121,15 @@ struct LaneRec {
 // OWN (the persistent loop with per-trajectory parameters): p is this row's private block — the kernel's with the row's phys — and
 // `shared` the kernel-argument block it was copied from.  The one lane-indexed read of the sweep (the terminal weight qf[i]) goes
 // to `shared`, whose cost fields are the same: a private block indexed by lane is kept whole in scratch memory (292 B per lane).
-template <bool RK4, bool OWN = false>
+// ref(t): called by the lane that is about to form the record of step t, and by every lane before the terminal pair (t = N) — the
+// persistent loop with reference rows puts the step's row into the private block (solve_loop.h: set_ref_row); NoRef: nothing.
+template <bool RK4, bool OWN = false, class Ref = NoRef>
 __device__ __forceinline__ void sweep16_cartpole_body(const quattro_model_params& p, const float* __restrict__ x,
                                                       const float* __restrict__ u, int N, int t_start, float reg,
                                                       float* __restrict__ Kout, float* __restrict__ kout,
                                                       int32_t* __restrict__ status, const int b, const bool live,
                                                       const int lane, float* stage, const int k_rows = 0,
-                                                      const quattro_model_params* shared = nullptr) {
+                                                      const quattro_model_params* shared = nullptr, Ref ref = Ref()) {
   using namespace cp16;
   constexpr int NX = 4;
   const int sub = lane & 15, i = sub >> 2, j = sub & 3, row0 = lane & 48;
@@ -146,6 +148,7 @@ __device__ __forceinline__ void sweep16_cartpole_body(const quattro_model_params
   {
     const float4 xN = px[N];
     const float xn[NX] = {xN.x, xN.y, xN.z, xN.w};
+    ref(N);
 #pragma unroll
     for (int c = 0; c < NX; ++c) vx[c] = qt_terminal_vx(p, c, xn[c]);
     if constexpr (OWN) Vij = (i == j) ? qt_terminal_vxx(*shared, i) : 0.0f;
@@ -208,6 +211,7 @@ __device__ __forceinline__ void sweep16_cartpole_body(const quattro_model_params
       const float xs[4] = {xq.x, xq.y, xq.z, xq.w};
       const float us[1] = {pu[t]};
       float rec[RS];
+      ref(t);
       cartpole_record<RK4>(p, xs, us, rec);
       float4* dst = reinterpret_cast<float4*>(stage + ls * RS);
 #pragma unroll

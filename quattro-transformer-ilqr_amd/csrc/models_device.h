@@ -408,10 +408,15 @@ struct EulerRecord<QUATTRO_MODEL_QUADROTOR, L> {
     rec[L::a(11, 9)] = dt * c3 * wq;
     rec[L::a(11, 10)] = dt * c3 * wp;
   }
+  // (`xr`: the reference this step's cost is taken against -- p.x_ref, or the step's row of reference rows the caller holds as
+  //  values (solve_loop.h: x_ref_rows); the three-argument form is the shared-reference case)
   static __device__ __forceinline__ void fill_lx(float* rec, const quattro_model_params& p, const float* x) {
+    fill_lx(rec, p, p.x_ref, x);
+  }
+  static __device__ __forceinline__ void fill_lx(float* rec, const quattro_model_params& p, const float* xr, const float* x) {
 #pragma clang fp contract(off)
 #pragma unroll
-    for (int i = 0; i < 12; ++i) rec[L::lx(i)] = 2.0f * p.q[i] * (x[i] - p.x_ref[i]);
+    for (int i = 0; i < 12; ++i) rec[L::lx(i)] = 2.0f * p.q[i] * (x[i] - xr[i]);
   }
   static __device__ __forceinline__ void fill_control(float* rec, const quattro_model_params& p, int a, float ra, float ua) {
     float lu, luu;

@@ -172,6 +172,23 @@ struct PlantSpec {
   float phys[8];
 };
 
+// Reference rows (quattro_ilqr_solve_ref_f32, quattro_mpc_run_ref_f32; the REF instantiations of the persistent kernels): a device
+// array x_ref_rows [B][R][n] whose rows replace the parameter block's x_ref wherever the cost of trajectory b is evaluated.  What a
+// phase of a kernel holds of it: the array, its row count, the plant step `s` at which the current plan starts (0 in a plain solve)
+// and `preview` (1 in a plain solve).  THE row rule, stated once: horizon step t (t = N: the terminal cost) reads row
+// min(s + preview * t, R - 1) — running past the last row holds the last row.
+struct RefRows {
+  const float* rows;
+  int R, s, preview;
+};
+__device__ __forceinline__ int qt_ref_row(const RefRows& rr, int t) {
+  const int i = rr.s + rr.preview * t;
+  return i < rr.R - 1 ? i : rr.R - 1;
+}
+struct NoRef {        // the bodies' hook "the cost of step t is about to be evaluated" where there are no rows: nothing
+  __device__ __forceinline__ void operator()(int) const {}
+};
+
 // the step sizes of a line search, by value (a kernel argument)
 namespace {
 struct AlphaList {

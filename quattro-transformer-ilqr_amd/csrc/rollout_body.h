@@ -81,10 +81,12 @@ struct ScratchStore {  // packed candidate records [t][cand_stride]
 
 // One closed-loop rollout: u'_t = u_t + alpha (k_t + K_t (x'_t - x_t)), x'_{t+1} = f(x'_t, u'_t), x'_0 = x_0.
 // Returns sum_t L(x'_t, u'_t) + Lf(x'_N).
-template <int MODEL, bool RK4, class Store>
+// ref(t): called before the cost of step t (t = N: the terminal cost) is evaluated — the persistent loops with reference rows put
+// the step's row into the block p refers to (solve_loop.h: set_ref_row); NoRef: nothing.
+template <int MODEL, bool RK4, class Store, class Ref = NoRef>
 __device__ __forceinline__ double rollout_closed(const quattro_model_params& p, const float* __restrict__ xnom,
                                                  const float* __restrict__ unom, const float* __restrict__ Kb,
-                                                 const float* __restrict__ kb, float alpha, int N, Store store) {
+                                                 const float* __restrict__ kb, float alpha, int N, Store store, Ref ref = Ref()) {
   constexpr int NX = ModelDims<MODEL>::NX, NU = ModelDims<MODEL>::NU;
   NomStep<MODEL> b0, b1;
   b0.load(xnom, unom, Kb, kb, 0);
@@ -102,6 +104,7 @@ __device__ __forceinline__ double rollout_closed(const quattro_model_params& p, 
       for (int i = 0; i < NX; ++i) du = fmaf(nb.K[a * NX + i], xh[i] - nb.x[i], du);
       uh[a] = fmaf(alpha, du, nb.u[a]);
     }
+    ref(t);
     J += (double)qt_stage_cost<MODEL>(p, xh, uh);
     float xnext[NX];
     qt_step<MODEL, RK4>(p, xh, uh, xnext);
@@ -117,15 +120,16 @@ __device__ __forceinline__ double rollout_closed(const quattro_model_params& p, 
     b1.load(xnom, unom, Kb, kb, t + 3 < N ? t + 3 : N - 1);
   }
   if (t < N) step(b0, t);
+  ref(N);
   J += (double)qt_final_cost<MODEL>(p, xh);
   return J;
 }
 
-// open-loop rollout + cost of trajectory b by ONE lane (the caller masks lanes without a trajectory)
-template <int MODEL, bool RK4>
+// open-loop rollout + cost of trajectory b by ONE lane (the caller masks lanes without a trajectory); ref: as in rollout_closed
+template <int MODEL, bool RK4, class Ref = NoRef>
 __device__ __forceinline__ void simulate_body(const quattro_model_params& p, const float* __restrict__ x0,
                                               const float* __restrict__ u, int N, float* __restrict__ x,
-                                              double* __restrict__ cost, const int b) {
+                                              double* __restrict__ cost, const int b, Ref ref = Ref()) {
   constexpr int NX = ModelDims<MODEL>::NX, NU = ModelDims<MODEL>::NU;
   float xh[NX];
   load_vec<NX>(x0 + (size_t)b * NX, xh);
@@ -138,6 +142,7 @@ __device__ __forceinline__ void simulate_body(const quattro_model_params& p, con
   load_vec<NU>(ub + (size_t)(N > 1 ? 1 : 0) * NU, u1);
   auto step = [&](const float* ut, int t) __attribute__((always_inline)) {
     float xn[NX];
+    ref(t);
     J += (double)qt_stage_cost<MODEL>(p, xh, ut);
     qt_step<MODEL, RK4>(p, xh, ut, xn);
     store_vec<NX>(xo + (size_t)(t + 1) * NX, xn);
@@ -152,6 +157,7 @@ __device__ __forceinline__ void simulate_body(const quattro_model_params& p, con
     load_vec<NU>(ub + (size_t)(t + 3 < N ? t + 3 : N - 1) * NU, u1);
   }
   if (t < N) step(u0, t);
+  ref(N);
   J += (double)qt_final_cost<MODEL>(p, xh);
   if (cost != nullptr) cost[b] = J;
 }
@@ -225,12 +231,13 @@ __device__ __forceinline__ void track_plan(const quattro_model_params& p, const 
 // loop, whose sweep owns a 16-lane row per trajectory, 64 inside a user model's, whose sweep owns the wave), lane ai < n_alpha <= 8 of them rolls candidate ai out.  Every candidate
 // leaves its (x', u') in the scratch; after the ballot the trajectory's LPT lanes copy the accepted candidate over the nominal.
 // `gid` = LPT * trajectory + lane-in-trajectory; `force` treats every trajectory as active whatever its flag says.
-template <int MODEL, bool RK4, int LPT>
+// ref: handed to every candidate's rollout_closed.
+template <int MODEL, bool RK4, int LPT, class Ref = NoRef>
 __device__ __forceinline__ void linesearch_body(const quattro_model_params& p, float* x_nom, float* u_nom,
                                                 const float* __restrict__ K, const float* __restrict__ k,
                                                 const AlphaList& al, int n_alpha, int B, int N, double tol, double* cost,
                                                 int32_t* __restrict__ alpha_idx, int32_t* active, int32_t* iters,
-                                                float* __restrict__ scratch, const int gid, const bool force) {
+                                                float* __restrict__ scratch, const int gid, const bool force, Ref ref = Ref()) {
   constexpr int NX = ModelDims<MODEL>::NX, NU = ModelDims<MODEL>::NU, CS = cand_stride<MODEL>();
   static_assert(LPT == 8 || LPT == 16 || LPT == 64, "8, 16 or 64 lanes per trajectory");
   const int b = gid / LPT, ai = gid % LPT;
@@ -246,7 +253,7 @@ __device__ __forceinline__ void linesearch_body(const quattro_model_params& p, f
   double J = 0.0;
   bool ok = false;
   if (mine) {
-    J = rollout_closed<MODEL, RK4>(p, xn, un, Kb, kb, al.a[ai & 7], N, ScratchStore<MODEL>{sc + (size_t)ai * N * CS});
+    J = rollout_closed<MODEL, RK4>(p, xn, un, Kb, kb, al.a[ai & 7], N, ScratchStore<MODEL>{sc + (size_t)ai * N * CS}, ref);
     ok = (J <= J0);   // false for NaN, like the reference's comparison
   }
   // first accepted alpha inside this trajectory's 8-lane group

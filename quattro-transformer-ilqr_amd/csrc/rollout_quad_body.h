@@ -2,6 +2,8 @@
 // by rollout_quad.hip (one launch per call) and solve_quad.hip (the device-resident solve loop).  Design notes:
 // rollout_quad.hip.
 #pragma once
+#include <type_traits>
+
 #include "models_device.h"
 
 namespace {
@@ -283,6 +285,50 @@ struct NomLane {
   }
 };
 
+// REF (quattro_ilqr_solve_ref_f32, quattro_mpc_run_ref_f32): LaneConst::xr becomes a value of the STEP.  Where the rows of a wave's
+// trajectories live, NomSrc's way: one wave-uniform buffer resource over the rows of the wave's trajectories ([nwt][R][12] from
+// trajectory wb on), this lane's loop-invariant byte offset (its trajectory, its axis), and the step's row — qt_ref_row, the
+// clamp — as a SCALAR offset.  (Offsets are 32-bit: the C entries bound R.)
+struct NoRefSrc {
+  static constexpr bool ON = false;
+  __device__ __forceinline__ NoRefSrc() {}
+  __device__ __forceinline__ NoRefSrc(const LaneConst&, const RefRows&, int, int, int) {}
+};
+struct RefSrc {
+  static constexpr bool ON = true;
+  __amdgpu_buffer_rsrc_t r;
+  int v;
+  RefRows rr;
+  __device__ __forceinline__ RefSrc(const LaneConst& L, const RefRows& rr_, int wb, int li, int nwt) : rr(rr_) {
+    r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(rr_.rows) + (size_t)wb * rr_.R * NX, 0, nwt * rr_.R * NX * 4, 0x00020000);
+    v = 4 * (li * rr_.R * NX + L.a);
+  }
+};
+// this lane's four components (a, 3 + a, 6 + a, 9 + a) of the row that horizon step t reads; every quad of a trajectory — all
+// candidates of a line search — loads the same four
+struct RefLane {
+  float xr[4];
+  __device__ __forceinline__ void load(const RefSrc& s, int t) {
+    const int row = qt_ref_row(s.rr, t);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) xr[g] = __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(s.r, s.v + 12 * g, row * (NX * 4), 0));
+  }
+  __device__ __forceinline__ void load(const NoRefSrc&, int) {}
+};
+// L with the step's reference in place of the problem's: a copy in registers, so that lane_stage_cost / lane_final_cost (and with
+// them every kernel without rows) stay as they are
+template <class RefS>
+__device__ __forceinline__ LaneConst with_ref(const LaneConst& L, const RefLane& rl) {
+  if constexpr (RefS::ON) {
+    LaneConst Lt = L;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) Lt.xr[g] = rl.xr[g];
+    return Lt;
+  } else {
+    return L;
+  }
+}
+
 // Stores.  One 16-byte store per lane per step: the x' row (12 floats, state 3g+a in lane a / register g) is transposed
 // inside the quad so that lane j < 3 holds x'[4j .. 4j+3] and lane 3 holds (u'_0..u'_3).  Per-state dword stores were
 // 5 requests of 12-16 bytes per quad and step; at 2048 waves that request rate, not bandwidth, cost 45 us per line
@@ -390,9 +436,12 @@ __device__ __forceinline__ void quad_track_body(const LaneConst& L, const bool r
 // One closed-loop rollout by a quad.  Returns this LANE's partial of sum_t L + Lf (fp64); quad_sum() gives the total.
 // PRIO: the state recurrence of a step at wave priority 1, the stage cost, the store and the loads that hang off it at 0
 // (rollout_quad.hip); without it the step runs at the caller's priority throughout and adds its stage cost ahead of the rate function.
-template <bool RK4, int PF, bool PRIO, class Store>
+// RefS = RefSrc: stage and terminal cost against the step's row.  The row's four floats are requested with the step's nominal data,
+// PF steps ahead, and the terminal row before the loop: the cost is not on the recurrence, and neither are its loads.
+template <bool RK4, int PF, bool PRIO, class Store, class RefS = NoRefSrc>
 __device__ __forceinline__ double quad_rollout_closed(const quattro_model_params& p, const LaneConst& L,
-                                                      const NomSrc& src, float alpha, int N, bool counted, Store store) {
+                                                      const NomSrc& src, float alpha, int N, bool counted, Store store,
+                                                      const RefS& ref = RefS()) {
   // nominal data is requested PF steps ahead (PF register buffers, loop unrolled by PF): the loads come from HBM / the
   // far cache (K was written by the sweep, 39 MB per 4096 trajectories) and a step is only ~0.5 us of issue.  PF = 4 in
   // the stand-alone kernels; 2 inside the device-resident solve loop, where the gains were written by the same workgroup a
@@ -401,24 +450,28 @@ __device__ __forceinline__ double quad_rollout_closed(const quattro_model_params
   NomLane nb[PF];
 #pragma unroll
   for (int d = 0; d < PF; ++d) nb[d].load(src, d < N ? d : N - 1);
+  RefLane rl[PF], rlN;
+#pragma unroll
+  for (int d = 0; d < PF; ++d) rl[d].load(ref, d < N ? d : N - 1);
+  rlN.load(ref, N);
   float xh[4];
 #pragma unroll
   for (int g = 0; g < 4; ++g) xh[g] = nb[0].x[g];
   double J = 0.0;
-  auto step = [&](const NomLane& b, int t) __attribute__((always_inline)) {
+  auto step = [&](const NomLane& b, const RefLane& rt, int t) __attribute__((always_inline)) {
     if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
     float dx[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) dx[g] = xh[g] - b.x[g];
     const float du = gain_dot(b.K, dx, b.k);
     const float uh = fmaf(alpha, du, b.u);
-    if constexpr (!PRIO) J += (double)lane_stage_cost(p, L, xh, uh, counted_mask);
+    if constexpr (!PRIO) J += (double)lane_stage_cost(p, with_ref<RefS>(L, rt), xh, uh, counted_mask);
     float xnext[4];
     const QuadU U(uh);
     quad_step<RK4>(L, xh, U, xnext);
     if constexpr (PRIO) {
       __builtin_amdgcn_s_setprio(0);
-      J += (double)lane_stage_cost(p, L, xh, uh, counted_mask);
+      J += (double)lane_stage_cost(p, with_ref<RefS>(L, rt), xh, uh, counted_mask);
     }
     store(L, t, U, xnext);
 #pragma unroll
@@ -428,14 +481,15 @@ __device__ __forceinline__ double quad_rollout_closed(const quattro_model_params
   for (; t + PF <= N; t += PF) {
 #pragma unroll
     for (int d = 0; d < PF; ++d) {
-      step(nb[d], t + d);
+      step(nb[d], rl[d], t + d);
       nb[d].load(src, t + d + PF < N ? t + d + PF : N - 1);
+      rl[d].load(ref, t + d + PF < N ? t + d + PF : N - 1);
     }
   }
 #pragma unroll
   for (int d = 0; d < PF - 1; ++d)
-    if (t + d < N) step(nb[d], t + d);          // wave-uniform tail (N % PF steps)
-  J += (double)lane_final_cost(L, xh);
+    if (t + d < N) step(nb[d], rl[d], t + d);          // wave-uniform tail (N % PF steps)
+  J += (double)lane_final_cost(with_ref<RefS>(L, rlN), xh);
   return J;
 }
 
@@ -443,11 +497,13 @@ __device__ __forceinline__ double quad_rollout_closed(const quattro_model_params
 // `gid` = 4 * trajectory + lane-in-quad; `live` = this quad has a trajectory to roll out (idle quads run along on
 // trajectory 0 without storing: the DPP exchanges and the wave-uniform barrier shortcut need every quad on the same path)
 // PHYS: the quad's physical parameters are row b of model_phys (lane_const_phys); the cost stays p's
-template <bool RK4, bool PHYS = false>
+// REF: the cost of step t against the row of rr that step reads (RefSrc), prefetched with the controls, two steps ahead
+template <bool RK4, bool PHYS = false, bool REF = false>
 __device__ __forceinline__ void simulate_quad_body(const quattro_model_params& p, const float* __restrict__ x0,
                                                    const float* __restrict__ u, int N, float* __restrict__ x,
                                                    double* __restrict__ cost, const int gid, const bool live,
-                                                   const float* __restrict__ model_phys = nullptr) {
+                                                   const float* __restrict__ model_phys = nullptr, const RefRows& rr = RefRows{}) {
+  using RefS = std::conditional_t<REF, RefSrc, NoRefSrc>;
   const int b = gid >> 2;
   const size_t bb = live ? b : 0;
   const LaneConst L = lane_const_of<PHYS>(p, model_phys, bb, gid & 3);
@@ -465,11 +521,16 @@ __device__ __forceinline__ void simulate_quad_body(const quattro_model_params& p
 #pragma unroll
     for (int g = 0; g < 4; ++g) xo[3 * g] = xh[g];
   }
+  const RefS ref(L, rr, bw, live ? b - bw : 0, 16);
+  RefLane r0, r1, rN;
+  r0.load(ref, 0);
+  r1.load(ref, N > 1 ? 1 : 0);
+  rN.load(ref, N);
   double J = 0.0;
   const unsigned long long live_mask = __builtin_amdgcn_ballot_w64(live);
   float u0 = ub[0], u1 = ub[(size_t)(N > 1 ? 1 : 0) * NU];
-  auto step = [&](float ut, int t) __attribute__((always_inline)) {
-    J += (double)lane_stage_cost(p, L, xh, ut, live_mask);
+  auto step = [&](float ut, const RefLane& rt, int t) __attribute__((always_inline)) {
+    J += (double)lane_stage_cost(p, with_ref<RefS>(L, rt), xh, ut, live_mask);
     float xn[4];
     const QuadU U(ut);
     quad_step<RK4>(L, xh, U, xn);
@@ -494,16 +555,22 @@ __device__ __forceinline__ void simulate_quad_body(const quattro_model_params& p
   // be acknowledged (the counter retires in order): a store round trip on the chain of every step.
   // (the empty asm "uses" the two prefetched controls, so their loads cannot sink below the wait)
   asm volatile("" : "+v"(u0), "+v"(u1));
+  if constexpr (REF) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) asm volatile("" : "+v"(r0.xr[g]), "+v"(r1.xr[g]), "+v"(rN.xr[g]));
+  }
   __builtin_amdgcn_s_waitcnt(0x0f70);        // vmcnt(0), nothing else
   int t = 0;
   for (; t + 1 < N; t += 2) {
-    step(u0, t);
+    step(u0, r0, t);
     u0 = ub[(size_t)(t + 2 < N ? t + 2 : N - 1) * NU];
-    step(u1, t + 1);
+    r0.load(ref, t + 2 < N ? t + 2 : N - 1);
+    step(u1, r1, t + 1);
     u1 = ub[(size_t)(t + 3 < N ? t + 3 : N - 1) * NU];
+    r1.load(ref, t + 3 < N ? t + 3 : N - 1);
   }
-  if (t < N) step(u0, t);
-  J += (double)lane_final_cost(L, xh);
+  if (t < N) step(u0, r0, t);
+  J += (double)lane_final_cost(with_ref<RefS>(L, rN), xh);
   J = quad_sum(J);
   if (live && L.j == 0 && cost != nullptr) cost[b] = J;
 }
@@ -513,13 +580,15 @@ __device__ __forceinline__ void simulate_quad_body(const quattro_model_params& p
 // `gid` = 32 * trajectory + lane-in-trajectory for this lane (the 64 lanes of a wave hold two consecutive trajectories);
 // `force` treats every trajectory as active whatever its flag says (fixed-iteration benchmarking runs).
 // PHYS: the candidates of trajectory b roll out under row b of model_phys (lane_const_phys); the cost stays p's
-template <bool RK4, int PF, bool PRIO, bool PHYS = false>
+// REF: every candidate's cost against the rows of rr (quad_rollout_closed with a RefSrc)
+template <bool RK4, int PF, bool PRIO, bool PHYS = false, bool REF = false>
 __device__ __forceinline__ void linesearch_quad_body(const quattro_model_params& p, float* x_nom, float* u_nom,
                                                      const float* __restrict__ K, const float* __restrict__ k,
                                                      const AlphaList& al, int n_alpha, int B, int N, double tol,
                                                      double* cost, int32_t* __restrict__ alpha_idx, int32_t* active,
                                                      int32_t* iters, float* __restrict__ scratch, const int gid,
-                                                     const bool force, const float* __restrict__ model_phys = nullptr) {
+                                                     const bool force, const float* __restrict__ model_phys = nullptr,
+                                                     const RefRows& rr = RefRows{}) {
   const int b = gid >> 5, ai = (gid >> 2) & 7, l32 = gid & 31;
   const bool live = (b < B) && (force || active == nullptr || active[b < B ? b : 0] != 0);
   if (!__any(live)) return;   // both trajectories of the wave converged / out of range: nothing to do (late iterations
@@ -537,7 +606,9 @@ __device__ __forceinline__ void linesearch_quad_body(const quattro_model_params&
 #pragma unroll
   for (int i = 1; i < QUATTRO_MAX_ALPHAS; ++i) alpha = (aa == i) ? al.a[i] : alpha;
   const double J0 = live ? cost[bb] : 0.0;
-  double J = quad_rollout_closed<RK4, PF, PRIO>(p, L, nom, alpha, N, mine, ScratchStore(L, sc + (size_t)aa * N * CS, mine));
+  using RefS = std::conditional_t<REF, RefSrc, NoRefSrc>;
+  double J = quad_rollout_closed<RK4, PF, PRIO>(p, L, nom, alpha, N, mine, ScratchStore(L, sc + (size_t)aa * N * CS, mine),
+                                                RefS(L, rr, wb, live ? b - wb : 0, 2));
   J = quad_sum(J);
   const bool ok = mine && (J <= J0);     // false for NaN, like the reference's comparison
   // first accepted alpha among this trajectory's 8 quads (bit 4*ai of its 32-bit half of the ballot)

@@ -39,6 +39,11 @@ struct SolveLoop {
   // per-trajectory model parameters (quattro_ilqr_solve_phys_f32, quattro_mpc_run_phys_f32; the PHYS instantiations of the kernels):
   // row b replaces the parameter block's phys wherever the controller's model of trajectory b is evaluated.  NULL: none.
   const float* model_phys;    // [B][8]
+  // reference rows (quattro_ilqr_solve_ref_f32, quattro_mpc_run_ref_f32; the REF instantiations of the kernels): row
+  // min(s + preview * t, ref_rows - 1) of trajectory b replaces the parameter block's x_ref at horizon step t of the plan that starts
+  // at plant step s (qt_ref_row, quattro_device.h).  A plain solve has s = 0 and preview = 1.  NULL: none.
+  const float* x_ref_rows;    // [B][ref_rows][n]
+  int ref_rows, preview;
 };
 
 namespace {
@@ -52,8 +57,9 @@ __device__ __forceinline__ int traj_steps(const SolveLoop& c) {
 
 // The parameter block a lane evaluates the model of trajectory bb with.  PHYS: `own`, a copy of the kernel's block whose phys is row
 // bb of c.model_phys, taken as values (the cart-pole's four rows of a wave hold four different sets; a user model's wave one);
-// otherwise the kernel's block itself, and `own` is never touched.
-template <bool PHYS>
+// otherwise the kernel's block itself, and `own` is never touched.  REF without PHYS: `own` as a plain copy, whose x_ref set_ref_row
+// then rewrites step by step.
+template <bool PHYS, bool REF = false>
 __device__ __forceinline__ const quattro_model_params& trajectory_params(const quattro_model_params& p, const SolveLoop& c,
                                                                          const size_t bb, quattro_model_params& own) {
   if constexpr (PHYS) {
@@ -64,9 +70,30 @@ __device__ __forceinline__ const quattro_model_params& trajectory_params(const q
 #pragma unroll
     for (int i = 0; i < 8; ++i) own.phys[i] = ph[i];
     return own;
+  } else if constexpr (REF) {
+    own = p;
+    return own;
   } else {
     return p;
   }
+}
+
+// The rows of c.x_ref_rows as plan cs of the loop reads them (cs = 0 in a plain solve, where c.hold is 0 too)
+__device__ __forceinline__ RefRows plan_ref_rows(const SolveLoop& c, const int cs) {
+  return RefRows{c.x_ref_rows, c.ref_rows, cs * c.hold, c.preview};
+}
+
+// REF, for the bodies that evaluate the model on a block of their own (trajectory_params: the cart-pole's rows, a user model's
+// wave): x_ref of that block becomes the row of trajectory bb that horizon step t reads.  Called before every evaluation of a
+// stage cost, a record or the terminal pair (t = N); NX: the model's state dimension (the rows' length).
+template <int NX>
+__device__ __forceinline__ void set_ref_row(quattro_model_params& own, const RefRows& rr, const size_t bb, const int t) {
+  const float* row = rr.rows + (bb * rr.R + qt_ref_row(rr, t)) * NX;
+  float v[NX];
+#pragma unroll
+  for (int i = 0; i < NX; ++i) v[i] = row[i];
+#pragma unroll
+  for (int i = 0; i < NX; ++i) own.x_ref[i] = v[i];
 }
 
 // every store of this wave has completed before its lanes read what other lanes of the wave wrote (the phases of a

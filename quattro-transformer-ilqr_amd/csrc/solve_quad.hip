@@ -159,7 +159,10 @@ __device__ __forceinline__ void wg_sync() {
 // values (sweep_tile16_body<.., PHYS>); in the nominal rollout and the line search each quad of wave 0 takes the row of the
 // trajectory it works on (lane_const_phys).  The plant of mpc_advance is a.plant / a.plant_phys as ever: the entry points
 // a.plant_phys at the same rows when the run names no plant of its own.
-template <bool RK4, bool PLANT, bool PHYS>
+// REF (with PLANT only, like PHYS): the cost of horizon step t of the plan that starts at plant step cs * c.hold is taken against
+// the row of c.x_ref_rows that step reads (qt_ref_row) — nominal rollout, l_x and V_x(N) of the sweep, every line-search candidate.
+// Each phase takes the rows from its own fresh copy of the arguments (plan_ref_rows), like everything else it reads.
+template <bool RK4, bool PLANT, bool PHYS, bool REF>
 __global__ __launch_bounds__(128, 4) void solve_quad_kernel(const SolveArgs) {
   const KernArgPtr kap = (KernArgPtr)__builtin_amdgcn_kernarg_segment_ptr();   // the one by-value argument sits at offset 0
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -205,8 +208,8 @@ __global__ __launch_bounds__(128, 4) void solve_quad_kernel(const SolveArgs) {
           }
         }
         if ((a.flags & QUATTRO_SOLVE_SIMULATE) != 0 || a.n_ctrl > 0)
-          simulate_quad_body<RK4, PHYS>(args.fa.p, a.x0, a.u, a.N, a.x, a.cost, 4 * b0 + ln, ln < 8 && b0 + (ln >> 2) < a.B,
-                                        a.model_phys);
+          simulate_quad_body<RK4, PHYS, REF>(args.fa.p, a.x0, a.u, a.N, a.x, a.cost, 4 * b0 + ln, ln < 8 && b0 + (ln >> 2) < a.B,
+                                             a.model_phys, plan_ref_rows(a, cs));
       }
       wg_sync();
     }
@@ -233,8 +236,9 @@ __global__ __launch_bounds__(128, 4) void solve_quad_kernel(const SolveArgs) {
         const SolveLoop& a = args.c;
         int ln = lane;
         asm volatile("" : "+v"(ln));
-        sweep_tile16_body<SWEEP_MODE, PHYS>(nullptr, nullptr, nullptr, a.N, a.reg, a.K, a.k, a.status, args.fa, b, ln,
-                                            s_t_all + wv * 16 * LD, s_vx_all + wv * 64, s_lin_all + wv * LIN_FLOATS, a.model_phys);
+        sweep_tile16_body<SWEEP_MODE, PHYS, REF>(nullptr, nullptr, nullptr, a.N, a.reg, a.K, a.k, a.status, args.fa, b, ln,
+                                                 s_t_all + wv * 16 * LD, s_vx_all + wv * 64, s_lin_all + wv * LIN_FLOATS, a.model_phys,
+                                                 plan_ref_rows(a, cs));
       }
       if (logging && mine && lane == 0) log_stamp(fresh_args(kap).c.log, b, log_it, 1, 2);
       wg_sync();
@@ -245,8 +249,9 @@ __global__ __launch_bounds__(128, 4) void solve_quad_kernel(const SolveArgs) {
         asm volatile("" : "+v"(ln));
         __builtin_amdgcn_s_setprio(LS_PRIO);        // (one constant priority: toggling inside the step, as the stand-alone
                                                     //  line search does, bought nothing here)
-        linesearch_quad_body<RK4, 2, false, PHYS>(args.fa.p, a.x, a.u, a.K, a.k, a.al, a.n_alpha, a.B, a.N, a.tol, a.cost,
-                                                  a.alpha_idx, a.active, a.iters, a.scratch, 32 * b0 + ln, force, a.model_phys);
+        linesearch_quad_body<RK4, 2, false, PHYS, REF>(args.fa.p, a.x, a.u, a.K, a.k, a.al, a.n_alpha, a.B, a.N, a.tol, a.cost,
+                                                       a.alpha_idx, a.active, a.iters, a.scratch, 32 * b0 + ln, force, a.model_phys,
+                                                       plan_ref_rows(a, cs));
         __builtin_amdgcn_s_setprio(0);
       }
       wg_sync();
@@ -304,15 +309,17 @@ int quattro_launch_solve_quad(const quattro_model_params& p, const SolveLoop& c,
   a.stamp_rows = stamp_rows;
   const dim3 grid((unsigned)((c.B + 1) / 2));
   const bool rk4 = p.integrator == QUATTRO_INTEGRATOR_RK4;
-  if (c.model_phys != nullptr) {      // (the two phys entries alone set it)
-    if (rk4) hipLaunchKernelGGL((solve_quad_kernel<true, true, true>), grid, dim3(128), 0, stream, a);
-    else hipLaunchKernelGGL((solve_quad_kernel<false, true, true>), grid, dim3(128), 0, stream, a);
-  } else if (c.hold > 0) {      // (quattro_mpc_run_plant_f32 alone sets it)
-    if (rk4) hipLaunchKernelGGL((solve_quad_kernel<true, true, false>), grid, dim3(128), 0, stream, a);
-    else hipLaunchKernelGGL((solve_quad_kernel<false, true, false>), grid, dim3(128), 0, stream, a);
-  } else {
-    if (rk4) hipLaunchKernelGGL((solve_quad_kernel<true, false, false>), grid, dim3(128), 0, stream, a);
-    else hipLaunchKernelGGL((solve_quad_kernel<false, false, false>), grid, dim3(128), 0, stream, a);
-  }
+  // (c.x_ref_rows: the two ref entries alone set it; c.model_phys: they and the two phys entries; c.hold: the plant run and those)
+#define QT_LAUNCH(PLANT, PHYS, REF)                                                                          \
+  do {                                                                                                       \
+    if (rk4) hipLaunchKernelGGL((solve_quad_kernel<true, PLANT, PHYS, REF>), grid, dim3(128), 0, stream, a); \
+    else hipLaunchKernelGGL((solve_quad_kernel<false, PLANT, PHYS, REF>), grid, dim3(128), 0, stream, a);    \
+  } while (0)
+  if (c.x_ref_rows != nullptr && c.model_phys != nullptr) QT_LAUNCH(true, true, true);
+  else if (c.x_ref_rows != nullptr) QT_LAUNCH(true, false, true);
+  else if (c.model_phys != nullptr) QT_LAUNCH(true, true, false);
+  else if (c.hold > 0) QT_LAUNCH(true, false, false);
+  else QT_LAUNCH(false, false, false);
+#undef QT_LAUNCH
   return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;
 }

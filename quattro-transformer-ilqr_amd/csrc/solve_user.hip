@@ -49,7 +49,10 @@ struct UserSolveArgs {
 // PHYS (with PLANT only: quattro_ilqr_solve_phys_f32 has n_ctrl == 0 and never reaches the MPC code): the wave evaluates its
 // trajectory's model — nominal rollout, linearisation, terminal pair, line search — on a block whose phys (the model's free
 // parameters P[0..7]) is its row of c.model_phys
-template <bool RK4, bool PLANT, bool PHYS>
+// REF (with PLANT only, like PHYS): the cost of horizon step t is taken against the row of c.x_ref_rows that step reads
+// (qt_ref_row): the wave's private block gets it as x_ref before every stage cost, record and terminal row (set_ref_row), so the
+// model's stage_cost / final_cost see it as p.x_ref, whatever they do with it
+template <bool RK4, bool PLANT, bool PHYS, bool REF>
 __global__ __launch_bounds__(QT_WAVE, 2) void solve_user_kernel(const UserSolveArgs a) {
   constexpr int MODEL = QUATTRO_MODEL_USER, NX = QT_USER_NX, NU = QT_USER_NU, NZ = NX + NU;
   constexpr int LPI = NZ <= 8 ? 8 : (NZ <= 16 ? 16 : 32), IPP = QT_WAVE / LPI;      // lanes per item, items per pass
@@ -71,10 +74,13 @@ __global__ __launch_bounds__(QT_WAVE, 2) void solve_user_kernel(const UserSolveA
   float* recb = a.rec + bb * N * R::STRIDE;
   volatile int32_t* act_flag = c.active + b;     // written by this wave's line search: always re-read from memory
   quattro_model_params own;
-  const quattro_model_params& mp = trajectory_params<PHYS>(a.p, c, bb, own);
+  const quattro_model_params& mp = trajectory_params<PHYS, REF>(a.p, c, bb, own);
   const int n_ctrl = c.n_ctrl > 0 ? c.n_ctrl : 1;
   for (int cs = 0; cs < n_ctrl; ++cs) {
-    wave_step_prologue<NX, PLANT>(c, bb, cs, lane == 0, [&] { simulate_body<MODEL, RK4>(mp, c.x0, c.u, N, c.x, c.cost, b); });
+    auto ref = [&](int t) __attribute__((always_inline)) {
+      if constexpr (REF) set_ref_row<NX>(own, plan_ref_rows(c, cs), bb, t);
+    };
+    wave_step_prologue<NX, PLANT>(c, bb, cs, lane == 0, [&] { simulate_body<MODEL, RK4>(mp, c.x0, c.u, N, c.x, c.cost, b, ref); });
     const bool logging = c.log.rec != nullptr && c.n_ctrl == 0;
     for (int it = 0; it < c.max_iter; ++it) {
       if (!(force || *act_flag != 0)) break;       // wave-uniform: one trajectory per wave
@@ -90,9 +96,12 @@ __global__ __launch_bounds__(QT_WAVE, 2) void solve_user_kernel(const UserSolveA
         const int j = lane % LPI;
         for (int t0 = 0; t0 < N; t0 += IPP) {
           const int t = t0 + lane / LPI;
-          if (t < N && j < NZ)
+          if (t < N && j < NZ) {
+            ref(t);
             user_linearize_item<R, RK4>(mp, xb + (size_t)t * NX, ub + (size_t)t * NU, recb + (size_t)t * R::STRIDE, j);
+          }
         }
+        ref(N);
         if (lane < NX) user_terminal_row(mp, xb + (size_t)N * NX, lane, a.VxN + bb * NX, a.VxxN + bb * NX * NX);
       }
       wave_handoff();
@@ -114,7 +123,7 @@ __global__ __launch_bounds__(QT_WAVE, 2) void solve_user_kernel(const UserSolveA
       if (logging && lane == 0) log_stamp(c.log, b, log_it, 1, 2);
       wave_handoff();
       linesearch_body<MODEL, RK4, 64>(mp, c.x, c.u, c.K, c.k, c.al, c.n_alpha, c.B, N, c.tol, c.cost, c.alpha_idx, c.active,
-                                      c.iters, c.scratch, 64 * b + lane, force);
+                                      c.iters, c.scratch, 64 * b + lane, force, ref);
       wave_handoff();
       if (logging)               // gains, accepted step, cost after the iteration, end stamp
         log_end(c.log, b, log_it, c.K + bb * N * NU * NX, c.k + bb * N * NU, *(volatile int32_t*)(c.alpha_idx + b),
@@ -182,15 +191,17 @@ int quattro_launch_solve_user(const quattro_model_params& p, const SolveLoop& c,
   const dim3 grid((unsigned)c.B);
   if (p.integrator != QUATTRO_INTEGRATOR_EULER && p.integrator != QUATTRO_INTEGRATOR_RK4) return QUATTRO_ERR_UNSUPPORTED;
   const bool rk4 = p.integrator == QUATTRO_INTEGRATOR_RK4;
-  if (c.model_phys != nullptr) {      // (the two phys entries alone set it)
-    if (rk4) hipLaunchKernelGGL((solve_user_kernel<true, true, true>), grid, dim3(QT_WAVE), 0, stream, a);
-    else hipLaunchKernelGGL((solve_user_kernel<false, true, true>), grid, dim3(QT_WAVE), 0, stream, a);
-  } else if (c.hold > 0) {
-    if (rk4) hipLaunchKernelGGL((solve_user_kernel<true, true, false>), grid, dim3(QT_WAVE), 0, stream, a);
-    else hipLaunchKernelGGL((solve_user_kernel<false, true, false>), grid, dim3(QT_WAVE), 0, stream, a);
-  } else {
-    if (rk4) hipLaunchKernelGGL((solve_user_kernel<true, false, false>), grid, dim3(QT_WAVE), 0, stream, a);
-    else hipLaunchKernelGGL((solve_user_kernel<false, false, false>), grid, dim3(QT_WAVE), 0, stream, a);
-  }
+  // (c.x_ref_rows: the two ref entries alone set it; c.model_phys: they and the two phys entries; c.hold: the plant run and those)
+#define QT_LAUNCH(PLANT, PHYS, REF)                                                                                 \
+  do {                                                                                                              \
+    if (rk4) hipLaunchKernelGGL((solve_user_kernel<true, PLANT, PHYS, REF>), grid, dim3(QT_WAVE), 0, stream, a);    \
+    else hipLaunchKernelGGL((solve_user_kernel<false, PLANT, PHYS, REF>), grid, dim3(QT_WAVE), 0, stream, a);       \
+  } while (0)
+  if (c.x_ref_rows != nullptr && c.model_phys != nullptr) QT_LAUNCH(true, true, true);
+  else if (c.x_ref_rows != nullptr) QT_LAUNCH(true, false, true);
+  else if (c.model_phys != nullptr) QT_LAUNCH(true, true, false);
+  else if (c.hold > 0) QT_LAUNCH(true, false, false);
+  else QT_LAUNCH(false, false, false);
+#undef QT_LAUNCH
   return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;
 }

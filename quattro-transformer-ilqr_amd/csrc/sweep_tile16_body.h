@@ -225,9 +225,10 @@ __device__ __forceinline__ void rk4_stage_entries(const QuadStage& s, const floa
   c[27] = c3 * s.wp;
 }
 
+// (`xr`: the reference the step's l_x is taken against -- p.x_ref, or the step's row of the reference rows, read where l_x is formed)
 template <class Emit>
-__device__ __forceinline__ void rk4_step_coefs(const quattro_model_params& p, const float* ph, const float* xs, const float* us,
-                                               Emit emit) {
+__device__ __forceinline__ void rk4_step_coefs(const quattro_model_params& p, const float* ph, const float* xr, const float* xs,
+                                               const float* us, Emit emit) {
   constexpr int NX = 12;
   // each stage's 28 coefficients leave before the next stage point is computed
   float c[Rk4Coef::PER_STAGE];
@@ -242,7 +243,7 @@ __device__ __forceinline__ void rk4_step_coefs(const quattro_model_params& p, co
   // moving the copy onto the helper would change their rounding.
   float lz[16], luud[4];
 #pragma unroll
-  for (int i = 0; i < NX; ++i) lz[i] = 2.0f * p.q[i] * (xs[i] - p.x_ref[i]);
+  for (int i = 0; i < NX; ++i) lz[i] = 2.0f * p.q[i] * (xs[i] - xr[i]);
 #pragma unroll
   for (int a = 0; a < 4; ++a) {
     float lu = 2.0f * p.r[a] * us[a], luu = 2.0f * p.r[a];
@@ -257,6 +258,12 @@ __device__ __forceinline__ void rk4_step_coefs(const quattro_model_params& p, co
 #pragma unroll
   for (int q = 0; q < 4; ++q) emit(Rk4Coef::LZ / 4 + q, make_float4(lz[4 * q], lz[4 * q + 1], lz[4 * q + 2], lz[4 * q + 3]));
   emit(Rk4Coef::LUUD / 4, make_float4(luud[0], luud[1], luud[2], luud[3]));
+}
+
+template <class Emit>
+__device__ __forceinline__ void rk4_step_coefs(const quattro_model_params& p, const float* ph, const float* xs, const float* us,
+                                               Emit emit) {
+  rk4_step_coefs(p, ph, p.x_ref, xs, us, emit);
 }
 
 // ---- MODE_FUSED_RK4, stage (2): where entry [row tile][column tile] of a stage's rate Jacobian M = [f_x | f_u] comes from: index
@@ -299,14 +306,20 @@ __device__ __forceinline__ Rk4Entry rk4_m_entry(const float* ph, int row_tile, i
 // replaces fa.p.phys.  The wave owns the trajectory, so the row is wave-uniform: its values are read ONCE, through a uniform
 // address in the constant address space (scalar loads; the array is never written while the kernel runs), and handed as values to
 // the code that reads phys.  Everything else of the problem (dt, the lane-indexed q, qf, x_ref, r) stays in the argument block.
-template <int MODE, bool PHYS = false>
+// REF (the same modes, quattro_ilqr_solve_ref_f32 / quattro_mpc_run_ref_f32): l_x of horizon step t and V_x(N) are taken against the
+// row of rr that step reads (qt_ref_row) instead of fa.p.x_ref.  The trajectory's block of rows has a wave-uniform base
+// (readfirstlane(b), like the PHYS row); which row a lane reads depends on the step it linearises, so the rows themselves are vector
+// loads: twelve floats per step, fetched where the step's (x_t, u_t) are.  l_xx, V_xx(N) and everything else stay the problem's.
+template <int MODE, bool PHYS = false, bool REF = false>
 __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec, const float* __restrict__ VxN,
                                                   const float* __restrict__ VxxN, int S, float reg,
                                                   float* __restrict__ Kout, float* __restrict__ kout,
                                                   int32_t* __restrict__ status, const FusedArgs& fa, const int b,
                                                   const int lane, float* s_t, float* s_vx, float* s_lin,
-                                                  const float* model_phys = nullptr) {
-  static_assert(!PHYS || MODE == MODE_FUSED || MODE == MODE_FUSED_RK4, "per-trajectory parameters: the fused modes only");
+                                                  const float* model_phys = nullptr, const RefRows& rr = RefRows{}) {
+  static_assert(!(PHYS || REF) || MODE == MODE_FUSED || MODE == MODE_FUSED_RK4, "per-trajectory parameters: the fused modes only");
+  const float* rows_b = nullptr;              // REF: the rows of this trajectory
+  if constexpr (REF) rows_b = rr.rows + (size_t)__builtin_amdgcn_readfirstlane(b) * rr.R * 12;
   float phv[8];
   if constexpr (PHYS) {
     typedef const float __attribute__((address_space(4))) * ConstRow;
@@ -340,9 +353,10 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
       vA1 = (xj == 3 * r + 1) ? 2.0f * fa.p.qf[xj] : 0.0f;
       vA2 = (xj == 3 * r + 2) ? 2.0f * fa.p.qf[xj] : 0.0f;
     }
-    vx0 = 2.0f * fa.p.qf[3 * r + 0] * (xN[3 * r + 0] - fa.p.x_ref[3 * r + 0]);
-    vx1 = 2.0f * fa.p.qf[3 * r + 1] * (xN[3 * r + 1] - fa.p.x_ref[3 * r + 1]);
-    vx2 = 2.0f * fa.p.qf[3 * r + 2] * (xN[3 * r + 2] - fa.p.x_ref[3 * r + 2]);
+    const float* const xrN = REF ? rows_b + 12 * qt_ref_row(rr, fa.N) : fa.p.x_ref;      // (the terminal cost is horizon step N)
+    vx0 = 2.0f * fa.p.qf[3 * r + 0] * (xN[3 * r + 0] - xrN[3 * r + 0]);
+    vx1 = 2.0f * fa.p.qf[3 * r + 1] * (xN[3 * r + 1] - xrN[3 * r + 1]);
+    vx2 = 2.0f * fa.p.qf[3 * r + 2] * (xN[3 * r + 2] - xrN[3 * r + 2]);
     if constexpr (FUSED) {
       // the constants of the problem, once: the header record, and the constant image (zeros, fill_const) of every stage
       // slot — a refill runs fill_state only, which writes the same entries of a slot every time
@@ -686,7 +700,8 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
         const float xs[12] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w, xc.x, xc.y, xc.z, xc.w};
         const float us[4] = {ua.x, ua.y, ua.z, ua.w};
         float4* dst = reinterpret_cast<float4*>(coef) + ls;
-        rk4_step_coefs(fa.p, ph, xs, us, [&](int q, float4 v) __attribute__((always_inline)) { dst[(size_t)q * S] = v; });
+        const float* const xr = REF ? rows_b + 12 * qt_ref_row(rr, t) : fa.p.x_ref;
+        rk4_step_coefs(fa.p, ph, xr, xs, us, [&](int q, float4 v) __attribute__((always_inline)) { dst[(size_t)q * S] = v; });
       }
     }
     // the records are read back by other lanes of this same wave: complete (written through to L2) before any is loaded
@@ -726,6 +741,7 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
     // (x_t, u_t) of a batch's steps, both lanes of a slot: requested a whole batch ahead (the loads of batch j - 1 fly while
     // the steps of batch j run; waiting for them at the refill would expose an HBM round trip twice per sweep)
     float4 xa, xb, xc, ua;
+    float4 ra, rb, rc;                                             // REF: the step's reference row, fetched with them
     auto fetch = [&](int base) __attribute__((always_inline)) {
       const int cnt = S - base < FUSED_BATCH ? S - base : FUSED_BATCH;
       const int t = fa.t_start + base + (sl < cnt ? sl : 0);
@@ -734,6 +750,12 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
       xb = px[1];
       xc = px[2];
       ua = *reinterpret_cast<const float4*>(fa.u + ((size_t)b * fa.N + t) * 4);
+      if constexpr (REF) {
+        const float4* pr = reinterpret_cast<const float4*>(rows_b + 12 * qt_ref_row(rr, t));
+        ra = pr[0];
+        rb = pr[1];
+        rc = pr[2];
+      }
     };
     const int top = ((S - 1) / FUSED_BATCH) * FUSED_BATCH;
     fetch(top);
@@ -744,6 +766,13 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
         using ER = EulerRecord<QUATTRO_MODEL_QUADROTOR, Tile16FRec>;
         const float xs[12] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w, xc.x, xc.y, xc.z, xc.w};
         const float us[4] = {ua.x, ua.y, ua.z, ua.w};
+        float xrv[12];
+        if constexpr (REF) {
+          const float v[12] = {ra.x, ra.y, ra.z, ra.w, rb.x, rb.y, rb.z, rb.w, rc.x, rc.y, rc.z, rc.w};
+#pragma unroll
+          for (int i = 0; i < 12; ++i) xrv[i] = v[i];
+        }
+        const float* const xr = REF ? xrv : fa.p.x_ref;
         // (all 64 lanes: the lanes past cnt hold a real step's (x, u), and the crossbar hop wants every lane active)
         QuadTrig tr;
         qt_sincos(dynl ? xs[6] : xs[8], &tr.sph, &tr.cph);
@@ -758,7 +787,7 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
             quad_trig_finish(tr);
             ER::fill_dynamics(mine, fa.p, ph, tr, xs, us);
           } else {
-            ER::fill_lx(mine, fa.p, xs);
+            ER::fill_lx(mine, fa.p, xr, xs);
           }
           ER::fill_control(mine, fa.p, ca, ra0, dynl ? us[0] : us[2]);
           ER::fill_control(mine, fa.p, ca + 1, ra1, dynl ? us[1] : us[3]);

@@ -11,7 +11,9 @@
 // T = float in the rollouts; T = Dual<float> / Dual<Dual<float>> (dual.h) where the reference takes finite differences
 // (:149-275): columns of [A | B] through the whole integrator step, gradient and Hessian of L and Lf.  p.phys[0..7] are the
 // model's free parameters, p.q / p.r / p.qf / p.x_ref / p.barrier_* are there for the cost to use (default_stage_cost /
-// default_final_cost are the built-in diagonal forms).  Compiled with -DQT_USER_MODEL_HEADER="..." -DQT_USER_NX=n -DQT_USER_NU=m.
+// default_final_cost are the built-in diagonal forms).  In a solve or closed loop with reference rows (quattro_ilqr_solve_ref_f32,
+// quattro_mpc_run_ref_f32) stage_cost at horizon step t and final_cost see that step's row of x_ref_rows as p.x_ref[0 .. n-1],
+// whatever they do with it; the model itself needs no change.  Compiled with -DQT_USER_MODEL_HEADER="..." -DQT_USER_NX=n -DQT_USER_NU=m.
 #pragma once
 #include "dual.h"
 

@@ -454,7 +454,7 @@ def solve_log_record(model, log, phase, x_nom, u_nom, K, k, cost, alpha_idx, act
 
 def ilqr_solve(model, x_nom, u_nom, K, k, cost, tol, max_iter, workspace, alphas=ALPHAS, reg=QUU_REG, x0=None,
                alpha_idx=None, active=None, iters=None, status=None, fixed_iters=False, reset=False, log=None,
-               persistent=False, enqueue=False, model_phys=None):
+               persistent=False, enqueue=False, model_phys=None, x_ref_rows=None):
     """The whole solve from ONE C call with no host involvement: up to max_iter iterations, every trajectory stopping on
     its own test; x0 given = roll the nominal out from it first.  Everything in place (quattro_ilqr_solve_phys_f32).
     reset: the call sets active / iters / alpha_idx / status itself; log: a SolveLog ring filled by the device;
@@ -462,9 +462,13 @@ def ilqr_solve(model, x_nom, u_nom, K, k, cost, tol, max_iter, workspace, alphas
     the persistent kernel.
     model_phys (B, len(model.phys)), or the (B, 8) float32 device tensor of model_phys_tensor: trajectory b is solved with row b
     for the model's phys (always the model's persistent kernel; NotImplementedError where there is none, ValueError together
-    with enqueue).  None: the solve with model.phys for every trajectory."""
+    with enqueue).  None: the solve with model.phys for every trajectory.
+    x_ref_rows (B, R, n) or (B, n), or the device tensor of x_ref_rows_tensor: the cost of trajectory b at horizon step t (t = N: the
+    terminal cost) is taken against row min(t, R - 1) of its rows in place of model.x_ref (quattro_ilqr_solve_ref_f32; the same
+    kernel rule and refusals as model_phys).  None: model.x_ref for every trajectory and step."""
     Bt, N, m = u_nom.shape
     model_phys = model_phys_tensor(model, model_phys, Bt, u_nom.device)
+    x_ref_rows = x_ref_rows_tensor(model, x_ref_rows, Bt, u_nom.device, name="x_ref_rows")
     n = model.n
     f32, i32 = torch.float32, torch.int32
     _req(x_nom, (Bt, N + 1, n), f32, "x_nom"); _req(u_nom, (Bt, N, model.m), f32, "u_nom")
@@ -484,7 +488,16 @@ def ilqr_solve(model, x_nom, u_nom, K, k, cost, tol, max_iter, workspace, alphas
     args = (ctypes.byref(p), _ptr(x0), _ptr(x_nom), _ptr(u_nom), Bt, N, float(reg), arr, na, float(tol), int(max_iter), flags,
             _ptr(K), _ptr(k), _ptr(cost), _ptr(alpha_idx), _ptr(active), _ptr(iters), _ptr(status), _ptr(workspace),
             workspace.numel() * workspace.element_size(), None if log is None else log.byref())
-    check(_lib.load_for(model).quattro_ilqr_solve_phys_f32(*args, _ptr(model_phys), _stream()), "quattro_ilqr_solve_phys_f32")
+    _solve_call(_lib.load_for(model), args, model_phys, x_ref_rows, _stream())
+
+
+def _solve_call(lib, args, model_phys, x_ref_rows, stream):
+    """The one C call of a solve: the ref entry with rows, the phys entry (whose NULL rows forward inside the library) without."""
+    if x_ref_rows is not None:
+        check(lib.quattro_ilqr_solve_ref_f32(*args, _ptr(model_phys), _ptr(x_ref_rows), x_ref_rows.shape[1], stream),
+              "quattro_ilqr_solve_ref_f32")
+    else:
+        check(lib.quattro_ilqr_solve_phys_f32(*args, _ptr(model_phys), stream), "quattro_ilqr_solve_phys_f32")
 
 
 class PreparedSolve:
@@ -503,23 +516,25 @@ class PreparedSolve:
         self.keep = (x_nom, u_nom, K, k, cost, workspace, x0, alpha_idx, active, iters, status)     # the pointers stay valid
         self.arr, self.na = _alphas(alphas)
         self.p = model.c_params()
-        self.fn = _lib.load_for(model).quattro_ilqr_solve_phys_f32
+        self.lib = _lib.load_for(model)
         self.model = model
         self.dims = (Bt, N, n, m)
         self.head = (ctypes.byref(self.p), _ptr(x0), _ptr(x_nom), _ptr(u_nom), Bt, N, float(reg), self.arr, self.na)
         self.tail = (_ptr(K), _ptr(k), _ptr(cost), _ptr(alpha_idx), _ptr(active), _ptr(iters), _ptr(status), _ptr(workspace),
                      workspace.numel() * workspace.element_size())
 
-    def __call__(self, tol, max_iter, fixed_iters=False, log=None, persistent=False, stream=None, model_phys=None):
-        """model_phys: per-trajectory phys rows (ilqr_solve).  Nothing of it is prepared or kept: the rows are THIS call's argument,
-        so a later call without it is the plain solve."""
+    def __call__(self, tol, max_iter, fixed_iters=False, log=None, persistent=False, stream=None, model_phys=None,
+                 x_ref_rows=None):
+        """model_phys, x_ref_rows: per-trajectory phys rows and reference rows (ilqr_solve).  Nothing of them is prepared or kept:
+        the rows are THIS call's argument, so a later call without them is the plain solve."""
         flags = _lib.SOLVE_SIMULATE | _lib.SOLVE_RESET | (_lib.SOLVE_FIXED_ITERS if fixed_iters else 0) | \
             (_lib.SOLVE_PERSISTENT if persistent else 0)
         if log is not None and (log.B, log.N, log.n, log.m) != self.dims:
             raise ValueError("log ring was built for another problem size")
         model_phys = model_phys_tensor(self.model, model_phys, self.dims[0], self.keep[0].device)
-        check(self.fn(*self.head, float(tol), int(max_iter), flags, *self.tail, None if log is None else log.byref(),
-                      _ptr(model_phys), _stream() if stream is None else stream), "quattro_ilqr_solve_phys_f32")
+        x_ref_rows = x_ref_rows_tensor(self.model, x_ref_rows, self.dims[0], self.keep[0].device, name="x_ref_rows")
+        _solve_call(self.lib, (*self.head, float(tol), int(max_iter), flags, *self.tail, None if log is None else log.byref()),
+                    model_phys, x_ref_rows, _stream() if stream is None else stream)
 
 
 def check_plant(model, plant):
@@ -560,6 +575,30 @@ def plant_phys_tensor(model, plant_phys, B, device, name="plant_phys"):
 def model_phys_tensor(model, model_phys, B, device):
     """Per-trajectory model parameters: plant_phys_tensor under the name the errors use."""
     return plant_phys_tensor(model, model_phys, B, device, name="model_phys")
+
+
+def check_ref_rows(model, rows, B, name="targets", device=None):
+    """Reference rows: None, (B, R, n) with R >= 1, or (B, n) for R = 1.  ValueError otherwise, under the keyword's `name`; host logic
+    only.  -> True where the rows need no conversion: None, or a contiguous (B, R, n) float32 tensor on `device` (any CUDA device
+    if None) whose first element is 16-byte aligned, as the C ABI asks (a slice of a larger tensor may not be)."""
+    if rows is None:
+        return True
+    shape = tuple(np.shape(rows))
+    if not ((len(shape) == 2 and shape == (B, model.n)) or (len(shape) == 3 and shape[0] == B and shape[1] >= 1 and shape[2] == model.n)):
+        raise ValueError(f"{name} must have shape {(B, 'R', model.n)} with R >= 1, or {(B, model.n)} (got {shape})")
+    return (isinstance(rows, torch.Tensor) and len(shape) == 3 and rows.is_cuda and rows.dtype == torch.float32
+            and rows.is_contiguous() and rows.data_ptr() % 16 == 0
+            and (device is None or rows.device == torch.device(device)))
+
+
+def x_ref_rows_tensor(model, rows, B, device, name="targets"):
+    """Reference rows (B, R, n), or (B, n) as R = 1 -> the contiguous, 16-byte aligned (B, R, n) float32 array on `device` that the
+    C ABI takes (x_ref_rows, include/quattro_hip.h).  Such an array is passed through as it is, None stays None; the shape is
+    checked (check_ref_rows) before anything touches the device."""
+    if check_ref_rows(model, rows, B, name, device):
+        return rows
+    t = torch.as_tensor(rows, dtype=torch.float32, device=device).reshape(B, -1, model.n).contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
 def track(model, x0, x_nom, u_nom, K, steps, plant=None, plant_phys=None, feedback=True, disturbance=None):
@@ -605,19 +644,23 @@ def _mpc_args(model, x_cur, x_nom, u_nom, K, k, cost, tol, max_iter, n_steps, wo
 
 def mpc_run(model, x_cur, x_nom, u_nom, K, k, cost, tol, max_iter, n_steps, workspace, traj_x, traj_u, traj_iters,
             disturbance=None, alphas=ALPHAS, reg=QUU_REG, alpha_idx=None, active=None, iters=None, status=None,
-            plant=None, plant_phys=None, hold=1, feedback=False, model_phys=None):
+            plant=None, plant_phys=None, hold=1, feedback=False, model_phys=None, x_ref_rows=None, preview=True):
     """B controllers x n_steps control steps (solve -> apply u_0 -> shift the warm start) in ONE launch
     (quattro_mpc_run_f32); x_cur and u_nom advance in place, the closed-loop record goes to traj_x / traj_u / traj_iters.
     plant / plant_phys / hold / feedback (any of them off its default: quattro_mpc_run_plant_f32): n_steps PLANT steps, a solve
     every `hold` of them and the gain law of track() in between, on a plant of its own; traj_iters is then (B, n_steps / hold).
     model_phys (as in ilqr_solve; quattro_mpc_run_phys_f32, the plant entry's arguments and these rows): controller b plans with
-    row b for its model's phys, and its plant is plant_phys[b], else plant.phys, else that same row."""
+    row b for its model's phys, and its plant is plant_phys[b], else plant.phys, else that same row.
+    x_ref_rows (as in ilqr_solve; quattro_mpc_run_ref_f32, the phys entry's arguments, these rows and preview): horizon step t of the
+    plan that starts at plant step s takes its cost against row min(s + preview * t, R - 1) of controller b's rows — preview=True
+    looks along the rows over the horizon, preview=False holds the row of the replan step for the whole solve."""
     Bt, N, m = u_nom.shape
     n = model.n
     f32, i32 = torch.float32, torch.int32
     hold = int(hold)
     check_phys_rows(model, model_phys, Bt, "model_phys")
-    plain = plant is None and plant_phys is None and hold == 1 and not feedback and model_phys is None
+    check_ref_rows(model, x_ref_rows, Bt, name="x_ref_rows")
+    plain = plant is None and plant_phys is None and hold == 1 and not feedback and model_phys is None and x_ref_rows is None
     if hold < 1 or n_steps % hold != 0:
         raise ValueError("n_steps must be a multiple of hold >= 1")
     _req(x_cur, (Bt, n), f32, "x_cur"); _req(x_nom, (Bt, N + 1, n), f32, "x_nom"); _req(u_nom, (Bt, N, model.m), f32, "u_nom")
@@ -638,8 +681,14 @@ def mpc_run(model, x_cur, x_nom, u_nom, K, k, cost, tol, max_iter, n_steps, work
     pp = None if plant is None else plant.c_params()
     pref = None if pp is None else ctypes.byref(pp)
     pphys = plant_phys_tensor(model, plant_phys, Bt, u_nom.device)
+    model_phys = model_phys_tensor(model, model_phys, Bt, u_nom.device)
+    if x_ref_rows is not None:
+        x_ref_rows = x_ref_rows_tensor(model, x_ref_rows, Bt, u_nom.device, name="x_ref_rows")
+        check(_lib.load_for(model).quattro_mpc_run_ref_f32(*head, pref, _ptr(pphys), hold, int(bool(feedback)), _ptr(model_phys),
+                                                           _ptr(x_ref_rows), x_ref_rows.shape[1], int(bool(preview)), _stream()),
+              "quattro_mpc_run_ref_f32")
+        return
     if model_phys is not None:
-        model_phys = model_phys_tensor(model, model_phys, Bt, u_nom.device)
         check(_lib.load_for(model).quattro_mpc_run_phys_f32(*head, pref, _ptr(pphys), hold, int(bool(feedback)), _ptr(model_phys),
                                                             _stream()), "quattro_mpc_run_phys_f32")
         return

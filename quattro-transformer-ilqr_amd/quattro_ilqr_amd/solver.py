@@ -354,9 +354,9 @@ class QuattroILQR:
             return bool(self._active_host.numpy().any())
         return int(self.active.sum().item()) != 0
 
-    def _check_model_phys(self, model_phys, B):
-        """model_phys runs in the device-resident loop alone: NotImplementedError for every mode that has none, ValueError for a
-        wrong shape, both before anything touches the device."""
+    def _require_device_loop(self, what):
+        """Per-trajectory rows (`what`: the keyword) run in the device-resident loop alone: NotImplementedError for every mode that
+        has none, before anything touches the device."""
         why = None
         if self.tf is not None:
             why = "a predictor (tf) makes the solve a host-driven hybrid loop"
@@ -367,11 +367,20 @@ class QuattroILQR:
         elif not ops.model_can_device_loop(self.model):
             why = f"model {self.model.name} ({self.model.integrator}) has no persistent kernel"
         if why is not None:
-            raise NotImplementedError(f"model_phys runs only in the device-resident loop: {why}")
+            raise NotImplementedError(f"{what} runs only in the device-resident loop: {why}")
+
+    def _check_model_phys(self, model_phys, B):
+        """_require_device_loop, then ValueError for a wrong shape; both before anything touches the device."""
+        self._require_device_loop("model_phys")
         ops.check_phys_rows(self.model, model_phys, B, "model_phys")
 
+    def _check_targets(self, targets, B):
+        """The same for reference rows."""
+        self._require_device_loop("targets")
+        ops.check_ref_rows(self.model, targets, B)
+
     def solve(self, x0, u_init=None, x_ref=None, max_iter=None, fixed_iters=False, log=None, want_alpha=True,
-              upload_guard=True, model_phys=None):
+              upload_guard=True, model_phys=None, targets=None):
         """x0 (B,n), u_init (B,N,m) (zeros if None).  Returns a dict of device tensors:
         K (B,N,m,n), k (B,N,m), x (B,N+1,n), u (B,N,m), cost (B,) fp64, iters (B,), alpha (B,) last accepted step
         (-1: none), status (B,).  fixed_iters=True runs exactly max_iter iterations (benchmarking: stop flags off).
@@ -383,13 +392,22 @@ class QuattroILQR:
         model.with_(phys=row b), return for their one trajectory, bit for bit.  Always the model's persistent kernel (a user
         model's too, as with device_loop="always"); NotImplementedError with a predictor, use_graph=True, device_loop=False or
         a model without such a kernel, ValueError for a wrong shape, both before anything touches the device.  A later call
-        without it is the plain solve."""
+        without it is the plain solve.
+        targets (B, R, n), or (B, n) for R = 1, or the device tensor of ops.x_ref_rows_tensor: per-trajectory, per-step state
+        targets.  The cost of trajectory b at horizon step t (t = N: the terminal cost) is taken against row min(t, R - 1) of its
+        rows in place of model.x_ref: R = 1 gives every trajectory a goal of its own, R = N + 1 a reference trajectory over the
+        horizon, anything between holds its last row.  Weights, barrier, dt and integrator stay the model's.  The same kernel rule,
+        refusals and order as model_phys, with which it combines.  Out of scope: iLQR_TF, ShardedILQR, datagen, hybrid mode.
+        x_ref: pure mode ignores it — the cost keeps model.x_ref — and hybrid mode feeds it to the predictor's input only
+        (x - x_ref + state_offset); a target for the COST is `targets`."""
         n, m, N, dev = self.model.n, self.model.m, self.horizon, self.device
         if not isinstance(x0, torch.Tensor):
             x0 = np.asarray(x0)
         B = int(np.prod(tuple(x0.shape))) // n
         if model_phys is not None:
             self._check_model_phys(model_phys, B)
+        if targets is not None:
+            self._check_targets(targets, B)
         self._alloc(B)
         self._upload(x0, u_init, guard=upload_guard)
         x0 = self._x0
@@ -407,7 +425,7 @@ class QuattroILQR:
                     self.tf.shifted_mean(xr - off, out=self._tf_mean)
                 self._ref_key = key
             x_ref_t = self._x_ref_t
-        if self.tf is None and not self.use_graph and (self._wants_device_loop() or model_phys is not None):
+        if self.tf is None and not self.use_graph and (self._wants_device_loop() or model_phys is not None or targets is not None):
             # the whole loop on the device: per-solve state reset, nominal rollout, iterations, per-trajectory stop tests —
             # one launch, no synchronisation
             if self._ws is None:
@@ -417,8 +435,9 @@ class QuattroILQR:
                                                      self.reg, x0, self.alpha_idx, self.active, self.iters, self.status)
             # (the rows stay referenced until the next solve: the launch is asynchronous)
             self._model_phys = ops.model_phys_tensor(self.model, model_phys, B, dev)
+            self._targets = ops.x_ref_rows_tensor(self.model, targets, B, dev)
             self._solve_call(self.tol, max_iter, fixed_iters=fixed_iters, log=log, persistent=self.device_loop == "always",
-                             model_phys=self._model_phys)
+                             model_phys=self._model_phys, x_ref_rows=self._targets)
             max_iter = 0
         else:
             self._ints.copy_(self._ints_init)          # active = 1, iters = 0, alpha_idx = -1, status = 0

@@ -17,7 +17,9 @@ and K, k, cost, alpha_idx, status of the solver), quadrotor B = 5, N = 26, cart-
 New forms: 50 plant steps with replan_every = 1 and with replan_every = 5 + feedback + per-controller plants; ops.track of 5 steps;
 the converged solve and the 10 control steps with per-trajectory model parameters (model_phys: every parameter of every
 trajectory within 12 % of the model's) next to the same calls without, and with neutral rows (the PHYS kernels on the default
-problem: same work, same iteration counts).
+problem: same work, same iteration counts); the same two calls with reference rows (targets: neutral rows -- the REF kernels on
+the default problem -- and a reference that moves 2 cm per step along a per-trajectory heading, with preview over the horizon:
+other work, reported with its iterations per trajectory).
 """
 import argparse
 import ctypes
@@ -70,8 +72,10 @@ def measure(defaults_only):
     raw = ctypes.CDLL(_lib.LIB_PATH)
     new_abi = hasattr(raw, "quattro_mpc_run_plant_f32")
     phys_abi = hasattr(raw, "quattro_mpc_run_phys_f32")
+    ref_abi = hasattr(raw, "quattro_mpc_run_ref_f32")
     # an older build of the library: bind what it has (the default forms need nothing newer)
-    for name in ("quattro_track_f32", "quattro_mpc_run_plant_f32", "quattro_ilqr_solve_phys_f32", "quattro_mpc_run_phys_f32"):
+    for name in ("quattro_track_f32", "quattro_mpc_run_plant_f32", "quattro_ilqr_solve_phys_f32", "quattro_mpc_run_phys_f32",
+                 "quattro_ilqr_solve_ref_f32", "quattro_mpc_run_ref_f32"):
         if not hasattr(raw, name):
             _lib.SIGNATURES.pop(name, None)
     from quattro_ilqr_amd import BatchedMPC, QuattroILQR, cartpole_model, ops, quadrotor_model
@@ -92,7 +96,7 @@ def measure(defaults_only):
             ts.append(1e3 * (time.perf_counter() - t0))
         return float(np.median(ts))
 
-    out = {"lib": os.path.basename(_lib.LIB_PATH), "new_abi": new_abi, "phys_abi": phys_abi}
+    out = {"lib": os.path.basename(_lib.LIB_PATH), "new_abi": new_abi, "phys_abi": phys_abi, "ref_abi": ref_abi}
     mpc = BatchedMPC(md, N, max_iter=100, tol=1e-3, device=dev)
 
     def run(steps, **kw):
@@ -147,6 +151,38 @@ def measure(defaults_only):
                 out.setdefault(f"mpc_run_10_steps_{tag}_ms", []).append(timed(lambda: run(10, **kw), reps=5))
                 if rnd == 0:
                     out[f"solve_{tag}_mean_iters"] = float(sv.solve(x0, max_iter=100, **kw)["iters"].float().mean())
+    if not defaults_only and ref_abi:
+        R = 10 + N + 1
+        neutral = ops.x_ref_rows_tensor(md, np.tile(np.asarray(md.x_ref, dtype=np.float32), (B, R, 1)), B, dev)
+        heading = 0.7 * np.arange(B)[:, None]
+        path = np.tile(np.asarray(md.x_ref, dtype=np.float64), (B, R, 1))
+        path[:, :, 0] += 0.02 * np.arange(R)[None, :] * np.cos(heading)
+        path[:, :, 1] += 0.02 * np.arange(R)[None, :] * np.sin(heading)
+        moving = ops.x_ref_rows_tensor(md, path.astype(np.float32), B, dev)
+        for rnd in range(3):
+            for tag, kw in (("shared", {}), ("neutral_targets", dict(targets=neutral)), ("moving_targets", dict(targets=moving))):
+                out.setdefault(f"ref_solve_{tag}_ms", []).append(timed(lambda: sv.solve(x0, max_iter=100, **kw), reps=5))
+                out.setdefault(f"ref_mpc_run_10_steps_{tag}_ms", []).append(timed(lambda: run(10, **kw), reps=5))
+                if rnd == 0:
+                    out[f"ref_solve_{tag}_mean_iters"] = float(sv.solve(x0, max_iter=100, **kw)["iters"].float().mean())
+                    out[f"ref_mpc_run_10_steps_{tag}_mean_iters"] = float(run(10, **kw)["iters"].float().mean())
+        # the cart-pole at BASELINE configs[1]'s shape: the same three forms
+        cR = 10 + 50 + 1
+        c_neutral = ops.x_ref_rows_tensor(cp, np.tile(np.asarray(cp.x_ref, dtype=np.float32), (1024, cR, 1)), 1024, dev)
+        c_path = np.tile(np.asarray(cp.x_ref, dtype=np.float64), (1024, cR, 1))
+        c_path[:, :, 0] += 0.01 * np.arange(cR)[None, :] * np.cos(0.7 * np.arange(1024))[:, None]
+        c_moving = ops.x_ref_rows_tensor(cp, c_path.astype(np.float32), 1024, dev)
+
+        def cp_run_kw(steps, **kw):
+            cp_mpc.u_warm = None
+            return cp_mpc.run(cx0, steps, **kw)
+
+        for rnd in range(3):
+            for tag, kw in (("shared", {}), ("neutral_targets", dict(targets=c_neutral)), ("moving_targets", dict(targets=c_moving))):
+                out.setdefault(f"ref_cartpole_solve_{tag}_ms", []).append(timed(lambda: cp_sv.solve(cx0, max_iter=100, **kw), reps=5))
+                out.setdefault(f"ref_cartpole_mpc_run_10_steps_{tag}_ms", []).append(timed(lambda: cp_run_kw(10, **kw), reps=5))
+                if rnd == 0:
+                    out[f"ref_cartpole_solve_{tag}_mean_iters"] = float(cp_sv.solve(cx0, max_iter=100, **kw)["iters"].float().mean())
     print(json.dumps(out), flush=True)
 
 
@@ -154,7 +190,7 @@ def ab(old, rounds):
     import numpy as np
     res = {"old": [], "new": []}
     for r in range(rounds):
-        for tag in ("old", "new"):
+        for tag in (("old", "new") if r % 2 == 0 else ("new", "old")):     # the order alternates: the child that runs second is ~0.4 % slower
             env = dict(os.environ)
             if tag == "old":
                 env["QUATTRO_HIP_LIB"] = os.path.realpath(old)
