@@ -68,6 +68,8 @@ extern "C" {
 #define QUATTRO_MAX_NX 16
 #define QUATTRO_MAX_NU 8
 #define QUATTRO_MAX_ALPHAS 8
+/* a row of per-trajectory cost weights (COST ROWS below): q, qf and r back to back */
+#define QUATTRO_COST_ROW_FLOATS (2 * QUATTRO_MAX_NX + QUATTRO_MAX_NU)
 
 /* Problem definition handed to the kernels BY VALUE (host struct).  Costs are
  *   L(x,u)  = sum_i q[i] (x_i - x_ref_i)^2 + sum_a r[a] u_a^2 + barrier_alpha * sum_a softplus_beta(-u_a)^2
@@ -403,8 +405,8 @@ int quattro_mpc_run_plant_f32(const quattro_model_params* p, float* x_cur, float
  *                        (quattro_model_has_device_loop(p) == 0), QUATTRO_ERR_BAD_ARG for QUATTRO_SOLVE_ENQUEUE together with
  *                        model_phys; every other argument is checked as by the entry each extends.
  * The stand-alone entries (quattro_simulate_f32, quattro_linearize*_f32, quattro_rollout_f32, quattro_linesearch_f32,
- * quattro_ilqr_iterate_f32, quattro_track_f32) and the other fields of p (cost, dt, integrator) have no per-trajectory form
- * (x_ref has one of its own: REFERENCE ROWS below). */
+ * quattro_ilqr_iterate_f32, quattro_track_f32) and the other fields of p (barrier, dt, integrator) have no per-trajectory form
+ * (x_ref has one of its own: REFERENCE ROWS below; q, qf and r theirs, for the cart-pole and user models: COST ROWS below). */
 int quattro_ilqr_solve_phys_f32(const quattro_model_params* p, const float* x0, float* x_nom, float* u_nom, int B, int N,
                                 float reg, const float* alphas, int n_alpha, double tol, int max_iter, int flags, float* K,
                                 float* k, double* cost, int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status,
@@ -443,7 +445,7 @@ int quattro_mpc_run_phys_f32(const quattro_model_params* p, float* x_cur, float*
  *                        QUATTRO_SOLVE_ENQUEUE together with rows; every other argument is checked as by the entry each extends.
  * The library still allocates nothing and quattro_model_workspace_bytes keeps its values.  The stand-alone entries
  * (quattro_simulate_f32, quattro_linearize*_f32, quattro_rollout_f32, quattro_linesearch_f32, quattro_ilqr_iterate_f32,
- * quattro_track_f32) have no row form, and neither have the cost weights. */
+ * quattro_track_f32) have no row form.  The cost weights have a per-trajectory form of their own: COST ROWS below. */
 int quattro_ilqr_solve_ref_f32(const quattro_model_params* p, const float* x0, float* x_nom, float* u_nom, int B, int N,
                                float reg, const float* alphas, int n_alpha, double tol, int max_iter, int flags, float* K,
                                float* k, double* cost, int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status,
@@ -456,6 +458,45 @@ int quattro_mpc_run_ref_f32(const quattro_model_params* p, float* x_cur, float* 
                             size_t workspace_bytes, const quattro_model_params* plant, const float* plant_phys, int hold,
                             int feedback, const float* model_phys, const float* x_ref_rows, int ref_rows, int preview,
                             void* stream);
+
+/* COST ROWS: per-trajectory cost weights.  The weights q, qf, r are otherwise the one set of p for the whole batch.  cost_rows
+ * [B][QUATTRO_COST_ROW_FLOATS] (device, fp32, 16-byte aligned; 40 floats a row: q at float 0, qf at float 16, r at float 32 -- p's three
+ * arrays back to back; entries beyond n / m are ignored) lifts that: row b replaces p->q, p->qf and p->r for trajectory (controller)
+ * b wherever the cost is evaluated -- stage cost and total cost of the nominal rollout and of every line-search rollout, l_x, l_xx
+ * (= 2Q), l_u and l_uu (2R plus the barrier's second derivative) of the linearisation, V_x(N) and V_xx(N) (= 2Qf).  barrier_alpha and
+ * barrier_beta, x_ref (unless reference rows are given), dt, the integrator and phys (unless model_phys is given) stay shared; p->q,
+ * p->qf and p->r are ignored.  The weights are constant over the horizon and over a closed-loop run; the tracked steps between
+ * solves (hold, feedback) have no cost and read no row.  A user-compiled model's stage_cost / final_cost see the row as p.q, p.qf,
+ * p.r, so default_stage_cost / default_final_cost follow it.  Rows are used as given: no value is validated, and a row that makes
+ * Q_uu singular or ill-conditioned shows in that trajectory's status bits alone.  The results are those of B calls with B = 1 and
+ * p->q, qf, r = row b, bit for bit.
+ *
+ * quattro_ilqr_solve_cost_f32: the arguments of quattro_ilqr_solve_ref_f32 in their order up to ref_rows, then cost_rows.
+ * quattro_mpc_run_cost_f32: the arguments of quattro_mpc_run_ref_f32 in their order up to preview, then cost_rows.  The log ring,
+ * model_phys, x_ref_rows, plant, plant_phys, hold and feedback all work together with cost_rows.
+ *   cost_rows == NULL : exactly the entry each extends (the same call, the same kernels, the same results).
+ *   cost_rows != NULL : always the model's persistent kernel (csrc/solve_cartpole.hip, csrc/solve_user.hip, their COST
+ *                       instantiations: one for weights alone, one that also takes model_phys and x_ref_rows, either or both).
+ *                       Before any launch: QUATTRO_ERR_UNSUPPORTED for a model without such a kernel -- which includes
+ *                       QUATTRO_MODEL_QUADROTOR, whose persistent kernel has no COST instantiation yet --, QUATTRO_ERR_BAD_ARG
+ *                       for QUATTRO_SOLVE_ENQUEUE together with rows; every other argument is checked as by the entry each
+ *                       extends.
+ * The library still allocates nothing and quattro_model_workspace_bytes keeps its values.  The stand-alone entries
+ * (quattro_simulate_f32, quattro_linearize*_f32, quattro_rollout_f32, quattro_linesearch_f32, quattro_ilqr_iterate_f32,
+ * quattro_track_f32, quattro_total_cost_f32) have no row form; per-step weights, per-trajectory barrier parameters, dt and
+ * integrator have none either. */
+int quattro_ilqr_solve_cost_f32(const quattro_model_params* p, const float* x0, float* x_nom, float* u_nom, int B, int N,
+                                float reg, const float* alphas, int n_alpha, double tol, int max_iter, int flags, float* K,
+                                float* k, double* cost, int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status,
+                                void* workspace, size_t workspace_bytes, const quattro_solve_log* log, const float* model_phys,
+                                const float* x_ref_rows, int ref_rows, const float* cost_rows, void* stream);
+int quattro_mpc_run_cost_f32(const quattro_model_params* p, float* x_cur, float* x_nom, float* u_nom, int B, int N, float reg,
+                             const float* alphas, int n_alpha, double tol, int max_iter, int n_steps, float* traj_x,
+                             float* traj_u, int32_t* traj_iters, const float* disturbance, float* K, float* k, double* cost,
+                             int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status, void* workspace,
+                             size_t workspace_bytes, const quattro_model_params* plant, const float* plant_phys, int hold,
+                             int feedback, const float* model_phys, const float* x_ref_rows, int ref_rows, int preview,
+                             const float* cost_rows, void* stream);
 
 /* Transformer gain predictor: weights of the reference's TransformerPredictor (quattro_ilqr_tf/transformer_model.py:85-138)
  * as DEVICE pointers, plus the DataNormalizer vectors (:15-50).  Matrices are PyTorch Linear layout [out][in];

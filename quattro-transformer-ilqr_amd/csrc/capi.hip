@@ -503,18 +503,26 @@ constexpr int MAX_REF_ROWS = 1 << 20;
 bool ref_ok(const float* x_ref_rows, int ref_rows, int preview) {
   return x_ref_rows == nullptr || (ref_rows >= 1 && ref_rows <= MAX_REF_ROWS && (preview == 0 || preview == 1));
 }
+// cost rows are read by the COST instantiations of the persistent kernels: the cart-pole's and a user model's.  The quadrotor's
+// kernel has none (include/quattro_hip.h, COST ROWS): QUATTRO_ERR_UNSUPPORTED before any launch, like a model without a kernel.
+bool has_cost_kernel(const quattro_model_params* p, const float* cost_rows) {
+  return cost_rows == nullptr || p->model_id != QUATTRO_MODEL_QUADROTOR;
+}
 }  // namespace
 
-// quattro_ilqr_solve_phys_f32 and quattro_ilqr_solve_ref_f32 with at least one of their arrays: always the persistent kernel
+// quattro_ilqr_solve_phys_f32, quattro_ilqr_solve_ref_f32 and quattro_ilqr_solve_cost_f32 with at least one of their arrays: always
+// the persistent kernel
 static int solve_rows(const quattro_model_params* p, const float* x0, float* x_nom, float* u_nom, int B, int N, float reg,
                       const float* alphas, int n_alpha, double tol, int max_iter, int flags, float* K, float* k, double* cost,
                       int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status, void* workspace, size_t workspace_bytes,
-                      const quattro_solve_log* log, const float* model_phys, const float* x_ref_rows, int ref_rows, void* stream) {
-  // the logged entry's checks in its order, then the refusals of these two: the rows are read by the persistent kernels alone
+                      const quattro_solve_log* log, const float* model_phys, const float* x_ref_rows, int ref_rows,
+                      const float* cost_rows, void* stream) {
+  // the logged entry's checks in its order, then the refusals of these three: the rows are read by the persistent kernels alone
   const bool args_ok = iters && max_iter >= 0 && !((flags & QUATTRO_SOLVE_SIMULATE) && !x0) && log_ok(log) &&
                        ref_ok(x_ref_rows, ref_rows, 1);
   int entry_rc = QUATTRO_ERR_BAD_ARG;
-  if (args_ok && !(flags & QUATTRO_SOLVE_ENQUEUE)) entry_rc = quattro_model_has_device_loop(p) ? QUATTRO_OK : QUATTRO_ERR_UNSUPPORTED;
+  if (args_ok && !(flags & QUATTRO_SOLVE_ENQUEUE))
+    entry_rc = p && quattro_model_has_device_loop(p) && has_cost_kernel(p, cost_rows) ? QUATTRO_OK : QUATTRO_ERR_UNSUPPORTED;
   WorkspacePlan w;
   const int rc = check_solve_args(p, x_nom, u_nom, B, N, alphas, n_alpha, K, k, cost, alpha_idx, active, entry_rc, workspace,
                                   workspace_bytes, &w);
@@ -526,6 +534,7 @@ static int solve_rows(const quattro_model_params* p, const float* x0, float* x_n
   loop.x_ref_rows = x_ref_rows;      // (a plain solve is one plan from step 0 that looks ahead: row min(t, ref_rows - 1))
   loop.ref_rows = ref_rows;
   loop.preview = 1;
+  loop.cost_rows = cost_rows;
   return launch_device_loop(*p, loop, w, (char*)workspace, (hipStream_t)stream);
 }
 
@@ -538,7 +547,7 @@ int quattro_ilqr_solve_phys_f32(const quattro_model_params* p, const float* x0, 
     return quattro_ilqr_solve_logged_f32(p, x0, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, flags, K, k, cost,
                                          alpha_idx, active, iters, status, workspace, workspace_bytes, log, stream);
   return solve_rows(p, x0, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, flags, K, k, cost, alpha_idx, active, iters,
-                    status, workspace, workspace_bytes, log, model_phys, nullptr, 0, stream);
+                    status, workspace, workspace_bytes, log, model_phys, nullptr, 0, nullptr, stream);
 }
 
 int quattro_ilqr_solve_ref_f32(const quattro_model_params* p, const float* x0, float* x_nom, float* u_nom, int B, int N,
@@ -550,7 +559,20 @@ int quattro_ilqr_solve_ref_f32(const quattro_model_params* p, const float* x0, f
     return quattro_ilqr_solve_phys_f32(p, x0, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, flags, K, k, cost,
                                        alpha_idx, active, iters, status, workspace, workspace_bytes, log, model_phys, stream);
   return solve_rows(p, x0, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, flags, K, k, cost, alpha_idx, active, iters,
-                    status, workspace, workspace_bytes, log, model_phys, x_ref_rows, ref_rows, stream);
+                    status, workspace, workspace_bytes, log, model_phys, x_ref_rows, ref_rows, nullptr, stream);
+}
+
+int quattro_ilqr_solve_cost_f32(const quattro_model_params* p, const float* x0, float* x_nom, float* u_nom, int B, int N,
+                                float reg, const float* alphas, int n_alpha, double tol, int max_iter, int flags, float* K,
+                                float* k, double* cost, int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status,
+                                void* workspace, size_t workspace_bytes, const quattro_solve_log* log, const float* model_phys,
+                                const float* x_ref_rows, int ref_rows, const float* cost_rows, void* stream) {
+  if (cost_rows == nullptr)
+    return quattro_ilqr_solve_ref_f32(p, x0, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, flags, K, k, cost, alpha_idx,
+                                      active, iters, status, workspace, workspace_bytes, log, model_phys, x_ref_rows, ref_rows,
+                                      stream);
+  return solve_rows(p, x0, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, flags, K, k, cost, alpha_idx, active, iters,
+                    status, workspace, workspace_bytes, log, model_phys, x_ref_rows, ref_rows, cost_rows, stream);
 }
 
 int quattro_ilqr_solve_f32(const quattro_model_params* p, const float* x0, float* x_nom, float* u_nom, int B, int N,
@@ -584,21 +606,22 @@ int quattro_mpc_run_f32(const quattro_model_params* p, float* x_cur, float* x_no
   return launch_device_loop(*p, loop, w, (char*)workspace, (hipStream_t)stream);
 }
 
-// quattro_mpc_run_plant_f32 (model_phys == NULL, x_ref_rows == NULL: the run as it always was), quattro_mpc_run_phys_f32 and
-// quattro_mpc_run_ref_f32
+// quattro_mpc_run_plant_f32 (model_phys == NULL, x_ref_rows == NULL, cost_rows == NULL: the run as it always was),
+// quattro_mpc_run_phys_f32, quattro_mpc_run_ref_f32 and quattro_mpc_run_cost_f32
 static int mpc_run_plant(const quattro_model_params* p, float* x_cur, float* x_nom, float* u_nom, int B, int N, float reg,
                          const float* alphas, int n_alpha, double tol, int max_iter, int n_steps, float* traj_x, float* traj_u,
                          int32_t* traj_iters, const float* disturbance, float* K, float* k, double* cost, int32_t* alpha_idx,
                          int32_t* active, int32_t* iters, int32_t* status, void* workspace, size_t workspace_bytes,
                          const quattro_model_params* plant, const float* plant_phys, int hold, int feedback,
-                         const float* model_phys, const float* x_ref_rows, int ref_rows, int preview, void* stream) {
+                         const float* model_phys, const float* x_ref_rows, int ref_rows, int preview, const float* cost_rows,
+                         void* stream) {
   const bool args_ok = x_cur && iters && traj_x && traj_u && traj_iters && max_iter >= 0 && n_steps > 0 && hold >= 1 && hold <= N &&
                        n_steps % hold == 0 && !(feedback && max_iter < 1) && ref_ok(x_ref_rows, ref_rows, preview);
   PlantSpec ps{};
   int entry_rc = QUATTRO_ERR_BAD_ARG;
   if (args_ok && model_ok(p)) {
     entry_rc = plant_spec(p, plant, &ps);
-    if (entry_rc == QUATTRO_OK && !quattro_model_has_device_loop(p)) entry_rc = QUATTRO_ERR_UNSUPPORTED;
+    if (entry_rc == QUATTRO_OK && !(quattro_model_has_device_loop(p) && has_cost_kernel(p, cost_rows))) entry_rc = QUATTRO_ERR_UNSUPPORTED;
   }
   WorkspacePlan w;
   const int rc = check_solve_args(p, x_nom, u_nom, B, N, alphas, n_alpha, K, k, cost, alpha_idx, active, entry_rc, workspace,
@@ -623,6 +646,7 @@ static int mpc_run_plant(const quattro_model_params* p, float* x_cur, float* x_n
   loop.x_ref_rows = x_ref_rows;
   loop.ref_rows = ref_rows;
   loop.preview = preview;
+  loop.cost_rows = cost_rows;
   return launch_device_loop(*p, loop, w, (char*)workspace, (hipStream_t)stream);
 }
 
@@ -634,7 +658,7 @@ int quattro_mpc_run_plant_f32(const quattro_model_params* p, float* x_cur, float
                               int feedback, void* stream) {
   return mpc_run_plant(p, x_cur, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, n_steps, traj_x, traj_u, traj_iters,
                        disturbance, K, k, cost, alpha_idx, active, iters, status, workspace, workspace_bytes, plant, plant_phys, hold,
-                       feedback, nullptr, nullptr, 0, 0, stream);
+                       feedback, nullptr, nullptr, 0, 0, nullptr, stream);
 }
 
 int quattro_mpc_run_phys_f32(const quattro_model_params* p, float* x_cur, float* x_nom, float* u_nom, int B, int N, float reg,
@@ -649,7 +673,7 @@ int quattro_mpc_run_phys_f32(const quattro_model_params* p, float* x_cur, float*
                                      workspace_bytes, plant, plant_phys, hold, feedback, stream);
   return mpc_run_plant(p, x_cur, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, n_steps, traj_x, traj_u, traj_iters,
                        disturbance, K, k, cost, alpha_idx, active, iters, status, workspace, workspace_bytes, plant, plant_phys, hold,
-                       feedback, model_phys, nullptr, 0, 0, stream);
+                       feedback, model_phys, nullptr, 0, 0, nullptr, stream);
 }
 
 int quattro_mpc_run_ref_f32(const quattro_model_params* p, float* x_cur, float* x_nom, float* u_nom, int B, int N, float reg,
@@ -665,7 +689,24 @@ int quattro_mpc_run_ref_f32(const quattro_model_params* p, float* x_cur, float* 
                                     workspace_bytes, plant, plant_phys, hold, feedback, model_phys, stream);
   return mpc_run_plant(p, x_cur, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, n_steps, traj_x, traj_u, traj_iters,
                        disturbance, K, k, cost, alpha_idx, active, iters, status, workspace, workspace_bytes, plant, plant_phys, hold,
-                       feedback, model_phys, x_ref_rows, ref_rows, preview, stream);
+                       feedback, model_phys, x_ref_rows, ref_rows, preview, nullptr, stream);
+}
+
+int quattro_mpc_run_cost_f32(const quattro_model_params* p, float* x_cur, float* x_nom, float* u_nom, int B, int N, float reg,
+                             const float* alphas, int n_alpha, double tol, int max_iter, int n_steps, float* traj_x,
+                             float* traj_u, int32_t* traj_iters, const float* disturbance, float* K, float* k, double* cost,
+                             int32_t* alpha_idx, int32_t* active, int32_t* iters, int32_t* status, void* workspace,
+                             size_t workspace_bytes, const quattro_model_params* plant, const float* plant_phys, int hold,
+                             int feedback, const float* model_phys, const float* x_ref_rows, int ref_rows, int preview,
+                             const float* cost_rows, void* stream) {
+  if (cost_rows == nullptr)
+    return quattro_mpc_run_ref_f32(p, x_cur, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, n_steps, traj_x, traj_u,
+                                   traj_iters, disturbance, K, k, cost, alpha_idx, active, iters, status, workspace,
+                                   workspace_bytes, plant, plant_phys, hold, feedback, model_phys, x_ref_rows, ref_rows, preview,
+                                   stream);
+  return mpc_run_plant(p, x_cur, x_nom, u_nom, B, N, reg, alphas, n_alpha, tol, max_iter, n_steps, traj_x, traj_u, traj_iters,
+                       disturbance, K, k, cost, alpha_idx, active, iters, status, workspace, workspace_bytes, plant, plant_phys, hold,
+                       feedback, model_phys, x_ref_rows, ref_rows, preview, cost_rows, stream);
 }
 
 int quattro_track_f32(const quattro_model_params* p, const quattro_model_params* plant, const float* plant_phys, const float* x0,

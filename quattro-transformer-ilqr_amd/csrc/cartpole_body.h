@@ -121,6 +121,8 @@ struct LaneRec {
 // OWN (the persistent loop with per-trajectory parameters): p is this row's private block — the kernel's with the row's phys — and
 // `shared` the kernel-argument block it was copied from.  The one lane-indexed read of the sweep (the terminal weight qf[i]) goes
 // to `shared`, whose cost fields are the same: a private block indexed by lane is kept whole in scratch memory (292 B per lane).
+// qf_own (the persistent loop with per-trajectory cost weights): the row's own qf[0..3] in global memory, where that read goes
+// instead -- `shared` holds the batch's weights, not the row's.
 // ref(t): called by the lane that is about to form the record of step t, and by every lane before the terminal pair (t = N) — the
 // persistent loop with reference rows puts the step's row into the private block (solve_loop.h: set_ref_row); NoRef: nothing.
 template <bool RK4, bool OWN = false, class Ref = NoRef>
@@ -129,7 +131,8 @@ __device__ __forceinline__ void sweep16_cartpole_body(const quattro_model_params
                                                       float* __restrict__ Kout, float* __restrict__ kout,
                                                       int32_t* __restrict__ status, const int b, const bool live,
                                                       const int lane, float* stage, const int k_rows = 0,
-                                                      const quattro_model_params* shared = nullptr, Ref ref = Ref()) {
+                                                      const quattro_model_params* shared = nullptr, Ref ref = Ref(),
+                                                      const float* __restrict__ qf_own = nullptr) {
   using namespace cp16;
   constexpr int NX = 4;
   const int sub = lane & 15, i = sub >> 2, j = sub & 3, row0 = lane & 48;
@@ -151,7 +154,7 @@ __device__ __forceinline__ void sweep16_cartpole_body(const quattro_model_params
     ref(N);
 #pragma unroll
     for (int c = 0; c < NX; ++c) vx[c] = qt_terminal_vx(p, c, xn[c]);
-    if constexpr (OWN) Vij = (i == j) ? qt_terminal_vxx(*shared, i) : 0.0f;
+    if constexpr (OWN) Vij = (i == j) ? (qf_own != nullptr ? qt_terminal_vxx(qf_own, i) : qt_terminal_vxx(*shared, i)) : 0.0f;
     else Vij = (i == j) ? qt_terminal_vxx(p, i) : 0.0f;
   }
   bool bad = false, singular = false;

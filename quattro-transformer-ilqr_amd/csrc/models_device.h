@@ -278,6 +278,9 @@ __device__ __forceinline__ float qt_terminal_vx(const quattro_model_params& p, i
   return 2.0f * p.qf[i] * (xi - p.x_ref[i]);
 }
 __device__ __forceinline__ float qt_terminal_vxx(const quattro_model_params& p, int i) { return 2.0f * p.qf[i]; }
+// the same entry from a Qf diagonal that is not the block's (a trajectory's row of cost weights, solve_loop.h: cost_rows).  THE
+// formula is the line above; this restates it rather than have that one forward here, so that the kernels which call it keep their code.
+__device__ __forceinline__ float qt_terminal_vxx(const float* qf, int i) { return 2.0f * qf[i]; }
 
 // ------------------------------------------------------------------------------------------------ linearisation
 // Record fillers for the Euler discretisation (A = I + dt Jx, B = dt Ju).  `fill_const` writes every entry that

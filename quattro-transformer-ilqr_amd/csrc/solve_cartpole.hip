@@ -28,7 +28,9 @@ struct CpSolveArgs {
 // trajectory's model — nominal rollout, records, terminal pair, line search — on a block whose phys is its row of c.model_phys
 // REF (with PLANT only, like PHYS): the cost of horizon step t is taken against the row of c.x_ref_rows that step reads
 // (qt_ref_row): the row's private block gets it as x_ref before every stage cost, record and terminal pair (set_ref_row)
-template <bool RK4, bool PLANT, bool PHYS, bool REF>
+// COST (with PLANT only; alone, or with PHYS and REF together, each of which then also runs without its array: trajectory_params,
+// rows_given): the private block's q, qf and r are the trajectory's row of c.cost_rows, so every cost evaluated on that block follows
+template <bool RK4, bool PLANT, bool PHYS, bool REF, bool COST>
 __global__ __launch_bounds__(QT_WAVE) void solve_cartpole_kernel(const CpSolveArgs a) {
   constexpr int MODEL = QUATTRO_MODEL_CARTPOLE, NX = 4;
   __shared__ __attribute__((aligned(16))) float s_stage[4 * cp16::STAGE_FLOATS];
@@ -42,11 +44,13 @@ __global__ __launch_bounds__(QT_WAVE) void solve_cartpole_kernel(const CpSolveAr
   const int N = c.N;
   float* stage = s_stage + (lane >> 4) * cp16::STAGE_FLOATS;
   quattro_model_params own;
-  const quattro_model_params& mp = trajectory_params<PHYS, REF>(a.p, c, bb, own);
+  const quattro_model_params& mp = trajectory_params<PHYS, REF, COST>(a.p, c, bb, own);
   const int n_ctrl = c.n_ctrl > 0 ? c.n_ctrl : 1;
   for (int cs = 0; cs < n_ctrl; ++cs) {
     auto ref = [&](int t) __attribute__((always_inline)) {
-      if constexpr (REF) set_ref_row<NX>(own, plan_ref_rows(c, cs), bb, t);
+      if constexpr (REF) {
+        if (rows_given<REF, COST>(c)) set_ref_row<NX>(own, plan_ref_rows(c, cs), bb, t);
+      }
     };
     wave_step_prologue<NX, PLANT>(c, bb, cs, have && sub == 0,
                            [&] { simulate_body<MODEL, RK4>(mp, c.x0, c.u, N, c.x, c.cost, b, ref); });
@@ -59,7 +63,8 @@ __global__ __launch_bounds__(QT_WAVE) void solve_cartpole_kernel(const CpSolveAr
         log_it = c.iters[bb];
         log_begin(c.log, b, log_it, c.x + bb * (N + 1) * NX, c.u + bb * N, c.cost[bb], sub, 16);
       }
-      sweep16_cartpole_body<RK4, PHYS || REF>(mp, c.x, c.u, N, 0, c.reg, c.K, c.k, c.status, b, act, lane, stage, 0, &a.p, ref);
+      sweep16_cartpole_body<RK4, PHYS || REF || COST>(mp, c.x, c.u, N, 0, c.reg, c.K, c.k, c.status, b, act, lane, stage, 0, &a.p, ref,
+                                                      COST ? c.cost_rows + bb * QUATTRO_COST_ROW_FLOATS + QUATTRO_MAX_NX : nullptr);
       if (logging && act && sub == 0) log_stamp(c.log, b, log_it, 1, 2);
       wave_handoff();
       linesearch_body<MODEL, RK4, 16>(mp, c.x, c.u, c.K, c.k, c.al, c.n_alpha, c.B, N, c.tol, c.cost, c.alpha_idx, c.active,
@@ -85,16 +90,19 @@ int quattro_launch_solve_cartpole(const quattro_model_params& p, const SolveLoop
   if (p.integrator != QUATTRO_INTEGRATOR_EULER && p.integrator != QUATTRO_INTEGRATOR_RK4) return QUATTRO_ERR_UNSUPPORTED;
   const bool rk4 = p.integrator == QUATTRO_INTEGRATOR_RK4;
   // (c.x_ref_rows: the two ref entries alone set it; c.model_phys: they and the two phys entries; c.hold: the plant run and those)
-#define QT_LAUNCH(PLANT, PHYS, REF)                                                                                     \
+#define QT_LAUNCH(PLANT, PHYS, REF, COST)                                                                                     \
   do {                                                                                                                  \
-    if (rk4) hipLaunchKernelGGL((solve_cartpole_kernel<true, PLANT, PHYS, REF>), grid, dim3(QT_WAVE), 0, stream, a);    \
-    else hipLaunchKernelGGL((solve_cartpole_kernel<false, PLANT, PHYS, REF>), grid, dim3(QT_WAVE), 0, stream, a);       \
+    if (rk4) hipLaunchKernelGGL((solve_cartpole_kernel<true, PLANT, PHYS, REF, COST>), grid, dim3(QT_WAVE), 0, stream, a);    \
+    else hipLaunchKernelGGL((solve_cartpole_kernel<false, PLANT, PHYS, REF, COST>), grid, dim3(QT_WAVE), 0, stream, a);       \
   } while (0)
-  if (c.x_ref_rows != nullptr && c.model_phys != nullptr) QT_LAUNCH(true, true, true);
-  else if (c.x_ref_rows != nullptr) QT_LAUNCH(true, false, true);
-  else if (c.model_phys != nullptr) QT_LAUNCH(true, true, false);
-  else if (c.hold > 0) QT_LAUNCH(true, false, false);
-  else QT_LAUNCH(false, false, false);
+  // (c.cost_rows: the two cost entries alone set it; weights alone have a kernel of their own, weights with either array share one)
+  if (c.cost_rows != nullptr && (c.x_ref_rows != nullptr || c.model_phys != nullptr)) QT_LAUNCH(true, true, true, true);
+  else if (c.cost_rows != nullptr) QT_LAUNCH(true, false, false, true);
+  else if (c.x_ref_rows != nullptr && c.model_phys != nullptr) QT_LAUNCH(true, true, true, false);
+  else if (c.x_ref_rows != nullptr) QT_LAUNCH(true, false, true, false);
+  else if (c.model_phys != nullptr) QT_LAUNCH(true, true, false, false);
+  else if (c.hold > 0) QT_LAUNCH(true, false, false, false);
+  else QT_LAUNCH(false, false, false, false);
 #undef QT_LAUNCH
   return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;
 }

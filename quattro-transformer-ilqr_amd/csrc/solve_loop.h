@@ -44,6 +44,10 @@ struct SolveLoop {
   // at plant step s (qt_ref_row, quattro_device.h).  A plain solve has s = 0 and preview = 1.  NULL: none.
   const float* x_ref_rows;    // [B][ref_rows][n]
   int ref_rows, preview;
+  // per-trajectory cost weights (quattro_ilqr_solve_cost_f32, quattro_mpc_run_cost_f32; the COST instantiations of the kernels): row b
+  // (q at float 0, qf at float 16, r at float 32: the parameter block's three arrays, back to back) replaces the block's q, qf and r wherever the cost of
+  // trajectory b is evaluated, constant over the horizon and over a run.  NULL: none.
+  const float* cost_rows;     // [B][QUATTRO_COST_ROW_FLOATS]
 };
 
 namespace {
@@ -59,10 +63,35 @@ __device__ __forceinline__ int traj_steps(const SolveLoop& c) {
 // bb of c.model_phys, taken as values (the cart-pole's four rows of a wave hold four different sets; a user model's wave one);
 // otherwise the kernel's block itself, and `own` is never touched.  REF without PHYS: `own` as a plain copy, whose x_ref set_ref_row
 // then rewrites step by step.
-template <bool PHYS, bool REF = false>
+// COST: `own` with q, qf and r of row bb of c.cost_rows, taken as values like phys.  COST is instantiated alone and with PHYS and REF
+// together; in the latter a NULL c.model_phys leaves the copy's phys what the kernel's block holds (a wave-uniform branch around the
+// row's loads: values either way, never a pointer into one block or the other), and a NULL c.x_ref_rows its x_ref (rows_given).
+template <bool PHYS, bool REF = false, bool COST = false>
 __device__ __forceinline__ const quattro_model_params& trajectory_params(const quattro_model_params& p, const SolveLoop& c,
                                                                          const size_t bb, quattro_model_params& own) {
-  if constexpr (PHYS) {
+  if constexpr (COST) {
+    float w[QUATTRO_COST_ROW_FLOATS];
+#pragma unroll
+    for (int i = 0; i < QUATTRO_COST_ROW_FLOATS; ++i) w[i] = c.cost_rows[bb * QUATTRO_COST_ROW_FLOATS + i];
+    own = p;
+    if constexpr (PHYS) {
+      if (c.model_phys != nullptr) {
+        float ph[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) ph[i] = c.model_phys[bb * 8 + i];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) own.phys[i] = ph[i];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < QUATTRO_MAX_NX; ++i) {
+      own.q[i] = w[i];
+      own.qf[i] = w[QUATTRO_MAX_NX + i];
+    }
+#pragma unroll
+    for (int i = 0; i < QUATTRO_MAX_NU; ++i) own.r[i] = w[2 * QUATTRO_MAX_NX + i];
+    return own;
+  } else if constexpr (PHYS) {
     float ph[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) ph[i] = c.model_phys[bb * 8 + i];
@@ -76,6 +105,15 @@ __device__ __forceinline__ const quattro_model_params& trajectory_params(const q
   } else {
     return p;
   }
+}
+
+// REF: whether this launch has reference rows to read.  Without COST the REF kernels run with rows only; the COST kernel that
+// carries REF also runs without (wave-uniform).
+template <bool REF, bool COST>
+__device__ __forceinline__ bool rows_given(const SolveLoop& c) {
+  if constexpr (!REF) return false;
+  else if constexpr (COST) return c.x_ref_rows != nullptr;
+  else return true;
 }
 
 // The rows of c.x_ref_rows as plan cs of the loop reads them (cs = 0 in a plain solve, where c.hold is 0 too)

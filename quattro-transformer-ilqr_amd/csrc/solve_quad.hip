@@ -302,6 +302,7 @@ int quattro_launch_solve_quad(const quattro_model_params& p, const SolveLoop& c,
                               int stamp_rows, hipStream_t stream) {
   if (p.integrator != QUATTRO_INTEGRATOR_EULER && p.integrator != QUATTRO_INTEGRATOR_RK4) return QUATTRO_ERR_UNSUPPORTED;
   if (p.integrator == QUATTRO_INTEGRATOR_RK4 && coef == nullptr) return QUATTRO_ERR_WORKSPACE;
+  if (c.cost_rows != nullptr) return QUATTRO_ERR_UNSUPPORTED;      // (no COST instantiation of this kernel: capi.hip refuses first)
   SolveArgs a;
   a.fa = fused_args(p, c.x, c.u, c.B, c.N, 0, coef, 0);     // (coef: the RK4 sweep's coefficient scratch, B * N * 132 floats)
   a.c = c;

@@ -52,7 +52,9 @@ struct UserSolveArgs {
 // REF (with PLANT only, like PHYS): the cost of horizon step t is taken against the row of c.x_ref_rows that step reads
 // (qt_ref_row): the wave's private block gets it as x_ref before every stage cost, record and terminal row (set_ref_row), so the
 // model's stage_cost / final_cost see it as p.x_ref, whatever they do with it
-template <bool RK4, bool PLANT, bool PHYS, bool REF>
+// COST (with PLANT only; alone, or with PHYS and REF together, each of which then also runs without its array: trajectory_params,
+// rows_given): the private block's q, qf and r are the trajectory's row of c.cost_rows, so every cost evaluated on that block follows
+template <bool RK4, bool PLANT, bool PHYS, bool REF, bool COST>
 __global__ __launch_bounds__(QT_WAVE, 2) void solve_user_kernel(const UserSolveArgs a) {
   constexpr int MODEL = QUATTRO_MODEL_USER, NX = QT_USER_NX, NU = QT_USER_NU, NZ = NX + NU;
   constexpr int LPI = NZ <= 8 ? 8 : (NZ <= 16 ? 16 : 32), IPP = QT_WAVE / LPI;      // lanes per item, items per pass
@@ -74,11 +76,13 @@ __global__ __launch_bounds__(QT_WAVE, 2) void solve_user_kernel(const UserSolveA
   float* recb = a.rec + bb * N * R::STRIDE;
   volatile int32_t* act_flag = c.active + b;     // written by this wave's line search: always re-read from memory
   quattro_model_params own;
-  const quattro_model_params& mp = trajectory_params<PHYS, REF>(a.p, c, bb, own);
+  const quattro_model_params& mp = trajectory_params<PHYS, REF, COST>(a.p, c, bb, own);
   const int n_ctrl = c.n_ctrl > 0 ? c.n_ctrl : 1;
   for (int cs = 0; cs < n_ctrl; ++cs) {
     auto ref = [&](int t) __attribute__((always_inline)) {
-      if constexpr (REF) set_ref_row<NX>(own, plan_ref_rows(c, cs), bb, t);
+      if constexpr (REF) {
+        if (rows_given<REF, COST>(c)) set_ref_row<NX>(own, plan_ref_rows(c, cs), bb, t);
+      }
     };
     wave_step_prologue<NX, PLANT>(c, bb, cs, lane == 0, [&] { simulate_body<MODEL, RK4>(mp, c.x0, c.u, N, c.x, c.cost, b, ref); });
     const bool logging = c.log.rec != nullptr && c.n_ctrl == 0;
@@ -192,16 +196,19 @@ int quattro_launch_solve_user(const quattro_model_params& p, const SolveLoop& c,
   if (p.integrator != QUATTRO_INTEGRATOR_EULER && p.integrator != QUATTRO_INTEGRATOR_RK4) return QUATTRO_ERR_UNSUPPORTED;
   const bool rk4 = p.integrator == QUATTRO_INTEGRATOR_RK4;
   // (c.x_ref_rows: the two ref entries alone set it; c.model_phys: they and the two phys entries; c.hold: the plant run and those)
-#define QT_LAUNCH(PLANT, PHYS, REF)                                                                                 \
+#define QT_LAUNCH(PLANT, PHYS, REF, COST)                                                                                 \
   do {                                                                                                              \
-    if (rk4) hipLaunchKernelGGL((solve_user_kernel<true, PLANT, PHYS, REF>), grid, dim3(QT_WAVE), 0, stream, a);    \
-    else hipLaunchKernelGGL((solve_user_kernel<false, PLANT, PHYS, REF>), grid, dim3(QT_WAVE), 0, stream, a);       \
+    if (rk4) hipLaunchKernelGGL((solve_user_kernel<true, PLANT, PHYS, REF, COST>), grid, dim3(QT_WAVE), 0, stream, a);    \
+    else hipLaunchKernelGGL((solve_user_kernel<false, PLANT, PHYS, REF, COST>), grid, dim3(QT_WAVE), 0, stream, a);       \
   } while (0)
-  if (c.x_ref_rows != nullptr && c.model_phys != nullptr) QT_LAUNCH(true, true, true);
-  else if (c.x_ref_rows != nullptr) QT_LAUNCH(true, false, true);
-  else if (c.model_phys != nullptr) QT_LAUNCH(true, true, false);
-  else if (c.hold > 0) QT_LAUNCH(true, false, false);
-  else QT_LAUNCH(false, false, false);
+  // (c.cost_rows: the two cost entries alone set it; weights alone have a kernel of their own, weights with either array share one)
+  if (c.cost_rows != nullptr && (c.x_ref_rows != nullptr || c.model_phys != nullptr)) QT_LAUNCH(true, true, true, true);
+  else if (c.cost_rows != nullptr) QT_LAUNCH(true, false, false, true);
+  else if (c.x_ref_rows != nullptr && c.model_phys != nullptr) QT_LAUNCH(true, true, true, false);
+  else if (c.x_ref_rows != nullptr) QT_LAUNCH(true, false, true, false);
+  else if (c.model_phys != nullptr) QT_LAUNCH(true, true, false, false);
+  else if (c.hold > 0) QT_LAUNCH(true, false, false, false);
+  else QT_LAUNCH(false, false, false, false);
 #undef QT_LAUNCH
   return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;
 }

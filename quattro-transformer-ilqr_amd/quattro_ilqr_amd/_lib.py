@@ -122,6 +122,9 @@ SIGNATURES = {
     "quattro_ilqr_solve_ref_f32": (c_int, [POINTER(ModelParams), _P, _P, _P, c_int, c_int, c_float, POINTER(c_float), c_int,
                                            c_double, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t,
                                            POINTER(SolveLogC), _P, _P, c_int, _P]),
+    "quattro_ilqr_solve_cost_f32": (c_int, [POINTER(ModelParams), _P, _P, _P, c_int, c_int, c_float, POINTER(c_float), c_int,
+                                            c_double, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t,
+                                            POINTER(SolveLogC), _P, _P, c_int, _P, _P]),
     "quattro_solve_log_record_f32": (c_int, [POINTER(SolveLogC), c_int, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int,
                                              c_int, c_int, _P]),
     "quattro_mpc_run_f32": (c_int, [POINTER(ModelParams), _P, _P, _P, c_int, c_int, c_float, POINTER(c_float), c_int,
@@ -137,6 +140,9 @@ SIGNATURES = {
     "quattro_mpc_run_ref_f32": (c_int, [POINTER(ModelParams), _P, _P, _P, c_int, c_int, c_float, POINTER(c_float), c_int,
                                         c_double, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t,
                                         POINTER(ModelParams), _P, c_int, c_int, _P, _P, c_int, c_int, _P]),
+    "quattro_mpc_run_cost_f32": (c_int, [POINTER(ModelParams), _P, _P, _P, c_int, c_int, c_float, POINTER(c_float), c_int,
+                                         c_double, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t,
+                                         POINTER(ModelParams), _P, c_int, c_int, _P, _P, c_int, c_int, _P, _P]),
     "quattro_tf_stream_elems": (c_size_t, [POINTER(TfWeights)]),
     "quattro_tf_param_floats": (c_size_t, [POINTER(TfWeights)]),
     "quattro_tf_pack_stream_bf16": (c_int, [POINTER(TfWeights), _P, _P, _P]),

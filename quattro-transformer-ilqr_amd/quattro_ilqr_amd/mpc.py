@@ -219,21 +219,23 @@ class BatchedMPC:
         self.device = self.solver.device
         self.u_warm = None                      # (B, N, m) warm start for the next control step
 
-    def control_step(self, x_current, x_ref=None, model_phys=None, targets=None):
+    def control_step(self, x_current, x_ref=None, model_phys=None, targets=None, weights=None):
         """x_current (B, n) -> (x_seq (B,N+1,n), u_seq (B,N,m), iters (B,)) as fresh device tensors; keeps the shifted
         control sequence as the next warm start.  model_phys: per-controller model parameters, as in QuattroILQR.solve.
         targets: per-controller, per-step state targets of THIS solve, as in QuattroILQR.solve (row min(t, R - 1) at horizon step
         t); x_ref: handed to the solver as it is — the predictor's input in hybrid mode, nothing in pure mode; a target for the
-        cost is `targets`."""
+        cost is `targets`.  weights: per-controller cost weights of THIS solve, as in QuattroILQR.solve."""
         if model_phys is not None:
             self.solver._check_model_phys(model_phys, int(np.prod(tuple(np.shape(x_current)))) // self.model.n)
         if targets is not None:
             self.solver._check_targets(targets, int(np.prod(tuple(np.shape(x_current)))) // self.model.n)
+        if weights is not None:
+            self.solver._check_weights(weights, int(np.prod(tuple(np.shape(x_current)))) // self.model.n)
         x_current = torch.as_tensor(x_current, dtype=torch.float32, device=self.device).reshape(-1, self.model.n)
         B = x_current.shape[0]
         if self.u_warm is not None and self.u_warm.shape[0] != B:
             raise ValueError("batch size changed between control steps")
-        out = self.solver.solve(x_current, self.u_warm, x_ref=x_ref, model_phys=model_phys, targets=targets)
+        out = self.solver.solve(x_current, self.u_warm, x_ref=x_ref, model_phys=model_phys, targets=targets, weights=weights)
         u = out["u"]
         self.u_warm = torch.cat([u[:, 1:], u[:, -1:]], dim=1).contiguous()
         return out["x"].clone(), u.clone(), out["iters"].clone()
@@ -244,7 +246,7 @@ class BatchedMPC:
         return xs[:, 1].contiguous()
 
     def run(self, x0, steps, disturbance=None, device_loop=True, *, plant=None, plant_phys=None, replan_every=1, feedback=False,
-            model_phys=None, targets=None, preview=True):
+            model_phys=None, targets=None, preview=True, weights=None):
         """Closed loop for `steps` control steps from x0 (B,n); the plant is the device model itself (the reference's
         plant is MuJoCo, out of scope), plus an optional additive state disturbance tensor (steps, B, n).
         Returns dict(x (B,steps+1,n), u (B,steps,m), iters (B,steps)).
@@ -281,7 +283,16 @@ class BatchedMPC:
         preview=False: a set-point schedule, known at replan time only and constant inside a solve, as the reference's
         simulator moves mpc_controller.x_ref between control steps.  Past its last row a controller holds that row.  The tracked
         steps between solves follow the plan as above; they have no cost and read no rows.  One launch (quattro_mpc_run_ref_f32);
-        the kernel rule, refusals and their order are model_phys's, with which — and with the plant keywords — it combines."""
+        the kernel rule, refusals and their order are model_phys's, with which — and with the plant keywords — it combines.
+
+        weights: per-controller cost weights, constant over the run — a dict with any of "q", "qf", "r" (each (B, n) / (B, n) /
+        (B, m), or one vector for the whole batch; a missing key keeps the model's), a plain (B, 2n + m) array [q | qf | r], or the
+        device tensor of ops.cost_rows_tensor.  Controller b PLANS with row b in place of model.q, qf and r in every solve of the
+        run: B candidate weightings of one controller against one plant, or a fleet with different priorities.  The tracked steps
+        have no cost.  To compare candidates, score the returned x, u with ops.total_cost under ONE evaluation cost.  One launch
+        (quattro_mpc_run_cost_f32); the kernel rule, refusals and their order are model_phys's, with which — and with targets and
+        the plant keywords — it combines.  Cart-pole and user-compiled models; the built-in quadrotor's kernel has no such form yet
+        (NotImplementedError, like a model without a persistent kernel)."""
         h = int(replan_every)
         if model_phys is not None:
             if not device_loop:
@@ -291,7 +302,12 @@ class BatchedMPC:
             if not device_loop:
                 raise NotImplementedError("targets runs only in the device-resident loop: device_loop=False is the host-driven loop")
             self.solver._check_targets(targets, int(np.prod(tuple(np.shape(x0)))) // self.model.n)
-        plain = plant is None and plant_phys is None and h == 1 and not feedback and model_phys is None and targets is None
+        if weights is not None:
+            if not device_loop:
+                raise NotImplementedError("weights runs only in the device-resident loop: device_loop=False is the host-driven loop")
+            self.solver._check_weights(weights, int(np.prod(tuple(np.shape(x0)))) // self.model.n)
+        plain = (plant is None and plant_phys is None and h == 1 and not feedback and model_phys is None and targets is None
+                 and weights is None)
         if not plain:
             ops.check_plant(self.model, plant)
             if h < 1 or h > self.horizon or steps % h != 0:
@@ -304,7 +320,8 @@ class BatchedMPC:
                 raise ValueError("feedback needs gains: max_iter >= 1")
         x = torch.as_tensor(x0, dtype=torch.float32, device=self.device).reshape(-1, self.model.n).contiguous()
         sv = self.solver
-        use_kernel = (ops.model_can_device_loop(self.model) if device_loop == "always" or model_phys is not None or targets is not None
+        rows = model_phys is not None or targets is not None or weights is not None
+        use_kernel = (ops.model_can_device_loop(self.model) if device_loop == "always" or rows
                       else bool(device_loop) and ops.model_has_device_loop(self.model))
         if not plain:
             plant_phys = ops.plant_phys_tensor(self.model, plant_phys, x.shape[0], self.device)
@@ -329,7 +346,8 @@ class BatchedMPC:
             extra = {} if plain else dict(plant=plant, plant_phys=plant_phys, hold=h, feedback=feedback,
                                           model_phys=ops.model_phys_tensor(self.model, model_phys, B, self.device),
                                           x_ref_rows=ops.x_ref_rows_tensor(self.model, targets, B, self.device),
-                                          preview=bool(preview))
+                                          preview=bool(preview),
+                                          cost_rows=ops.cost_rows_tensor(self.model, weights, B, self.device))
             ops.mpc_run(self.model, x_cur, sv.x, sv.u, sv.K, sv.k, sv.cost, sv.tol, sv.max_iter, steps, sv._ws, traj_x,
                         traj_u, traj_it, disturbance=dist_t, alphas=sv.alphas, reg=sv.reg, alpha_idx=sv.alpha_idx,
                         active=sv.active, iters=sv.iters, status=sv.status, **extra)

@@ -454,7 +454,7 @@ def solve_log_record(model, log, phase, x_nom, u_nom, K, k, cost, alpha_idx, act
 
 def ilqr_solve(model, x_nom, u_nom, K, k, cost, tol, max_iter, workspace, alphas=ALPHAS, reg=QUU_REG, x0=None,
                alpha_idx=None, active=None, iters=None, status=None, fixed_iters=False, reset=False, log=None,
-               persistent=False, enqueue=False, model_phys=None, x_ref_rows=None):
+               persistent=False, enqueue=False, model_phys=None, x_ref_rows=None, cost_rows=None):
     """The whole solve from ONE C call with no host involvement: up to max_iter iterations, every trajectory stopping on
     its own test; x0 given = roll the nominal out from it first.  Everything in place (quattro_ilqr_solve_phys_f32).
     reset: the call sets active / iters / alpha_idx / status itself; log: a SolveLog ring filled by the device;
@@ -465,10 +465,14 @@ def ilqr_solve(model, x_nom, u_nom, K, k, cost, tol, max_iter, workspace, alphas
     with enqueue).  None: the solve with model.phys for every trajectory.
     x_ref_rows (B, R, n) or (B, n), or the device tensor of x_ref_rows_tensor: the cost of trajectory b at horizon step t (t = N: the
     terminal cost) is taken against row min(t, R - 1) of its rows in place of model.x_ref (quattro_ilqr_solve_ref_f32; the same
-    kernel rule and refusals as model_phys).  None: model.x_ref for every trajectory and step."""
+    kernel rule and refusals as model_phys).  None: model.x_ref for every trajectory and step.
+    cost_rows: per-trajectory cost weights in any form cost_rows_tensor takes, or its (B, 40) device tensor: trajectory b is solved
+    with row b for model.q, qf and r (quattro_ilqr_solve_cost_f32; the same kernel rule and refusals as model_phys).  None: the
+    model's weights for every trajectory."""
     Bt, N, m = u_nom.shape
     model_phys = model_phys_tensor(model, model_phys, Bt, u_nom.device)
     x_ref_rows = x_ref_rows_tensor(model, x_ref_rows, Bt, u_nom.device, name="x_ref_rows")
+    cost_rows = cost_rows_tensor(model, cost_rows, Bt, u_nom.device, name="cost_rows")
     n = model.n
     f32, i32 = torch.float32, torch.int32
     _req(x_nom, (Bt, N + 1, n), f32, "x_nom"); _req(u_nom, (Bt, N, model.m), f32, "u_nom")
@@ -488,12 +492,17 @@ def ilqr_solve(model, x_nom, u_nom, K, k, cost, tol, max_iter, workspace, alphas
     args = (ctypes.byref(p), _ptr(x0), _ptr(x_nom), _ptr(u_nom), Bt, N, float(reg), arr, na, float(tol), int(max_iter), flags,
             _ptr(K), _ptr(k), _ptr(cost), _ptr(alpha_idx), _ptr(active), _ptr(iters), _ptr(status), _ptr(workspace),
             workspace.numel() * workspace.element_size(), None if log is None else log.byref())
-    _solve_call(_lib.load_for(model), args, model_phys, x_ref_rows, _stream())
+    _solve_call(_lib.load_for(model), args, model_phys, x_ref_rows, _stream(), cost_rows)
 
 
-def _solve_call(lib, args, model_phys, x_ref_rows, stream):
-    """The one C call of a solve: the ref entry with rows, the phys entry (whose NULL rows forward inside the library) without."""
-    if x_ref_rows is not None:
+def _solve_call(lib, args, model_phys, x_ref_rows, stream, cost_rows=None):
+    """The one C call of a solve: the cost entry with weights, else the ref entry with rows, else the phys entry (whose NULL rows
+    forward inside the library)."""
+    if cost_rows is not None:
+        check(lib.quattro_ilqr_solve_cost_f32(*args, _ptr(model_phys), _ptr(x_ref_rows),
+                                              0 if x_ref_rows is None else x_ref_rows.shape[1], _ptr(cost_rows), stream),
+              "quattro_ilqr_solve_cost_f32")
+    elif x_ref_rows is not None:
         check(lib.quattro_ilqr_solve_ref_f32(*args, _ptr(model_phys), _ptr(x_ref_rows), x_ref_rows.shape[1], stream),
               "quattro_ilqr_solve_ref_f32")
     else:
@@ -524,17 +533,18 @@ class PreparedSolve:
                      workspace.numel() * workspace.element_size())
 
     def __call__(self, tol, max_iter, fixed_iters=False, log=None, persistent=False, stream=None, model_phys=None,
-                 x_ref_rows=None):
-        """model_phys, x_ref_rows: per-trajectory phys rows and reference rows (ilqr_solve).  Nothing of them is prepared or kept:
-        the rows are THIS call's argument, so a later call without them is the plain solve."""
+                 x_ref_rows=None, cost_rows=None):
+        """model_phys, x_ref_rows, cost_rows: per-trajectory phys rows, reference rows and cost weights (ilqr_solve).  Nothing of
+        them is prepared or kept: the rows are THIS call's argument, so a later call without them is the plain solve."""
         flags = _lib.SOLVE_SIMULATE | _lib.SOLVE_RESET | (_lib.SOLVE_FIXED_ITERS if fixed_iters else 0) | \
             (_lib.SOLVE_PERSISTENT if persistent else 0)
         if log is not None and (log.B, log.N, log.n, log.m) != self.dims:
             raise ValueError("log ring was built for another problem size")
         model_phys = model_phys_tensor(self.model, model_phys, self.dims[0], self.keep[0].device)
         x_ref_rows = x_ref_rows_tensor(self.model, x_ref_rows, self.dims[0], self.keep[0].device, name="x_ref_rows")
+        cost_rows = cost_rows_tensor(self.model, cost_rows, self.dims[0], self.keep[0].device, name="cost_rows")
         _solve_call(self.lib, (*self.head, float(tol), int(max_iter), flags, *self.tail, None if log is None else log.byref()),
-                    model_phys, x_ref_rows, _stream() if stream is None else stream)
+                    model_phys, x_ref_rows, _stream() if stream is None else stream, cost_rows)
 
 
 def check_plant(model, plant):
@@ -601,6 +611,67 @@ def x_ref_rows_tensor(model, rows, B, device, name="targets"):
     return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
+COST_ROW_FLOATS = 2 * _lib.MAX_NX + _lib.MAX_NU      # QUATTRO_COST_ROW_FLOATS: q at float 0, qf at float MAX_NX, r at float 2 MAX_NX
+_COST_KEYS = ("q", "qf", "r")
+
+
+def model_can_cost_rows(model):
+    """Whether the model's persistent kernel has a form that reads per-trajectory cost weights: the cart-pole's and a user model's
+    have, the built-in quadrotor's has not (the C entries answer QUATTRO_ERR_UNSUPPORTED for it before any launch)."""
+    return model_can_device_loop(model) and model.model_id != _lib.MODEL_QUADROTOR
+
+
+def check_cost_rows(model, weights, B, name="weights", device=None):
+    """Per-trajectory cost weights: None; a dict with any of the keys "q", "qf", "r", each (B, n) / (B, n) / (B, m) or one vector
+    that is broadcast over the batch (a missing key takes the model's own values); a plain (B, 2n + m) array in the order
+    [q | qf | r]; or the (B, 40) float32 device tensor the C ABI takes.  ValueError otherwise, under the keyword's `name`; host
+    logic only, the values are not looked at.  -> True where the rows need no conversion (None or such a tensor)."""
+    if weights is None:
+        return True
+    n, m = model.n, model.m
+    if isinstance(weights, dict):
+        unknown = [key for key in weights if key not in _COST_KEYS]
+        if unknown:
+            raise ValueError(f"{name} has unknown keys {unknown}: the keys are {list(_COST_KEYS)}")
+        for key in weights:
+            d = m if key == "r" else n
+            shape = tuple(np.shape(weights[key]))
+            if shape != (B, d) and shape != (d,):
+                raise ValueError(f"{name}[{key!r}] must have shape {(B, d)} or {(d,)} (got {shape})")
+        return False
+    shape = tuple(np.shape(weights))
+    if (isinstance(weights, torch.Tensor) and shape == (B, COST_ROW_FLOATS) and weights.is_cuda and weights.dtype == torch.float32
+            and weights.is_contiguous() and weights.data_ptr() % 16 == 0
+            and (device is None or weights.device == torch.device(device))):
+        return True
+    if shape != (B, 2 * n + m):
+        raise ValueError(f"{name} must be a dict with keys from {list(_COST_KEYS)} or have shape {(B, 2 * n + m)} (got {shape})")
+    return False
+
+
+def cost_rows_tensor(model, weights, B, device, name="weights"):
+    """Per-trajectory cost weights in any form check_cost_rows takes -> the (B, 40) float32 array on `device` that the C ABI takes
+    (cost_rows, include/quattro_hip.h: q at float 0, qf at float 16, r at float 32; the entries beyond n / m are zero and ignored).
+    Such an array is passed through as it is, None stays None; the one check and the one conversion of the rows, before anything
+    touches the device."""
+    if check_cost_rows(model, weights, B, name, device):
+        return weights
+    n, m = model.n, model.m
+    parts = {"q": np.asarray(model.q, dtype=np.float32), "qf": np.asarray(model.qf, dtype=np.float32),
+             "r": np.asarray(model.r, dtype=np.float32)}
+    if isinstance(weights, dict):
+        for key, v in weights.items():
+            parts[key] = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+    else:
+        w = weights.detach().cpu().numpy() if isinstance(weights, torch.Tensor) else np.asarray(weights)
+        parts = {"q": w[:, :n], "qf": w[:, n:2 * n], "r": w[:, 2 * n:]}
+    rows = np.zeros((B, COST_ROW_FLOATS), dtype=np.float32)
+    for key, at, d in (("q", 0, n), ("qf", _lib.MAX_NX, n), ("r", 2 * _lib.MAX_NX, m)):
+        rows[:, at:at + d] = np.broadcast_to(np.asarray(parts[key], dtype=np.float32), (B, d))
+    t = torch.as_tensor(rows, device=device)
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 def track(model, x0, x_nom, u_nom, K, steps, plant=None, plant_phys=None, feedback=True, disturbance=None):
     """`steps` <= N plant steps from x0 (B,n) along the first rows of a nominal with its gains (quattro_track_f32):
     u = u_nom[j] + (feedback ? K[j] (x - x_nom[j]) : 0), x <- f_plant(x, u) + disturbance[j].  plant: a DeviceModel like `model`
@@ -644,7 +715,7 @@ def _mpc_args(model, x_cur, x_nom, u_nom, K, k, cost, tol, max_iter, n_steps, wo
 
 def mpc_run(model, x_cur, x_nom, u_nom, K, k, cost, tol, max_iter, n_steps, workspace, traj_x, traj_u, traj_iters,
             disturbance=None, alphas=ALPHAS, reg=QUU_REG, alpha_idx=None, active=None, iters=None, status=None,
-            plant=None, plant_phys=None, hold=1, feedback=False, model_phys=None, x_ref_rows=None, preview=True):
+            plant=None, plant_phys=None, hold=1, feedback=False, model_phys=None, x_ref_rows=None, preview=True, cost_rows=None):
     """B controllers x n_steps control steps (solve -> apply u_0 -> shift the warm start) in ONE launch
     (quattro_mpc_run_f32); x_cur and u_nom advance in place, the closed-loop record goes to traj_x / traj_u / traj_iters.
     plant / plant_phys / hold / feedback (any of them off its default: quattro_mpc_run_plant_f32): n_steps PLANT steps, a solve
@@ -653,14 +724,18 @@ def mpc_run(model, x_cur, x_nom, u_nom, K, k, cost, tol, max_iter, n_steps, work
     row b for its model's phys, and its plant is plant_phys[b], else plant.phys, else that same row.
     x_ref_rows (as in ilqr_solve; quattro_mpc_run_ref_f32, the phys entry's arguments, these rows and preview): horizon step t of the
     plan that starts at plant step s takes its cost against row min(s + preview * t, R - 1) of controller b's rows — preview=True
-    looks along the rows over the horizon, preview=False holds the row of the replan step for the whole solve."""
+    looks along the rows over the horizon, preview=False holds the row of the replan step for the whole solve.
+    cost_rows (as in ilqr_solve; quattro_mpc_run_cost_f32, the ref entry's arguments and these rows): controller b plans with row b
+    for its q, qf and r, in every solve of the run."""
     Bt, N, m = u_nom.shape
     n = model.n
     f32, i32 = torch.float32, torch.int32
     hold = int(hold)
     check_phys_rows(model, model_phys, Bt, "model_phys")
     check_ref_rows(model, x_ref_rows, Bt, name="x_ref_rows")
-    plain = plant is None and plant_phys is None and hold == 1 and not feedback and model_phys is None and x_ref_rows is None
+    check_cost_rows(model, cost_rows, Bt, name="cost_rows")
+    plain = (plant is None and plant_phys is None and hold == 1 and not feedback and model_phys is None and x_ref_rows is None
+             and cost_rows is None)
     if hold < 1 or n_steps % hold != 0:
         raise ValueError("n_steps must be a multiple of hold >= 1")
     _req(x_cur, (Bt, n), f32, "x_cur"); _req(x_nom, (Bt, N + 1, n), f32, "x_nom"); _req(u_nom, (Bt, N, model.m), f32, "u_nom")
@@ -682,6 +757,14 @@ def mpc_run(model, x_cur, x_nom, u_nom, K, k, cost, tol, max_iter, n_steps, work
     pref = None if pp is None else ctypes.byref(pp)
     pphys = plant_phys_tensor(model, plant_phys, Bt, u_nom.device)
     model_phys = model_phys_tensor(model, model_phys, Bt, u_nom.device)
+    if cost_rows is not None:
+        x_ref_rows = x_ref_rows_tensor(model, x_ref_rows, Bt, u_nom.device, name="x_ref_rows")
+        cost_rows = cost_rows_tensor(model, cost_rows, Bt, u_nom.device, name="cost_rows")
+        check(_lib.load_for(model).quattro_mpc_run_cost_f32(*head, pref, _ptr(pphys), hold, int(bool(feedback)), _ptr(model_phys),
+                                                            _ptr(x_ref_rows), 0 if x_ref_rows is None else x_ref_rows.shape[1],
+                                                            int(bool(preview)), _ptr(cost_rows), _stream()),
+              "quattro_mpc_run_cost_f32")
+        return
     if x_ref_rows is not None:
         x_ref_rows = x_ref_rows_tensor(model, x_ref_rows, Bt, u_nom.device, name="x_ref_rows")
         check(_lib.load_for(model).quattro_mpc_run_ref_f32(*head, pref, _ptr(pphys), hold, int(bool(feedback)), _ptr(model_phys),

@@ -379,8 +379,16 @@ class QuattroILQR:
         self._require_device_loop("targets")
         ops.check_ref_rows(self.model, targets, B)
 
+    def _check_weights(self, weights, B):
+        """The same for per-trajectory cost weights."""
+        self._require_device_loop("weights")
+        if not ops.model_can_cost_rows(self.model):
+            raise NotImplementedError(f"weights runs only in the device-resident loop: model {self.model.name} "
+                                      f"({self.model.integrator}) has no persistent kernel that takes cost rows")
+        ops.check_cost_rows(self.model, weights, B)
+
     def solve(self, x0, u_init=None, x_ref=None, max_iter=None, fixed_iters=False, log=None, want_alpha=True,
-              upload_guard=True, model_phys=None, targets=None):
+              upload_guard=True, model_phys=None, targets=None, weights=None):
         """x0 (B,n), u_init (B,N,m) (zeros if None).  Returns a dict of device tensors:
         K (B,N,m,n), k (B,N,m), x (B,N+1,n), u (B,N,m), cost (B,) fp64, iters (B,), alpha (B,) last accepted step
         (-1: none), status (B,).  fixed_iters=True runs exactly max_iter iterations (benchmarking: stop flags off).
@@ -399,7 +407,16 @@ class QuattroILQR:
         horizon, anything between holds its last row.  Weights, barrier, dt and integrator stay the model's.  The same kernel rule,
         refusals and order as model_phys, with which it combines.  Out of scope: iLQR_TF, ShardedILQR, datagen, hybrid mode.
         x_ref: pure mode ignores it — the cost keeps model.x_ref — and hybrid mode feeds it to the predictor's input only
-        (x - x_ref + state_offset); a target for the COST is `targets`."""
+        (x - x_ref + state_offset); a target for the COST is `targets`.
+        weights: per-trajectory cost weights — a dict with any of the keys "q", "qf", "r" (each (B, n) / (B, n) / (B, m), or one
+        vector that is broadcast over the batch; a missing key keeps the model's values), a plain (B, 2n + m) array in the order
+        [q | qf | r], or the device tensor of ops.cost_rows_tensor.  Trajectory b is solved with row b in place of model.q, qf
+        and r: what B solvers, each built on model.with_(q=..., qf=..., r=...), return for their one trajectory, bit for bit.  The
+        barrier, x_ref (unless targets), dt, integrator and phys (unless model_phys) stay the model's; the values are used as
+        given, and a row that makes Q_uu singular shows in that trajectory's status alone.  The same kernel rule, refusals and
+        order as model_phys, with which and with targets it combines.  The cart-pole and user-compiled models take weights; the
+        built-in quadrotor's persistent kernel has no such form yet and refuses like a model without a kernel
+        (NotImplementedError).  Out of scope: per-step weights, ShardedILQR."""
         n, m, N, dev = self.model.n, self.model.m, self.horizon, self.device
         if not isinstance(x0, torch.Tensor):
             x0 = np.asarray(x0)
@@ -408,6 +425,8 @@ class QuattroILQR:
             self._check_model_phys(model_phys, B)
         if targets is not None:
             self._check_targets(targets, B)
+        if weights is not None:
+            self._check_weights(weights, B)
         self._alloc(B)
         self._upload(x0, u_init, guard=upload_guard)
         x0 = self._x0
@@ -425,7 +444,8 @@ class QuattroILQR:
                     self.tf.shifted_mean(xr - off, out=self._tf_mean)
                 self._ref_key = key
             x_ref_t = self._x_ref_t
-        if self.tf is None and not self.use_graph and (self._wants_device_loop() or model_phys is not None or targets is not None):
+        if self.tf is None and not self.use_graph and (self._wants_device_loop() or model_phys is not None or targets is not None
+                                                           or weights is not None):
             # the whole loop on the device: per-solve state reset, nominal rollout, iterations, per-trajectory stop tests —
             # one launch, no synchronisation
             if self._ws is None:
@@ -436,8 +456,9 @@ class QuattroILQR:
             # (the rows stay referenced until the next solve: the launch is asynchronous)
             self._model_phys = ops.model_phys_tensor(self.model, model_phys, B, dev)
             self._targets = ops.x_ref_rows_tensor(self.model, targets, B, dev)
+            self._weights = ops.cost_rows_tensor(self.model, weights, B, dev)
             self._solve_call(self.tol, max_iter, fixed_iters=fixed_iters, log=log, persistent=self.device_loop == "always",
-                             model_phys=self._model_phys, x_ref_rows=self._targets)
+                             model_phys=self._model_phys, x_ref_rows=self._targets, cost_rows=self._weights)
             max_iter = 0
         else:
             self._ints.copy_(self._ints_init)          # active = 1, iters = 0, alpha_idx = -1, status = 0

@@ -19,7 +19,10 @@ the converged solve and the 10 control steps with per-trajectory model parameter
 trajectory within 12 % of the model's) next to the same calls without, and with neutral rows (the PHYS kernels on the default
 problem: same work, same iteration counts); the same two calls with reference rows (targets: neutral rows -- the REF kernels on
 the default problem -- and a reference that moves 2 cm per step along a per-trajectory heading, with preview over the horizon:
-other work, reported with its iterations per trajectory).
+other work, reported with its iterations per trajectory); and, for the cart-pole (the quadrotor's kernel takes no cost rows), the
+same two calls with per-trajectory cost weights (weights: no rows, neutral rows -- the COST kernel on the default problem -- and
+heterogeneous rows, every component of q, qf and r of every trajectory scaled by a log-uniform factor in [0.4, 2.5]: other work,
+reported with its iterations per trajectory).
 """
 import argparse
 import ctypes
@@ -73,9 +76,10 @@ def measure(defaults_only):
     new_abi = hasattr(raw, "quattro_mpc_run_plant_f32")
     phys_abi = hasattr(raw, "quattro_mpc_run_phys_f32")
     ref_abi = hasattr(raw, "quattro_mpc_run_ref_f32")
+    cost_abi = hasattr(raw, "quattro_mpc_run_cost_f32")
     # an older build of the library: bind what it has (the default forms need nothing newer)
     for name in ("quattro_track_f32", "quattro_mpc_run_plant_f32", "quattro_ilqr_solve_phys_f32", "quattro_mpc_run_phys_f32",
-                 "quattro_ilqr_solve_ref_f32", "quattro_mpc_run_ref_f32"):
+                 "quattro_ilqr_solve_ref_f32", "quattro_mpc_run_ref_f32", "quattro_ilqr_solve_cost_f32", "quattro_mpc_run_cost_f32"):
         if not hasattr(raw, name):
             _lib.SIGNATURES.pop(name, None)
     from quattro_ilqr_amd import BatchedMPC, QuattroILQR, cartpole_model, ops, quadrotor_model
@@ -96,7 +100,7 @@ def measure(defaults_only):
             ts.append(1e3 * (time.perf_counter() - t0))
         return float(np.median(ts))
 
-    out = {"lib": os.path.basename(_lib.LIB_PATH), "new_abi": new_abi, "phys_abi": phys_abi, "ref_abi": ref_abi}
+    out = {"lib": os.path.basename(_lib.LIB_PATH), "new_abi": new_abi, "phys_abi": phys_abi, "ref_abi": ref_abi, "cost_abi": cost_abi}
     mpc = BatchedMPC(md, N, max_iter=100, tol=1e-3, device=dev)
 
     def run(steps, **kw):
@@ -183,6 +187,23 @@ def measure(defaults_only):
                 out.setdefault(f"ref_cartpole_mpc_run_10_steps_{tag}_ms", []).append(timed(lambda: cp_run_kw(10, **kw), reps=5))
                 if rnd == 0:
                     out[f"ref_cartpole_solve_{tag}_mean_iters"] = float(cp_sv.solve(cx0, max_iter=100, **kw)["iters"].float().mean())
+    if not defaults_only and cost_abi:
+        def weight_rows(model, nb):
+            own = np.concatenate([model.q, model.qf, model.r]).astype(np.float64)
+            lo, hi = np.log(0.4), np.log(2.5)
+            f = np.exp(np.random.default_rng(11).uniform(lo, hi, (nb, own.size))).astype(np.float32)
+            return (ops.cost_rows_tensor(model, np.tile(own.astype(np.float32), (nb, 1)), nb, dev),
+                    ops.cost_rows_tensor(model, (own[None, :] * f).astype(np.float32), nb, dev))
+
+        # (cp_run_kw: the reference-rows block above; a library with the cost entries has the ref entries)
+        w_neutral, w_het = weight_rows(cp, 1024)
+        for rnd in range(3):
+            for tag, kw in (("shared", {}), ("neutral_weights", dict(weights=w_neutral)), ("het_weights", dict(weights=w_het))):
+                out.setdefault(f"cost_cartpole_solve_{tag}_ms", []).append(timed(lambda: cp_sv.solve(cx0, max_iter=100, **kw), reps=5))
+                out.setdefault(f"cost_cartpole_mpc_run_10_steps_{tag}_ms", []).append(timed(lambda: cp_run_kw(10, **kw), reps=5))
+                if rnd == 0:
+                    out[f"cost_cartpole_solve_{tag}_mean_iters"] = float(cp_sv.solve(cx0, max_iter=100, **kw)["iters"].float().mean())
+                    out[f"cost_cartpole_mpc_run_10_steps_{tag}_mean_iters"] = float(cp_run_kw(10, **kw)["iters"].float().mean())
     print(json.dumps(out), flush=True)
 
 
