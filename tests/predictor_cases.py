@@ -94,8 +94,11 @@ def sinusoid_pe(max_len, d=D):
     return pe[None]
 
 
-def random_model(n, c, ns, P, T, ff, layers, seed, sharp=True, qk_scale=4.0, max_seq_len=128):
-    """(w, norm, hp).  sharp=False restates TransformerILQR.random_init: what the suite tested before this module."""
+def random_model(n, c, ns, P, T, ff, layers, seed, sharp=True, qk_scale=4.0, max_seq_len=128, d_model=D, nhead=NHEAD):
+    """(w, norm, hp).  sharp=False restates TransformerILQR.random_init: what the suite tested before this module.  d_model and
+    nhead default to the predictor kernel's 128 / 4 (tests/train_cases.py draws other widths from the same recipe); the order of
+    the random draws does not depend on them, so the defaults give the models they always gave."""
+    D = d_model
     g = np.random.default_rng(seed)
     bs, ln, te = (0.3, 0.3, 0.5) if sharp else (0.02, 0.05, 0.02)
     lin = lambda o, i: (g.uniform(-1, 1, (o, i)) / np.sqrt(i)).astype(np.float32)
@@ -104,7 +107,7 @@ def random_model(n, c, ns, P, T, ff, layers, seed, sharp=True, qk_scale=4.0, max
          "state_embed.weight": lin(D, n), "state_embed.bias": vec(D, bs),
          "control_embed.weight": lin(D, c), "control_embed.bias": vec(D, bs),
          "output_linear.weight": lin(c, D), "output_linear.bias": vec(c, bs),
-         "pos_encoder.pe": sinusoid_pe(max_seq_len)}
+         "pos_encoder.pe": sinusoid_pe(max_seq_len, D)}
     for i in range(layers):
         p = f"transformer_decoder.layers.{i}."
         wi = lin(3 * D, D)
@@ -122,7 +125,7 @@ def random_model(n, c, ns, P, T, ff, layers, seed, sharp=True, qk_scale=4.0, max
                     u_mean=f(g.standard_normal(c)), u_std=f(0.5 + 1.5 * g.random(c)))
     else:
         norm = dict(x_mean=np.zeros(n), x_std=np.ones(n), u_mean=np.zeros(c), u_std=np.ones(c))
-    hp = dict(target_len=T, prompt_len=P, state_dim=n, control_dim=c, d_model=D, nhead=NHEAD, num_decoder_layers=layers,
+    hp = dict(target_len=T, prompt_len=P, state_dim=n, control_dim=c, d_model=D, nhead=nhead, num_decoder_layers=layers,
               dim_feedforward=ff, dropout=0.0, max_seq_len=max_seq_len)
     return w, norm, hp
 

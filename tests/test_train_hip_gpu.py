@@ -2,13 +2,13 @@
 (`training.forward`, which tests/test_training_*.py pin to the REFERENCE module's outputs on the shipped checkpoints):
 loss, prediction and every parameter gradient, with and without dropout; Adam against torch.optim.Adam; fit() end to end.
 Reference: quattro_ilqr_tf/transformer_ilqr.py:102-208 (fit), transformer_model.py:85-138 (the network)."""
-import math
 import sys
 
 import numpy as np
 import pytest
 
 from conftest import PKG_DIR
+from train_cases import forward_with_masks as _forward_with_masks
 
 pytestmark = pytest.mark.gpu
 sys.path.insert(0, PKG_DIR)
@@ -73,37 +73,6 @@ def test_loss_prediction_and_every_gradient_match_fp32_autograd(name):
     total = sum(int(np.prod(s)) for _, _, s in tr.shapes.values())
     assert abs(float(tr.grads.abs().sum()) - sum(float(tr.view(tr.grads, k).abs().sum()) for k in tr.shapes)) < 1e-3
     assert total <= tr.n_params
-
-
-def _forward_with_masks(params, buffers, x, u, nhead, masks):
-    """training.forward with explicit dropout factors per site (0: positions; per layer: attention weights, out-proj,
-    ff hidden, ff output) — the same network, term for term (transformer_model.py:122-138)."""
-    import torch
-    import torch.nn.functional as F
-    W = params
-    T, d = W["target_embedding"].shape
-    B = x.shape[0]
-    h = torch.cat([F.linear(x, W["state_embed.weight"], W["state_embed.bias"]),
-                   F.linear(u, W["control_embed.weight"], W["control_embed.bias"]),
-                   W["target_embedding"].unsqueeze(0).expand(B, T, d)], dim=1)
-    L = h.shape[1]
-    h = (h + buffers["pos_encoder.pe"][:, :L]) * masks[0].view(B, L, d)
-    hd = d // nhead
-    causal = torch.triu(torch.ones(L, L, dtype=torch.bool, device=h.device), diagonal=1)
-    n_layers = sum(1 for k in W if k.endswith("self_attn.in_proj_weight"))
-    for i in range(n_layers):
-        q = f"transformer_decoder.layers.{i}."
-        qkv = F.linear(h, W[q + "self_attn.in_proj_weight"], W[q + "self_attn.in_proj_bias"])
-        qh, kh, vh = (t.reshape(B, L, nhead, hd).transpose(1, 2) for t in qkv.split(d, dim=-1))
-        s = (qh @ kh.transpose(-1, -2)) * (1.0 / math.sqrt(hd))
-        a = torch.softmax(s.masked_fill(causal, float("-inf")), dim=-1) * masks[1 + 4 * i].view(B, nhead, L, L)
-        o = (a @ vh).transpose(1, 2).reshape(B, L, d)
-        o = F.linear(o, W[q + "self_attn.out_proj.weight"], W[q + "self_attn.out_proj.bias"])
-        h = F.layer_norm(h + o * masks[2 + 4 * i].view(B, L, d), (d,), W[q + "norm1.weight"], W[q + "norm1.bias"], 1e-5)
-        f = torch.relu(F.linear(h, W[q + "linear1.weight"], W[q + "linear1.bias"])) * masks[3 + 4 * i].view(B, L, -1)
-        f = F.linear(f, W[q + "linear2.weight"], W[q + "linear2.bias"])
-        h = F.layer_norm(h + f * masks[4 + 4 * i].view(B, L, d), (d,), W[q + "norm2.weight"], W[q + "norm2.bias"], 1e-5)
-    return F.linear(h[:, -T:, :], W["output_linear.weight"], W["output_linear.bias"])
 
 
 @pytest.mark.parametrize("name", ["quadrotor", "small"])
