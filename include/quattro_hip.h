@@ -498,6 +498,36 @@ int quattro_mpc_run_cost_f32(const quattro_model_params* p, float* x_cur, float*
                              int feedback, const float* model_phys, const float* x_ref_rows, int ref_rows, int preview,
                              const float* cost_rows, void* stream);
 
+/* SCORING: per-step costs and their fp64 total of given sequences, under per-trajectory targets, weights and parameters.  The last
+ * stage of a tuning or fleet study: a closed-loop run made with reference rows, cost rows or model_phys (the entries above) is scored
+ * on the device against what it was asked to follow, under ONE evaluation cost or under each controller's own.  Replaces
+ * compute_total_cost (quattro_ilqr_tf.py:138-143) step by step: the reference sums L over the sequence and adds Lf; this entry returns
+ * every term of that sum and the sum, with the terminal term optional (Lf belongs to a horizon, not to a run of plant steps).
+ *   x [B][S+1][n], u [B][S][m] : any sequences; they need not satisfy the dynamics
+ *   model_phys [B][8], x_ref_rows [B][ref_rows][n], cost_rows [B][QUATTRO_COST_ROW_FLOATS] : the arrays of the *_phys / *_ref / *_cost
+ *                       entries, the same layouts, 16-byte aligned; each may be NULL on its own (p's values then).  phys matters only
+ *                       to a user model whose cost reads P: the built-in costs do not read it, and the rows are accepted without effect
+ *   step s < S        : stage[b][s] = L(x_s, u_s) with q, r of row b of cost_rows, phys of row b of model_phys and x_ref = row
+ *                       min((s / ref_hold) * ref_hold, ref_rows - 1) of trajectory b's reference rows (integer division).  ref_hold = 1
+ *                       is "row s": what a closed loop with preview = 1 was planned against at plant step s.  ref_hold = h is the
+ *                       set-point schedule of preview = 0 with a plan every h plant steps.  Past the last row the last row holds (the
+ *                       row rule of the REFERENCE ROWS, stated for plant steps)
+ *   slot S            : with QUATTRO_SCORE_TERMINAL in flags, stage[b][S] = Lf(x_S) with qf of the row and the reference row of the
+ *                       same rule at s = S; without it +0.0f
+ *   total [b] (fp64)  : sum of (double)stage[b][s] for s = 0 .. S in that order -- the accumulation of quattro_total_cost_f32, so that
+ *                       without rows and with the flag total equals its cost bit for bit.  Without the flag slot S adds nothing
+ *   stage [B][S+1]    : may be NULL (totals only); total may not
+ * One wave per trajectory evaluates 64 steps at a time (quattro_total_cost_f32 is one lane per trajectory, serial over steps: right
+ * for a horizon of 50, wrong for a run of thousands of plant steps); the total is accumulated in step order whatever the mapping.
+ * Nothing is allocated and no workspace is taken.  Every model takes every kind of row here, the built-in quadrotor's cost rows
+ * included (scoring needs the model's stage and final cost only, not its persistent kernel).  Before any launch: the model check
+ * of quattro_total_cost_f32 first; then QUATTRO_ERR_BAD_ARG for a NULL x, u or total, B <= 0, S <= 0, unknown bits in flags,
+ * reference rows with ref_rows < 1 or ref_hold < 1 (neither is looked at without rows), or a row array that is not 16-byte aligned. */
+#define QUATTRO_SCORE_TERMINAL 1
+int quattro_score_f32(const quattro_model_params* p, const float* x, const float* u, int B, int S, const float* model_phys,
+                      const float* x_ref_rows, int ref_rows, int ref_hold, const float* cost_rows, int flags, float* stage,
+                      double* total, void* stream);
+
 /* Transformer gain predictor: weights of the reference's TransformerPredictor (quattro_ilqr_tf/transformer_model.py:85-138)
  * as DEVICE pointers, plus the DataNormalizer vectors (:15-50).  Matrices are PyTorch Linear layout [out][in];
  * the `w_*` matrices are 16-bit (raw uint16 bit patterns: bf16, or IEEE half when `precision` says so), everything else

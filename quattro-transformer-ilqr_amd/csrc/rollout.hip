@@ -2,7 +2,7 @@
 // the fused line search (evaluate every alpha, accept the first that does not increase the cost, commit it).
 //
 // Arithmetic replaced (reference quattro_ilqr_tf/quattro_ilqr_tf.py): simulate :127-132, compute_total_cost
-// :138-143, forward_pass :377-390, and the alpha loop + stop test of optimize :433-451, :472 (:546-563, :584).
+// :138-143 (total_cost_kernel; term by term under per-trajectory rows: score_kernel), forward_pass :377-390, and the alpha loop + stop test of optimize :433-451, :472 (:546-563, :584).
 //
 // Serial in t by nature (x'_{t+1} depends on x'_t); parallel over (trajectory, alpha).  Eight lanes per
 // trajectory (one per alpha, n_alpha <= 8) sit next to each other in a wave, so the loads of K_t, k_t, x_t, u_t
@@ -43,6 +43,83 @@ __global__ __launch_bounds__(64) void total_cost_kernel(const quattro_model_para
   load_vec<NX>(xb + (size_t)N * NX, xt);
   J += (double)qt_final_cost<MODEL>(p, xt);
   cost[b] = J;
+}
+
+// Scoring (quattro_score_f32): stage[b][s] = L(x_s, u_s) for s < S, slot S = Lf(x_S) or +0, total[b] = their fp64 sum in step order,
+// each trajectory under rows of its own (phys, reference, weights; any of them NULL: the block's values).  One wave per trajectory,
+// a step per lane, 64 steps a pass: the trajectory's q, qf, r, phys are wave-uniform, only x_ref and the step's (x, u) differ from lane
+// to lane.  The block `own` is filled with VALUES behind wave-uniform branches (the way solve_loop.h's trajectory_params and
+// set_ref_row fill theirs; code of this kernel's own), so every call runs the same cost code with or without rows.
+// Lanes past the end of the last pass stay out of the branch that evaluates the cost: qt_stage_cost's __all(negligible) is then
+// taken over lanes that hold a step, and its shortcut is exact whichever way it goes.  The ordered sum goes through 512 bytes of LDS
+// (every lane adds the pass's terms in step order: the same J in all lanes), so it needs no global memory when stage == NULL.
+template <int MODEL>
+__global__ __launch_bounds__(QT_WAVE) void score_kernel(const quattro_model_params p, const float* __restrict__ x,
+                                                        const float* __restrict__ u, const int S,
+                                                        const float* __restrict__ model_phys, const float* __restrict__ x_ref_rows,
+                                                        const int ref_rows, const int ref_hold, const float* __restrict__ cost_rows,
+                                                        const int terminal, float* __restrict__ stage, double* __restrict__ total) {
+  constexpr int NX = ModelDims<MODEL>::NX, NU = ModelDims<MODEL>::NU;
+  __shared__ double term[QT_WAVE];
+  const size_t bb = blockIdx.x;
+  const int lane = threadIdx.x;
+  quattro_model_params own = p;
+  if (cost_rows != nullptr) {
+    float w[QUATTRO_COST_ROW_FLOATS];
+#pragma unroll
+    for (int i = 0; i < QUATTRO_COST_ROW_FLOATS; ++i) w[i] = cost_rows[bb * QUATTRO_COST_ROW_FLOATS + i];
+#pragma unroll
+    for (int i = 0; i < QUATTRO_MAX_NX; ++i) {
+      own.q[i] = w[i];
+      own.qf[i] = w[QUATTRO_MAX_NX + i];
+    }
+#pragma unroll
+    for (int i = 0; i < QUATTRO_MAX_NU; ++i) own.r[i] = w[2 * QUATTRO_MAX_NX + i];
+  }
+  if (model_phys != nullptr) {
+    float ph[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) ph[i] = model_phys[bb * 8 + i];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) own.phys[i] = ph[i];
+  }
+  const size_t steps = (size_t)S + 1;                          // slots of a trajectory: S stage costs and the terminal slot
+  const float* xb = x + bb * steps * NX;
+  const float* ub = u + bb * (size_t)S * NU;
+  double J = 0.0;
+  for (size_t base = 0; base < steps; base += QT_WAVE) {
+    float c = 0.0f;
+    if (base + lane < steps) {
+      const int s = (int)(base + lane);
+      float xs[NX], xr[NX];
+      load_vec<NX>(xb + (size_t)s * NX, xs);
+#pragma unroll
+      for (int i = 0; i < NX; ++i) xr[i] = p.x_ref[i];
+      if (x_ref_rows != nullptr) {
+        const int held = (s / ref_hold) * ref_hold;
+        const int row = held < ref_rows - 1 ? held : ref_rows - 1;
+        const float* rr = x_ref_rows + (bb * (size_t)ref_rows + (size_t)row) * NX;
+#pragma unroll
+        for (int i = 0; i < NX; ++i) xr[i] = rr[i];
+      }
+#pragma unroll
+      for (int i = 0; i < NX; ++i) own.x_ref[i] = xr[i];
+      if (s < S) {
+        float us[NU];
+        load_vec<NU>(ub + (size_t)s * NU, us);
+        c = qt_stage_cost<MODEL>(own, xs, us);
+      } else if (terminal != 0) {
+        c = qt_final_cost<MODEL>(own, xs);
+      }
+      if (stage != nullptr) stage[bb * steps + (size_t)s] = c;
+    }
+    term[lane] = (double)c;
+    __syncthreads();
+    const int cnt = steps - base < (size_t)QT_WAVE ? (int)(steps - base) : QT_WAVE;
+    for (int i = 0; i < cnt; ++i) J += term[i];
+    __syncthreads();
+  }
+  if (lane == 0) total[bb] = J;
 }
 
 // costs (and optionally trajectories) of every (trajectory, alpha): thread = b * 8 + alpha slot
@@ -166,6 +243,27 @@ int quattro_launch_total_cost(const quattro_model_params& p, const float* x, con
 #ifdef QT_USER_MODEL_HEADER
   else if (p.model_id == QUATTRO_MODEL_USER)
     hipLaunchKernelGGL((total_cost_kernel<QUATTRO_MODEL_USER>), grid, dim3(threads), 0, stream, p, x, u, B, N, cost);
+#endif
+  else
+    return QUATTRO_ERR_UNSUPPORTED;
+  return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;
+}
+
+// one wave (one workgroup) per trajectory; the quadrotor too: the generic stage and final cost, no lane-cooperative form
+int quattro_launch_score(const quattro_model_params& p, const float* x, const float* u, int B, int S, const float* model_phys,
+                         const float* x_ref_rows, int ref_rows, int ref_hold, const float* cost_rows, int terminal, float* stage,
+                         double* total, hipStream_t stream) {
+  const dim3 grid((unsigned)B), block(QT_WAVE);
+  if (p.model_id == QUATTRO_MODEL_CARTPOLE)
+    hipLaunchKernelGGL((score_kernel<QUATTRO_MODEL_CARTPOLE>), grid, block, 0, stream, p, x, u, S, model_phys, x_ref_rows, ref_rows,
+                       ref_hold, cost_rows, terminal, stage, total);
+  else if (p.model_id == QUATTRO_MODEL_QUADROTOR)
+    hipLaunchKernelGGL((score_kernel<QUATTRO_MODEL_QUADROTOR>), grid, block, 0, stream, p, x, u, S, model_phys, x_ref_rows, ref_rows,
+                       ref_hold, cost_rows, terminal, stage, total);
+#ifdef QT_USER_MODEL_HEADER
+  else if (p.model_id == QUATTRO_MODEL_USER)
+    hipLaunchKernelGGL((score_kernel<QUATTRO_MODEL_USER>), grid, block, 0, stream, p, x, u, S, model_phys, x_ref_rows, ref_rows,
+                       ref_hold, cost_rows, terminal, stage, total);
 #endif
   else
     return QUATTRO_ERR_UNSUPPORTED;

@@ -245,8 +245,40 @@ class BatchedMPC:
         xs, _ = ops.simulate(self.model, x.contiguous(), u0.reshape(-1, 1, self.model.m).contiguous())
         return xs[:, 1].contiguous()
 
+    _SCORE_KEYS = ("targets", "weights", "model_phys", "terminal", "ref_hold")
+
+    def _score_args(self, score, B, targets, preview, replan_every):
+        """The keywords of the one ops.score call that `score=` of run() asks for, or None; host logic only.  True: the model's own q, r
+        (not the run's `weights=` candidates), no terminal term, no model_phys, against the run's own targets if it had any -- row s
+        at plant step s under preview, the row of the last replan step without.  A dict overrides any of these."""
+        if score is None or score is False:
+            return None
+        args = dict(targets=targets, weights=None, model_phys=None, terminal=False, ref_hold=1 if preview else int(replan_every))
+        if score is not True:
+            if not isinstance(score, dict):
+                raise ValueError(f"score must be None, True or a dict with keys from {list(self._SCORE_KEYS)} (got {type(score).__name__})")
+            unknown = [key for key in score if key not in self._SCORE_KEYS]
+            if unknown:
+                raise ValueError(f"score has unknown keys {unknown}: the keys are {list(self._SCORE_KEYS)}")
+            args.update(score)
+        ops.check_ref_rows(self.model, args["targets"], B, name="score['targets']" if args["targets"] is not targets else "targets")
+        ops.check_cost_rows(self.model, args["weights"], B, name="score['weights']")
+        ops.check_phys_rows(self.model, args["model_phys"], B, "score['model_phys']")
+        h = args["ref_hold"]
+        if isinstance(h, bool) or int(h) != h or int(h) < 1:
+            raise ValueError(f"score['ref_hold'] must be an integer >= 1 (got {h!r})")
+        args["ref_hold"], args["terminal"] = int(h), bool(args["terminal"])
+        return args
+
+    def _scored(self, out, args):
+        """The dict run() returns, with "score" (B,) float64 and "stage_cost" (B, steps + 1) added where asked for: one ops.score call
+        on the returned x, u, whichever path made them."""
+        if args is not None:
+            out["score"], out["stage_cost"] = ops.score(self.model, out["x"].contiguous(), out["u"].contiguous(), **args)
+        return out
+
     def run(self, x0, steps, disturbance=None, device_loop=True, *, plant=None, plant_phys=None, replan_every=1, feedback=False,
-            model_phys=None, targets=None, preview=True, weights=None):
+            model_phys=None, targets=None, preview=True, weights=None, score=None):
         """Closed loop for `steps` control steps from x0 (B,n); the plant is the device model itself (the reference's
         plant is MuJoCo, out of scope), plus an optional additive state disturbance tensor (steps, B, n).
         Returns dict(x (B,steps+1,n), u (B,steps,m), iters (B,steps)).
@@ -289,10 +321,19 @@ class BatchedMPC:
         (B, m), or one vector for the whole batch; a missing key keeps the model's), a plain (B, 2n + m) array [q | qf | r], or the
         device tensor of ops.cost_rows_tensor.  Controller b PLANS with row b in place of model.q, qf and r in every solve of the
         run: B candidate weightings of one controller against one plant, or a fleet with different priorities.  The tracked steps
-        have no cost.  To compare candidates, score the returned x, u with ops.total_cost under ONE evaluation cost.  One launch
+        have no cost.  To compare candidates, score the run under ONE evaluation cost: `score=` below.  One launch
         (quattro_mpc_run_cost_f32); the kernel rule, refusals and their order are model_phys's, with which — and with targets and
         the plant keywords — it combines.  Cart-pole and user-compiled models; the built-in quadrotor's kernel has no such form yet
-        (NotImplementedError, like a model without a persistent kernel)."""
+        (NotImplementedError, like a model without a persistent kernel).
+
+        score (default None: the dict above, nothing else launched): True adds "stage_cost" (B, steps + 1) float32 -- the cost of every
+        plant step, slot `steps` zero -- and "score" (B,) float64, their sum in step order, from one ops.score call on the returned x, u
+        on every path of run.  They are taken under ONE evaluation cost: the model's own q and r, NOT the candidates of `weights=`, no
+        terminal term, no model_phys, against the run's own `targets` if it had any, as the run followed them (row s at plant step s
+        with preview=True; the row of the last replan step with preview=False).  A dict with any of targets, weights, model_phys,
+        terminal, ref_hold (ops.score's keywords) overrides these: a fleet scored under each controller's own weights, a run scored
+        against another path.  Every model, the quadrotor's weights included.  ValueError for anything else, a wrong shape or
+        ref_hold < 1, before anything touches the device."""
         h = int(replan_every)
         if model_phys is not None:
             if not device_loop:
@@ -318,6 +359,7 @@ class BatchedMPC:
                     raise ValueError(f"plant_phys must have shape {(B0, len(self.model.phys))} (got {tuple(plant_phys.shape)})")
             if feedback and self.solver.max_iter < 1:
                 raise ValueError("feedback needs gains: max_iter >= 1")
+        sc = self._score_args(score, int(np.prod(tuple(np.shape(x0)))) // self.model.n, targets, preview, replan_every)
         x = torch.as_tensor(x0, dtype=torch.float32, device=self.device).reshape(-1, self.model.n).contiguous()
         sv = self.solver
         rows = model_phys is not None or targets is not None or weights is not None
@@ -352,7 +394,7 @@ class BatchedMPC:
                         traj_u, traj_it, disturbance=dist_t, alphas=sv.alphas, reg=sv.reg, alpha_idx=sv.alpha_idx,
                         active=sv.active, iters=sv.iters, status=sv.status, **extra)
             self.u_warm = sv.u.clone()
-            return dict(x=traj_x, u=traj_u, iters=traj_it)
+            return self._scored(dict(x=traj_x, u=traj_u, iters=traj_it), sc)
         if not plain:
             B, n = x.shape[0], self.model.n
             if self.u_warm is not None and self.u_warm.shape[0] != B:
@@ -369,7 +411,7 @@ class BatchedMPC:
                 self.u_warm = torch.cat([u[:, h:]] + [u[:, -1:]] * h, dim=1).contiguous()
                 x = xt[:, -1].contiguous()
                 xs.append(xt[:, 1:]); us.append(ut); its.append(out["iters"].clone())
-            return dict(x=torch.cat(xs, dim=1), u=torch.cat(us, dim=1), iters=torch.stack(its, dim=1))
+            return self._scored(dict(x=torch.cat(xs, dim=1), u=torch.cat(us, dim=1), iters=torch.stack(its, dim=1)), sc)
         xs, us, its = [x], [], []
         for s in range(steps):
             _, u_seq, iters = self.control_step(x)
@@ -377,4 +419,4 @@ class BatchedMPC:
             if disturbance is not None:
                 x = (x + disturbance[s]).contiguous()
             xs.append(x); us.append(u_seq[:, 0]); its.append(iters)
-        return dict(x=torch.stack(xs, dim=1), u=torch.stack(us, dim=1), iters=torch.stack(its, dim=1))
+        return self._scored(dict(x=torch.stack(xs, dim=1), u=torch.stack(us, dim=1), iters=torch.stack(its, dim=1)), sc)

@@ -672,6 +672,44 @@ def cost_rows_tensor(model, weights, B, device, name="weights"):
     return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
+def score(model, x, u, targets=None, weights=None, model_phys=None, terminal=False, ref_hold=1, want_stage=True):
+    """Per-step costs and their fp64 totals of sequences x (B, S+1, n), u (B, S, m), which need not satisfy the dynamics, on the
+    device (quattro_score_f32): -> (total (B,) float64, stage (B, S+1) float32, or None with want_stage=False).
+    stage[b, s] = L(x_s, u_s) for s < S; stage[b, S] = Lf(x_S) with terminal=True, else +0; total[b] is the fp64 sum of stage[b, :]
+    in step order (with terminal=True and no rows: ops.total_cost, bit for bit).  Each trajectory under rows of its own, in the
+    forms the solves and runs take, every model (the built-in quadrotor's weights too: model_can_cost_rows guards solves and runs):
+      targets     as x_ref_rows_tensor takes them: step s is scored against row min((s // ref_hold) * ref_hold, R - 1) of trajectory b
+                  -- ref_hold=1 is "row s", what a run with preview=True was planned against at plant step s; ref_hold=h is the
+                  set-point schedule of preview=False with replan_every=h; past the last row the last row holds
+      weights     as cost_rows_tensor takes them: q, r (and qf for the terminal slot) of row b
+      model_phys  as model_phys_tensor takes them: phys of row b (read by a user model's cost only)
+    None: the model's own x_ref / q, qf, r / phys.  ValueError for a wrong shape or ref_hold < 1, before anything touches the device."""
+    if len(np.shape(x)) != 3 or len(np.shape(u)) != 3:
+        raise ValueError(f"x must have shape (B, S + 1, n) and u (B, S, m) (got {tuple(np.shape(x))} and {tuple(np.shape(u))})")
+    Bt, S, m = (int(v) for v in u.shape)
+    if Bt < 1 or S < 1 or m != model.m or tuple(x.shape) != (Bt, S + 1, model.n):
+        raise ValueError(f"x must have shape (B, S + 1, {model.n}) and u (B, S, {model.m}) with B, S >= 1 "
+                         f"(got {tuple(x.shape)} and {tuple(u.shape)})")
+    check_phys_rows(model, model_phys, Bt, "model_phys")
+    check_ref_rows(model, targets, Bt, name="targets")
+    check_cost_rows(model, weights, Bt, name="weights")
+    if isinstance(ref_hold, bool) or int(ref_hold) != ref_hold or int(ref_hold) < 1:
+        raise ValueError(f"ref_hold must be an integer >= 1 (got {ref_hold!r})")
+    f32 = torch.float32
+    _req(x, (Bt, S + 1, model.n), f32, "x"); _req(u, (Bt, S, model.m), f32, "u")
+    model_phys = model_phys_tensor(model, model_phys, Bt, u.device)
+    rows = x_ref_rows_tensor(model, targets, Bt, u.device, name="targets")
+    cost_rows = cost_rows_tensor(model, weights, Bt, u.device, name="weights")
+    stage = torch.empty((Bt, S + 1), dtype=f32, device=u.device) if want_stage else None
+    total = torch.empty((Bt,), dtype=torch.float64, device=u.device)
+    p = model.c_params()
+    check(_lib.load_for(model).quattro_score_f32(ctypes.byref(p), _ptr(x), _ptr(u), Bt, S, _ptr(model_phys), _ptr(rows),
+                                                 0 if rows is None else rows.shape[1], int(ref_hold), _ptr(cost_rows),
+                                                 _lib.SCORE_TERMINAL if terminal else 0, _ptr(stage), _ptr(total), _stream()),
+          "quattro_score_f32")
+    return total, stage
+
+
 def track(model, x0, x_nom, u_nom, K, steps, plant=None, plant_phys=None, feedback=True, disturbance=None):
     """`steps` <= N plant steps from x0 (B,n) along the first rows of a nominal with its gains (quattro_track_f32):
     u = u_nom[j] + (feedback ? K[j] (x - x_nom[j]) : 0), x <- f_plant(x, u) + disturbance[j].  plant: a DeviceModel like `model`
