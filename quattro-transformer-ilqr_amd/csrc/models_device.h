@@ -325,13 +325,39 @@ struct EulerRecord<QUATTRO_MODEL_CARTPOLE, L> {
   }
 };
 
+// The quotients of parameters that the Euler quadrotor's record entries are built from.  They depend on the model alone, so a kernel
+// whose parameters are the same for every trajectory may take them from its argument block, where the host has left them
+// (fused_args, sweep_tile16_body.h): the same expressions in the same precision, and IEEE division is correctly rounded on the
+// host as on the device, so the bits are those of a division on the spot.  The record kernels (linearize.hip) keep dividing on the
+// device, and the tests that compare the fused sweep with them bit for bit compare the two divisions with it.
+struct QuadQuot {
+  float dm;           // dt / mass
+  float c1, c2, c3;   // (Iy - Iz) / Ix, (Iz - Ix) / Iy, (Ix - Iy) / Iz
+  float ax, ay, kz;   // arm / Ix, arm / Iy, kyaw / Iz
+};
+QT_HD QuadQuot quad_quot(float dt, const float* ph) {
+  const float mass = ph[0], Ix = ph[1], Iy = ph[2], Iz = ph[3], arm = ph[4], kyaw = ph[6];
+  QuadQuot q;
+  q.dm = dt / mass;
+  q.c1 = (Iy - Iz) / Ix;
+  q.c2 = (Iz - Ix) / Iy;
+  q.c3 = (Ix - Iy) / Iz;
+  q.ax = arm / Ix;
+  q.ay = arm / Iy;
+  q.kz = kyaw / Iz;
+  return q;
+}
+
 template <class L>
 struct EulerRecord<QUATTRO_MODEL_QUADROTOR, L> {
   // (`ph`: the seven physical parameters as this trajectory has them -- p.phys, or a row of per-trajectory values the caller holds
-  //  as VALUES (solve_loop.h: model_phys); the two-argument forms below are the shared-parameter case)
+  //  as VALUES (solve_loop.h: model_phys); the two-argument forms below are the shared-parameter case.  The forms that take a
+  //  QuadQuot do the work; the others divide and forward)
   static __device__ __forceinline__ void fill_const(float* rec, const quattro_model_params& p) { fill_const(rec, p, p.phys); }
   static __device__ __forceinline__ void fill_const(float* rec, const quattro_model_params& p, const float* ph) {
-    const float Ix = ph[1], Iy = ph[2], Iz = ph[3], arm = ph[4], kyaw = ph[6];
+    fill_const(rec, p, quad_quot(p.dt, ph));
+  }
+  static __device__ __forceinline__ void fill_const(float* rec, const quattro_model_params& p, const QuadQuot& qq) {
     const float dt = p.dt;
     for (int i = 0; i < 12; ++i) {
       rec[L::a(i, i)] = 1.0f;
@@ -341,9 +367,9 @@ struct EulerRecord<QUATTRO_MODEL_QUADROTOR, L> {
     rec[L::a(6, 9)] = dt;
     const float sphi[4] = {-1.0f, 1.0f, 1.0f, -1.0f}, sth[4] = {1.0f, 1.0f, -1.0f, -1.0f}, sps[4] = {1.0f, -1.0f, 1.0f, -1.0f};
     for (int a = 0; a < 4; ++a) {
-      rec[L::b(9, a)] = dt * sphi[a] * (arm / Ix);
-      rec[L::b(10, a)] = dt * sth[a] * (arm / Iy);
-      rec[L::b(11, a)] = dt * sps[a] * (kyaw / Iz);
+      rec[L::b(9, a)] = dt * sphi[a] * qq.ax;
+      rec[L::b(10, a)] = dt * sth[a] * qq.ay;
+      rec[L::b(11, a)] = dt * sps[a] * qq.kz;
       rec[L::luu(a, a)] = 2.0f * p.r[a];
     }
   }
@@ -365,8 +391,12 @@ struct EulerRecord<QUATTRO_MODEL_QUADROTOR, L> {
   }
   static __device__ __forceinline__ void fill_dynamics(float* rec, const quattro_model_params& p, const float* ph,
                                                        const QuadTrig& t, const float* x, const float* u) {
+    fill_dynamics(rec, p, ph[0], quad_quot(p.dt, ph), t, x, u);
+  }
+  // (the thrust per mass depends on the state: it stays a division by the mass)
+  static __device__ __forceinline__ void fill_dynamics(float* rec, const quattro_model_params& p, const float mass, const QuadQuot& qq,
+                                                       const QuadTrig& t, const float* x, const float* u) {
 #pragma clang fp contract(off)
-    const float mass = ph[0], Ix = ph[1], Iy = ph[2], Iz = ph[3];
     const float dt = p.dt;
     const float wp = x[9], wq = x[10], wr = x[11];
     const float tm = (u[0] + u[1] + u[2] + u[3]) / mass;
@@ -382,7 +412,7 @@ struct EulerRecord<QUATTRO_MODEL_QUADROTOR, L> {
     rec[L::a(4, 8)] = -dtm * rx;
     rec[L::a(5, 6)] = -dtm * t.cth * t.sph;
     rec[L::a(5, 7)] = -dtm * t.sth * t.cph;
-    const float dm = dt / mass;
+    const float dm = qq.dm;
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
       rec[L::b(3, a)] = dm * rx;
@@ -403,7 +433,7 @@ struct EulerRecord<QUATTRO_MODEL_QUADROTOR, L> {
     rec[L::a(8, 7)] = dt * mix * t.sth * sec2;
     rec[L::a(8, 10)] = dt * t.sph * t.sec;
     rec[L::a(8, 11)] = dt * t.cph * t.sec;
-    const float c1 = (Iy - Iz) / Ix, c2 = (Iz - Ix) / Iy, c3 = (Ix - Iy) / Iz;
+    const float c1 = qq.c1, c2 = qq.c2, c3 = qq.c3;
     rec[L::a(9, 10)] = dt * c1 * wr;
     rec[L::a(9, 11)] = dt * c1 * wq;
     rec[L::a(10, 9)] = dt * c2 * wr;

@@ -74,9 +74,16 @@ __device__ __forceinline__ float recip(float x) { return __builtin_amdgcn_rcpf(x
 // from `S`: R itself, except for the first pivot, whose column (tile column 3) has been handed to Q_u by then (see step()) and
 // survives in a copy.  The right-hand side Q_u needs no instructions of its own: it rides in tile column 3 of R.
 template <int P, bool CHECK>
-__device__ __forceinline__ void gj_step(float& R, const float S, int r, int c4, float& pivmin, float R0, bool& illc) {
+__device__ __forceinline__ void gj_step(float& R, const float S, int r, int c4, unsigned& pivz, float R0, bool& illc) {
   const float piv = qt_readlane(S, 16 * P + 4 * P + 3);
-  pivmin = fminf(pivmin, fabsf(piv));
+  // a zero pivot, +0 or -0, is all the SINGULAR bit reports (a NaN pivot poisons the gains: NONFINITE; a denormal one is a pivot).
+  // The pivot is wave-uniform, so the test is scalar work on its bit pattern: the smallest pattern seen, sign shifted out, is
+  // kept (s_lshl_b32 + s_min_u32).  The empty asm statements pin both to scalar registers as plain integers: left alone, the
+  // compiler reads the shift as fabs and compares in floating point, or folds two minima into v_min3_u32 — vector work again.
+  unsigned pb = __float_as_uint(piv);
+  asm("" : "+s"(pb));
+  pivz = min(pivz, pb << 1);
+  asm("" : "+s"(pivz));
   if constexpr (CHECK) {
     const float d0 = qt_readlane(R0, 16 * P + 4 * P + 3);   // (Q_uu + reg I)[P][P] before any elimination
     illc = illc || !(piv > 1.0e-6f * fabsf(d0));            // also true for piv <= 0 and NaN
@@ -98,6 +105,15 @@ __device__ __forceinline__ void gj_step(float& R, const float S, int r, int c4, 
 // block raised instead 64.0, three levels (pivots 3, transposition 2, rest 1) 60.1 us.
 
 constexpr int LD = 20;  // LDS row pitch (floats) of the 16x16 transpose tile: 16-B aligned rows, conflict-free b128 writes
+
+// An LDS location as the 32-bit byte address a lane keeps in a register of its own (pinned there by an empty asm statement where
+// it is formed).  From a pointer and an index the compiler forms the address again at every use — shift, add, a select for a
+// per-lane stride: five vector instructions per step of the fused recursion for its three record loads and one for the
+// transposition tile's write, none of which depends on the step.
+typedef __attribute__((address_space(3))) float LdsF32;
+typedef __attribute__((address_space(3))) f32x4 LdsF32x4;
+__device__ __forceinline__ unsigned lds_addr(const float* p) { return (unsigned)(uintptr_t)(const LdsF32*)p; }
+__device__ __forceinline__ float lds_f32(unsigned a) { return *(const LdsF32*)(uintptr_t)a; }
 
 // MODE_FUSED (Euler quadrotor): no record buffer at all.  The 76 state-dependent floats of a TILE16C record are functions
 // of (x_t, u_t) only, not of the value function, so the wave linearises its own trajectory ahead of the chain: two lanes
@@ -153,6 +169,9 @@ struct FusedArgs {
   int k_rows;       // rows per trajectory of the gain arrays the fused modes write: 0 = N - t_start (index t - t_start);
                     // N = the full stacks, step t written in place at row t (quattro_linearize_sweep_rows_f32)
   int rn, rm;       // MODE_ROWPAD: the problem's own dimensions (records, terminal pair and gains are laid out for them)
+  QuadQuot quot;    // MODE_FUSED: the parameter quotients of p (quad_quot), divided once on the host instead of by every wave of every
+                    // launch (eight division sequences, ~90 vector instructions per wave).  Per-trajectory parameters (PHYS) are
+                    // divided on the device as before
 };
 // (host) the argument block of the fused quadrotor modes; coef = NULL unless MODE_FUSED_RK4
 inline FusedArgs fused_args(const quattro_model_params& p, const float* x, const float* u, int B, int N, int t_start,
@@ -168,6 +187,7 @@ inline FusedArgs fused_args(const quattro_model_params& p, const float* x, const
   fa.k_rows = k_rows;
   fa.rn = 12;
   fa.rm = 4;
+  fa.quot = quad_quot(p.dt, p.phys);
   return fa;
 }
 
@@ -328,6 +348,8 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
     for (int i = 0; i < 8; ++i) phv[i] = row[i];
   }
   const float* const ph = PHYS ? phv : fa.p.phys;
+  QuadQuot qq{};                              // MODE_FUSED: the argument block's, or those of this trajectory's row
+  if constexpr (MODE == MODE_FUSED) qq = PHYS ? quad_quot(fa.p.dt, ph) : fa.quot;
   constexpr bool ROWPAD = MODE == MODE_ROWPAD;
   constexpr bool COMPACT = MODE != MODE_TILE16 && !ROWPAD;   // constants of the problem in a header record
   constexpr int REC_STRIDE = MODE == MODE_TILE16 ? Tile16Rec::STRIDE : MODE == MODE_DENSEF ? Tile16RRec::STRIDE : Tile16CRec::STRIDE;
@@ -363,9 +385,9 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
       static_assert(sweep_lin_floats<MODE>() % 4 == 0, "the LDS slice is zeroed in 16-byte pieces");
       for (int i = lane; i < sweep_lin_floats<MODE>() / 4; i += QT_WAVE) reinterpret_cast<f32x4*>(s_lin)[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
       wave_sync();
-      if (lane == 0) EulerRecord<QUATTRO_MODEL_QUADROTOR, Tile16Rec>::fill_const(s_lin, fa.p, ph);
+      if (lane == 0) EulerRecord<QUATTRO_MODEL_QUADROTOR, Tile16Rec>::fill_const(s_lin, fa.p, qq);
       if (lane < FUSED_BATCH)
-        EulerRecord<QUATTRO_MODEL_QUADROTOR, Tile16FRec>::fill_const(s_lin + Tile16Rec::STRIDE + lane * Tile16FRec::STRIDE, fa.p, ph);
+        EulerRecord<QUATTRO_MODEL_QUADROTOR, Tile16FRec>::fill_const(s_lin + Tile16Rec::STRIDE + lane * Tile16FRec::STRIDE, fa.p, qq);
       wave_sync();
     }
   } else if constexpr (ROWPAD) {
@@ -401,15 +423,21 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
   LanePtrs lp;
   int pad_of[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pad_stride = 0;     // MODE_ROWPAD (see below)
   const float* pad_base = nullptr;
-  // MODE_FUSED: float offsets into s_lin of this lane's three loads (+ local step x STRIDE for the dynamic ones)
-  int of_f = 0, of_q = 0, of_z = 0;
+  // The fused modes read l_uu[r][r] and l_z[z(c)] of a step from ONE per-lane base: only the lanes (r, u_r) use l_uu (qsel), and
+  // for them the two entries lie a constant apart (FZQ / RZQ floats); every other lane reads a neighbouring entry of the same
+  // record there and drops it.
+  // MODE_FUSED_RK4: float offset into s_lin of l_z (+ local step x COST_STEP).  MODE_FUSED: byte addresses in LDS of the F triple
+  // and of l_uu (+ local step x stride; the stride of the F triple is the record's for a dynamic lane, 0 for one that reads the header)
+  constexpr int FZQ = Tile16FRec::LZ + 12 - Tile16FRec::LUUD, RZQ = Rk4Tab::LUUD - 12;
+  static_assert(FZQ > 0 && FZQ <= Tile16FRec::LZ && RZQ >= 0 && 16 + RZQ <= Rk4Tab::COST_STEP, "l_uu and l_z from one base, inside the record");
+  int of_z = 0;
+  unsigned af = 0, af_step = 0, aq = 0;
   f32x4 lqc = {0.0f, 0.0f, 0.0f, 0.0f};
   const bool qsel = ucol && (g == r);
   if constexpr (RK4F) {
     lp.dynf = true;
     lp.dynq = ucol;
     lp.pf = lp.plq = lp.plz = nullptr;
-    of_q = Rk4Tab::COST + Rk4Tab::LUUD + r;
     of_z = Rk4Tab::COST + (ucol ? 12 + g : xj);
     // l_xx = 2Q (diagonal), l_ux = 0: this lane's quad (l_xx[3r..3r+2][x_j], l_ux[r][x_j]) straight from the parameters
     if (!ucol) {
@@ -421,9 +449,10 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
     lp.dynf = d >= 0;
     lp.dynq = ucol;
     lp.pf = lp.plq = lp.plz = nullptr;
-    of_f = lp.dynf ? Tile16Rec::STRIDE + Tile16FRec::F + 3 * d : Tile16Rec::F + 3 * lane;
-    of_q = Tile16Rec::STRIDE + Tile16FRec::LUUD + r;
-    of_z = Tile16Rec::STRIDE + Tile16FRec::LZ + (ucol ? 12 + g : xj);
+    af = lds_addr(s_lin + (lp.dynf ? Tile16Rec::STRIDE + Tile16FRec::F + 3 * d : Tile16Rec::F + 3 * lane));
+    af_step = lp.dynf ? 4 * Tile16FRec::STRIDE : 0;
+    aq = lds_addr(s_lin + Tile16Rec::STRIDE + Tile16FRec::LZ + (ucol ? 12 + g : xj) - FZQ);
+    asm volatile("" : "+v"(af), "+v"(af_step), "+v"(aq));
     // l_xx = 2Q and l_ux = 0 are constants of the problem: this lane's quad of them stays in registers for the whole
     // sweep; only l_uu[r][r] (one float, control-column lane g == r) changes from step to step
     if (!ucol) lqc = *reinterpret_cast<const f32x4*>(&s_lin[Tile16Rec::LXB + 4 * (12 * r + xj)]);
@@ -500,8 +529,10 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
       rk_eye[q] = (4 * r + q == c) ? 1.0f : 0.0f;
     }
   }
+  unsigned a_tw = lds_addr(s_t + c * LD + 4 * r);   // where this lane writes its quad of the transposed tile
+  asm volatile("" : "+v"(a_tw));
   bool bad = false, illc = false;
-  float pivmin = 3.0e38f;   // smallest |pivot| seen: 0 (or NaN-poisoned gains) marks a singular Q_uu + reg I
+  unsigned pivz = ~0u;      // smallest pivot bit pattern seen, without its sign (wave-uniform): 0 marks a singular Q_uu + reg I
 
   // one step of the recursion on the record held in `cur`
   auto step = [&](const StepRegs& cur, int s) __attribute__((always_inline)) {
@@ -540,10 +571,10 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
     // (bit-identical k), sixteen vector instructions fewer per step — the elimination is 23 % of the kernel.
     R = (c == 3) ? qu : R;
     __builtin_amdgcn_s_setprio(2);          // the pivots
-    gj_step<0, CHECK_PIVOTS>(R, R0, r, c4, pivmin, R0, illc);
-    gj_step<1, CHECK_PIVOTS>(R, R, r, c4, pivmin, R0, illc);
-    gj_step<2, CHECK_PIVOTS>(R, R, r, c4, pivmin, R0, illc);
-    gj_step<3, CHECK_PIVOTS>(R, R, r, c4, pivmin, R0, illc);
+    gj_step<0, CHECK_PIVOTS>(R, R0, r, c4, pivz, R0, illc);
+    gj_step<1, CHECK_PIVOTS>(R, R, r, c4, pivz, R0, illc);
+    gj_step<2, CHECK_PIVOTS>(R, R, r, c4, pivz, R0, illc);
+    gj_step<3, CHECK_PIVOTS>(R, R, r, c4, pivz, R0, illc);
     // In the control columns of the tile the three values below are meaningless (they hold -I, Q_uu - reg I): they
     // are left as they are.  Every product that follows only ever combines state-column lanes with state-row
     // registers into the state-state entries that survive, so nothing is spent on zeroing the rest.
@@ -567,7 +598,7 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
     // operand roles swapped, no data movement at all — 101 vs 86 us, the MFMA pipe is the contended resource at 4 waves
     // per SIMD.)
     wave_sync();
-    *reinterpret_cast<f32x4*>(&s_t[c * LD + 4 * r]) = Vn;
+    *(LdsF32x4*)(uintptr_t)a_tw = Vn;
     s_vx[lane] = vxn;        // (every lane into a slot of its own — s_vx has 64 floats, the first 16 are read: a store behind
                              //  `if (r == 0)` is an exec-mask branch per step)
     wave_sync();
@@ -629,18 +660,21 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
       o.f0 = fmaf(sixth, acc[0] + D[0], rk_eye[0]);
       o.f1 = fmaf(sixth, acc[1] + D[1], rk_eye[1]);
       o.f2 = fmaf(sixth, acc[2] + D[2], rk_eye[2]);
-      o.lq = f32x4{s_lin[of_q + ls * Rk4Tab::COST_STEP], 0.0f, 0.0f, 0.0f};
-      o.lz = s_lin[of_z + ls * Rk4Tab::COST_STEP];
+      const float* cz = s_lin + of_z + ls * Rk4Tab::COST_STEP;
+      o.lq = f32x4{cz[RZQ], 0.0f, 0.0f, 0.0f};
+      o.lz = cz[0];
       return o;
     } else if constexpr (FUSED) {
       StepRegs o;
-      const int off = ls * Tile16FRec::STRIDE;
-      const int a = of_f + (lp.dynf ? off : 0);
-      o.f0 = s_lin[a + 0];
-      o.f1 = s_lin[a + 1];
-      o.f2 = s_lin[a + 2];
-      o.lq = f32x4{s_lin[of_q + off], 0.0f, 0.0f, 0.0f};
-      o.lz = s_lin[of_z + off];
+      // two vector instructions of address arithmetic per step: base + step x per-lane stride (one v_mad_u32_u24), base + step x
+      // record pitch (the product is scalar); everything else is an immediate offset of the load
+      const unsigned a = af + __umul24((unsigned)ls, af_step);
+      const unsigned q = aq + (unsigned)ls * (4 * Tile16FRec::STRIDE);
+      o.f0 = lds_f32(a);
+      o.f1 = lds_f32(a + 4);
+      o.f2 = lds_f32(a + 8);
+      o.lq = f32x4{lds_f32(q), 0.0f, 0.0f, 0.0f};
+      o.lz = lds_f32(q + 4 * FZQ);
       return o;
     } else if constexpr (ROWPAD) {
       // every entry unconditionally from a clamped offset (a conditional load is a branch), constants selected afterwards:
@@ -785,7 +819,7 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
           float* mine = stage + sl * Tile16FRec::STRIDE;
           if (dynl) {
             quad_trig_finish(tr);
-            ER::fill_dynamics(mine, fa.p, ph, tr, xs, us);
+            ER::fill_dynamics(mine, fa.p, ph[0], qq, tr, xs, us);
           } else {
             ER::fill_lx(mine, fa.p, xr, xs);
           }
@@ -800,7 +834,7 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
   } else {
     run(S, 0);
   }
-  const bool singular = !(pivmin > 0.0f);
+  const bool singular = pivz == 0u;
   if (status != nullptr) {
     const bool any_bad = __any(bad);
     if (lane == 0)
