@@ -3,9 +3,10 @@
 // Same arithmetic as rollout.hip (reference quattro_ilqr_tf.py: simulate :127-132, compute_total_cost :138-143,
 // forward_pass :377-390, alpha loop + stop test of optimize :433-451, :472), different mapping.  A rollout is a serial
 // chain in t, and with one lane per candidate a B = 4096 line search is only 512 waves on 1024 SIMDs: every wave runs
-// alone on its SIMD, issues one instruction (vector OR scalar) per 4-cycle slot, and a step of ~550 instructions costs
-// 1.7 us.  Splitting a step over the 4 lanes of a quad cuts the per-wave instruction count ~4x and gives 4x the waves
-// (2 per SIMD at B = 4096), so the chain gets shorter and the SIMDs fill up.
+// alone on its SIMD, issues one instruction (vector OR scalar) per 4-cycle slot, and a step of that ONE-LANE form, ~550
+// instructions, costs 1.7 us.  Splitting a step over the 4 lanes of a quad cuts the per-wave instruction count ~4x and gives
+// 4x the waves (2 per SIMD at B = 4096), so the chain gets shorter and the SIMDs fill up.  (What a step of the quad form
+// issues today is stated once, at quad_rollout_closed in rollout_quad_body.h.)
 //
 // Lane roles inside a quad (j = lane & 3):
 //   axis lane a = j < 3 owns the four states of its axis: (p_a, v_a, angle_a, omega_a) = x[a], x[3+a], x[6+a], x[9+a];

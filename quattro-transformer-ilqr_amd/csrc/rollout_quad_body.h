@@ -36,6 +36,12 @@ struct LaneConst {
   __device__ __forceinline__ float sel(float v0, float v1, float v2) const { return is0 ? v0 : (is1 ? v1 : v2); }
 };
 
+// the torque row as VALUES in registers.  tc[3] is -gain in every role, and left to itself the compiler keeps gain and negates it at
+// each use that cannot take a source modifier -- QuadDrive's DPP multiply-adds: a v_xor per step.
+__device__ __forceinline__ void pin_torque_row(LaneConst& L) {
+  asm("" : "+v"(L.tc[0]), "+v"(L.tc[1]), "+v"(L.tc[2]), "+v"(L.tc[3]));   // (not volatile: a row nobody reads still drops out)
+}
+
 __device__ __forceinline__ LaneConst lane_const(const quattro_model_params& p, int j) {
   LaneConst L;
   L.j = j;
@@ -57,6 +63,7 @@ __device__ __forceinline__ LaneConst lane_const(const quattro_model_params& p, i
               s3 = L.sel(-1.0f, -1.0f, -1.0f);
   const float gain = L.sel(arm / Ix, arm / Iy, kyaw / Iz);
   L.tc[0] = s0 * gain; L.tc[1] = s1 * gain; L.tc[2] = s2 * gain; L.tc[3] = s3 * gain;
+  pin_torque_row(L);
   L.gy = L.sel((Iy - Iz) / Ix, (Iz - Ix) / Iy, (Ix - Iy) / Iz);
   L.gz = L.sel(0.0f, 0.0f, -p.phys[5]);
   L.inv_mass = 1.0f / p.phys[0];
@@ -88,6 +95,7 @@ __device__ __forceinline__ LaneConst lane_const_plant(const PlantSpec& plant, co
               s3 = L.sel(-1.0f, -1.0f, -1.0f);
   const float gain = L.sel(arm / Ix, arm / Iy, kyaw / Iz);
   L.tc[0] = s0 * gain; L.tc[1] = s1 * gain; L.tc[2] = s2 * gain; L.tc[3] = s3 * gain;
+  pin_torque_row(L);
   L.gy = L.sel((Iy - Iz) / Ix, (Iz - Ix) / Iy, (Ix - Iy) / Iz);
   L.gz = L.sel(0.0f, 0.0f, -grav);
   L.inv_mass = 1.0f / mass;
@@ -111,6 +119,7 @@ __device__ __forceinline__ LaneConst lane_const_phys(const quattro_model_params&
               s3 = L.sel(-1.0f, -1.0f, -1.0f);
   const float gain = L.sel(arm / Ix, arm / Iy, kyaw / Iz);
   L.tc[0] = s0 * gain; L.tc[1] = s1 * gain; L.tc[2] = s2 * gain; L.tc[3] = s3 * gain;
+  pin_torque_row(L);
   L.gy = L.sel((Iy - Iz) / Ix, (Iz - Ix) / Iy, (Ix - Iy) / Iz);
   L.gz = L.sel(0.0f, 0.0f, -grav);
   L.inv_mass = 1.0f / mass;
@@ -124,12 +133,51 @@ __device__ __forceinline__ LaneConst lane_const_of(const quattro_model_params& p
   else return lane_const(p, j);
 }
 
-// the four controls of the quad (lane j owns u_j), in every lane: broadcast ONCE per step and shared by the rate
-// function (four calls under RK4) and the store
+// the four controls of the quad: lane j holds u_j (`own`).  Round 6: they are broadcast to every lane (`c`, four DPP moves, as
+// rounds 2 - 5 did for every step) only where the step's store wants all four in one lane anyway -- lane 3's record, the control
+// row of gather_quarter: Store::ALL_U.  A step that stores its own lane's values (simulate, the tracked plant, a cost-only
+// rollout) keeps `own` alone, and the rate function reads the quad through DPP operands (QuadDrive).
 struct QuadU {
-  float u0, u1, u2, u3;
-  __device__ __forceinline__ explicit QuadU(float uo)
-      : u0(quad_bcast<0>(uo)), u1(quad_bcast<1>(uo)), u2(quad_bcast<2>(uo)), u3(quad_bcast<3>(uo)) {}
+  float own;
+  bool all;
+  float c[4];
+  __device__ __forceinline__ explicit QuadU(float uo, bool want_all = false) : own(uo), all(want_all) {
+    if (all) { c[0] = quad_bcast<0>(uo); c[1] = quad_bcast<1>(uo); c[2] = quad_bcast<2>(uo); c[3] = quad_bcast<3>(uo); }
+  }
+};
+
+// what the rate function takes from the controls, once per step (the four stage calls of RK4 share it): thrust / mass and this
+// lane's torque row.  From the broadcast copies where the step has them.  Where not: v_add_f32_dpp / v_mul_f32_dpp /
+// v_fmac_f32_dpp on the own-control register -- gain_dot's idiom, its leading s_nop for the VALU-write -> DPP-read hazard
+// included -- with one move left (the sum's first term; only src0 can be the DPP operand): 9 issue slots for the 11 of four moves
+// and seven operations.  (With the four moves needed anyway it would be 13: measured, the line search 0.6 us slower.)  Same values
+// either way: a + b and a * b commute bit for bit, the sum keeps its association ((u0 + u1) + u2) + u3 and the row its order
+// tc0 u0, + tc1 u1, + tc2 u2, + tc3 u3, fused as before.
+struct QuadDrive {
+  float tm, tau;
+  __device__ __forceinline__ QuadDrive(const LaneConst& L, const QuadU& U) {
+    if (U.all) {
+      tm = (U.c[0] + U.c[1] + U.c[2] + U.c[3]) * L.inv_mass;
+      tau = fmaf(L.tc[3], U.c[3], fmaf(L.tc[2], U.c[2], fmaf(L.tc[1], U.c[1], L.tc[0] * U.c[0])));
+      return;
+    }
+    float s, t;
+#define QT_DP(l) " quad_perm:[" l "," l "," l "," l "] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+    asm volatile("s_nop 1\n\t"
+                 "v_mov_b32_dpp %0, %2" QT_DP("0")
+                 "v_mul_f32_dpp %1, %2, %3" QT_DP("0")
+                 "v_add_f32_dpp %0, %2, %0" QT_DP("1")
+                 "v_fmac_f32_dpp %1, %2, %4" QT_DP("1")
+                 "v_add_f32_dpp %0, %2, %0" QT_DP("2")
+                 "v_fmac_f32_dpp %1, %2, %5" QT_DP("2")
+                 "v_add_f32_dpp %0, %2, %0" QT_DP("3")
+                 "v_fmac_f32_dpp %1, %2, %6" QT_DP("3")
+                 : "=&v"(s), "=&v"(t)
+                 : "v"(U.own), "v"(L.tc[0]), "v"(L.tc[1]), "v"(L.tc[2]), "v"(L.tc[3]));
+#undef QT_DP
+    tm = s * L.inv_mass;
+    tau = t;
+  }
 };
 
 // time derivative of the own states xo = (p_a, v_a, angle_a, omega_a) given the quad's controls
@@ -154,10 +202,8 @@ __device__ __forceinline__ void stage_sincos(const TrigBase& b, float x, float* 
 }
 
 template <bool STAGE>
-__device__ __forceinline__ void quad_rate(const LaneConst& L, const float* xo, const QuadU& U, float* xd, TrigBase& tb) {
-  const float u0 = U.u0, u1 = U.u1, u2 = U.u2, u3 = U.u3;
-  const float tm = (u0 + u1 + u2 + u3) * L.inv_mass;
-  const float tau = fmaf(L.tc[3], u3, fmaf(L.tc[2], u2, fmaf(L.tc[1], u1, L.tc[0] * u0)));
+__device__ __forceinline__ void quad_rate(const LaneConst& L, const float* xo, const QuadDrive& D, float* xd, TrigBase& tb) {
+  const float tm = D.tm, tau = D.tau;
   float so, co;
   if constexpr (STAGE) {
     stage_sincos(tb, xo[2], &so, &co);
@@ -178,29 +224,45 @@ __device__ __forceinline__ void quad_rate(const LaneConst& L, const float* xo, c
   // Euler-angle rates
   const float mix = fmaf(wq, sph, wr * cph);
   xd[2] = L.sel(fmaf(mix, tth, wp), fmaf(wq, cph, -(wr * sph)), mix * sec);
-  // body rates
-  xd[3] = fmaf(L.gy, L.sel(wq * wr, wp * wr, wp * wq), tau);
+  // body rates: the lane's product omega_b omega_c -- wq wr, wp wr, wp wq by axis, lane 3 as axis 0 -- as a product of two quad
+  // permutations of the body-rate register, [q, p, p, q] x [r, r, q, r]: the operands and their order per lane are those of the
+  // role select over three products that stood here (two multiplies and two selects in the ISA)
+  xd[3] = fmaf(L.gy, quad_perm<QT_QP(1, 0, 0, 1)>(xo[3]) * quad_perm<QT_QP(2, 2, 1, 2)>(xo[3]), tau);
 }
 
 template <bool RK4>
 __device__ __forceinline__ void quad_step(const LaneConst& L, const float* xo, const QuadU& uo, float* xn) {
+  const QuadDrive D(L, uo);
   TrigBase tb;
   if constexpr (!RK4) {
     float k1[4];
-    quad_rate<false>(L, xo, uo, k1, tb);
+    quad_rate<false>(L, xo, D, k1, tb);
 #pragma unroll
     for (int g = 0; g < 4; ++g) xn[g] = fmaf(L.dt, k1[g], xo[g]);
   } else {   // stage 0 sets the trig base, the later stages reach their angles from it by angle addition
     rk4_step<4>(L.dt, xo, xn, [&](int s, const float* xs, float* k) __attribute__((always_inline)) {
-      if (s == 0) quad_rate<false>(L, xs, uo, k, tb);
-      else quad_rate<true>(L, xs, uo, k, tb);
+      if (s == 0) quad_rate<false>(L, xs, D, k, tb);
+      else quad_rate<true>(L, xs, D, k, tb);
     });
   }
 }
 
+// The lanes whose barrier term counts, as lane_stage_cost takes them: the lanes of rollouts whose result is used -- or none where
+// the problem has no barrier.  Taken once, outside the step loop.  The test is p.barrier_alpha != 0.0f on the BITS (true for NaN,
+// false for +-0): as a float compare inside the step the compiler kept the wave-uniform, loop-invariant answer as a 0/1 VGPR and
+// compared it again every step (v_cndmask, v_cmp, s_andn2, s_cbranch).  Folded into the mask, the step's one remaining test --
+// may the short cut be taken -- answers both.
+__device__ __forceinline__ unsigned long long barrier_lanes(const quattro_model_params& p, bool counted) {
+  const bool on = (__float_as_uint(p.barrier_alpha) << 1) != 0u;
+  unsigned long long m = on ? __builtin_amdgcn_ballot_w64(counted) : 0ull;
+  asm volatile("" : "+s"(m));   // (a value from here on: the select is not carried into the loop)
+  return m;
+}
+
 // this lane's share of L(x,u): its four state terms, its control's R and barrier terms.  `counted` = lane belongs to a
 // rollout whose result is used (the wave-uniform barrier shortcut must not be vetoed by idle quads), as a lane mask the caller
-// takes once, outside its loop (__builtin_amdgcn_ballot_w64(counted)).
+// takes once, outside its loop: barrier_lanes(p, counted), which is empty where p has no barrier -- the term is then never added,
+// as `if (p.barrier_alpha != 0.0f)` around it had it.
 __device__ __forceinline__ float lane_stage_cost(const quattro_model_params& p, const LaneConst& L, const float* xo,
                                                  float uo, unsigned long long counted) {
   float c = 0.0f;
@@ -210,18 +272,16 @@ __device__ __forceinline__ float lane_stage_cost(const quattro_model_params& p, 
     c = fmaf(L.qw[g] * d, d, c);
   }
   c = fmaf(L.rj * uo, uo, c);
-  if (p.barrier_alpha != 0.0f) {
-    // exact shortcut, per lane (see qt_stage_cost): with beta*u > 20 the lane's barrier term is below
-    // alpha * 4.25e-18 / beta^2; when that is under half an ulp of c the fmaf below returns c unchanged
-    const float ib = 1.0f / p.barrier_beta;
-    // (the wave-wide test as lane masks of the two raw compares combined on the scalar unit: `__all(a && b)` makes the
-    // compiler materialise the conjunction as a 0/1 VGPR and compare it again)
-    const unsigned long long big = __builtin_amdgcn_ballot_w64(p.barrier_beta * uo > 20.0f);
-    const unsigned long long tiny = __builtin_amdgcn_ballot_w64(fabsf(p.barrier_alpha) * 4.25e-18f * ib * ib < c * 2.9e-8f);
-    if ((counted & ~(big & tiny)) != 0ull) {
-      const float sp = qt_softplus(-uo, p.barrier_beta);
-      c = fmaf(p.barrier_alpha, sp * sp, c);
-    }
+  // exact shortcut, per lane (see qt_stage_cost): with beta*u > 20 the lane's barrier term is below
+  // alpha * 4.25e-18 / beta^2; when that is under half an ulp of c the fmaf below returns c unchanged
+  const float ib = 1.0f / p.barrier_beta;
+  // (the wave-wide test as lane masks of the two raw compares combined on the scalar unit: `__all(a && b)` makes the
+  // compiler materialise the conjunction as a 0/1 VGPR and compare it again)
+  const unsigned long long big = __builtin_amdgcn_ballot_w64(p.barrier_beta * uo > 20.0f);
+  const unsigned long long tiny = __builtin_amdgcn_ballot_w64(fabsf(p.barrier_alpha) * 4.25e-18f * ib * ib < c * 2.9e-8f);
+  if ((counted & ~(big & tiny)) != 0ull) {
+    const float sp = qt_softplus(-uo, p.barrier_beta);
+    c = fmaf(p.barrier_alpha, sp * sp, c);
   }
   return c;
 }
@@ -341,13 +401,15 @@ __device__ __forceinline__ float4 gather_quarter(const LaneConst& L, const QuadU
   const float t2 = quad_perm<QT_QP(2, 0, 1, 3)>(L.sel(xn[2], xn[3], xn[0]));         // states 2, 6, 10
   const float t3 = L.sel(xn[1], xn[2], xn[3]);                                       // own lane: states 3, 7, 11
   const bool l3 = L.j == 3;
-  return make_float4(l3 ? U.u0 : t0, l3 ? U.u1 : t1, l3 ? U.u2 : t2, l3 ? U.u3 : t3);
+  return make_float4(l3 ? U.c[0] : t0, l3 ? U.c[1] : t1, l3 ? U.c[2] : t2, l3 ? U.c[3] : t3);
 }
 
 struct NoStore {
+  static constexpr bool ALL_U = false;
   __device__ __forceinline__ void operator()(const LaneConst&, int, const QuadU&, const float*) const {}
 };
 struct ArrayStore {     // x_new [N+1][12], u_new [N][4]
+  static constexpr bool ALL_U = true;
   float* base;          // lanes 0..2: x_new + 12 + 4j (row t+1 at + 12 t); lane 3: u_new (row t at + 4 t)
   int stride;
   bool en;
@@ -363,11 +425,12 @@ struct ArrayStore {     // x_new [N+1][12], u_new [N][4]
 // inside the quad on the serial chain (it was ~16 of a step's ~175 vector instructions, for all six candidates); the
 // one candidate that is accepted is put back into natural order by the copy that commits it.
 struct ScratchStore {
+  static constexpr bool ALL_U = true;
   float* s;
   bool en, l3;
   __device__ __forceinline__ ScratchStore(const LaneConst& L, float* rec, bool en_) : s(rec + 4 * L.j), en(en_), l3(L.j == 3) {}
   __device__ __forceinline__ void operator()(const LaneConst&, int t, const QuadU& U, const float* xnext) const {
-    const float4 v = make_float4(l3 ? U.u0 : xnext[0], l3 ? U.u1 : xnext[1], l3 ? U.u2 : xnext[2], l3 ? U.u3 : xnext[3]);
+    const float4 v = make_float4(l3 ? U.c[0] : xnext[0], l3 ? U.c[1] : xnext[1], l3 ? U.c[2] : xnext[2], l3 ? U.c[3] : xnext[3]);
     if (en) *reinterpret_cast<float4*>(s + (size_t)t * CS) = v;
   }
 };
@@ -434,6 +497,10 @@ __device__ __forceinline__ void quad_track_body(const LaneConst& L, const bool r
 }
 
 // One closed-loop rollout by a quad.  Returns this LANE's partial of sum_t L + Lf (fp64); quad_sum() gives the total.
+// What a step issues (round 6, Euler, gfx950, by the SQ counters per wave over N = 50, prologue and commit included): the line
+// search 136 vector / 19 scalar instructions and 5.4 branches per step (6 798 / 963 / 269 per wave), simulate_quad_body's step
+// 80 / 11 / 4.1 (4 008 / 565 / 205); of the line search's ~120 in the loop body 12 are K dx, ~16 the stage cost with its short
+// cut, ~48 the rate function including its in-quad broadcasts, 4 + 1 the record.
 // PRIO: the state recurrence of a step at wave priority 1, the stage cost, the store and the loads that hang off it at 0
 // (rollout_quad.hip); without it the step runs at the caller's priority throughout and adds its stage cost ahead of the rate function.
 // RefS = RefSrc: stage and terminal cost against the step's row.  The row's four floats are requested with the step's nominal data,
@@ -446,7 +513,7 @@ __device__ __forceinline__ double quad_rollout_closed(const quattro_model_params
   // far cache (K was written by the sweep, 39 MB per 4096 trajectories) and a step is only ~0.5 us of issue.  PF = 4 in
   // the stand-alone kernels; 2 inside the device-resident solve loop, where the gains were written by the same workgroup a
   // moment ago (L2-resident) and the loop shares its 128 registers with the sweep.
-  const unsigned long long counted_mask = __builtin_amdgcn_ballot_w64(counted);
+  const unsigned long long counted_mask = barrier_lanes(p, counted);
   NomLane nb[PF];
 #pragma unroll
   for (int d = 0; d < PF; ++d) nb[d].load(src, d < N ? d : N - 1);
@@ -467,7 +534,7 @@ __device__ __forceinline__ double quad_rollout_closed(const quattro_model_params
     const float uh = fmaf(alpha, du, b.u);
     if constexpr (!PRIO) J += (double)lane_stage_cost(p, with_ref<RefS>(L, rt), xh, uh, counted_mask);
     float xnext[4];
-    const QuadU U(uh);
+    const QuadU U(uh, Store::ALL_U);
     quad_step<RK4>(L, xh, U, xnext);
     if constexpr (PRIO) {
       __builtin_amdgcn_s_setprio(0);
@@ -507,7 +574,6 @@ __device__ __forceinline__ void simulate_quad_body(const quattro_model_params& p
   const int b = gid >> 2;
   const size_t bb = live ? b : 0;
   const LaneConst L = lane_const_of<PHYS>(p, model_phys, bb, gid & 3);
-  const float* ub = u + bb * N * NU + L.j;
   float* xo = x + bb * (N + 1) * NX + L.a;
   float xh[4];
 #pragma unroll
@@ -516,7 +582,23 @@ __device__ __forceinline__ void simulate_quad_body(const quattro_model_params& p
   const int bw = __builtin_amdgcn_readfirstlane(b);         // the wave's first trajectory (gid grows with the lane)
   const __amdgpu_buffer_rsrc_t rsx =
       __builtin_amdgcn_make_buffer_rsrc(x + (size_t)bw * (N + 1) * NX, 0, 16 * (N + 1) * NX * 4, 0x00020000);
-  const int vox = writer ? 4 * ((b - bw) * (N + 1) * NX + L.a) : -1;
+  // (a lane that writes nothing: an offset the range check drops, with room for the stores' immediate offsets above it -- the
+  //  resource is 16 (N + 1) 48 bytes, far below 2^30)
+  const int vox = writer ? 4 * ((b - bw) * (N + 1) * NX + L.a) : 0x40000000;
+  // Round 6: the controls come the same way, NomSrc's: the wave's 16 trajectories as one wave-uniform resource, this lane's
+  // loop-invariant byte offset, the (clamped) step as a SCALAR offset -- a 64-bit address per lane and step was a vector shift-add
+  // and two scalar instructions of a kernel that pays for every issue slot.  An idle quad reads the wave's first trajectory's.
+  // The step is carried as a byte offset of its own (`ou`, two steps ahead, one add and one min per step), and the resource's flag
+  // word is pinned in a register of its own: sharing rsx's, the compiler copied it into place again in every step.
+  int uflags = 0x00020000;
+  asm("" : "+s"(uflags));
+  const __amdgpu_buffer_rsrc_t rsu =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(u) + (size_t)bw * N * NU, 0, 16 * N * NU * 4, uflags);
+  const int vou = 4 * ((live ? b - bw : 0) * N * NU + L.j);
+  const int ou_last = (N - 1) * (NU * 4);
+  auto control = [&](int ofs) __attribute__((always_inline)) {     // the control at byte offset ofs of the row, clamped to the last
+    return __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsu, vou, ofs < ou_last ? ofs : ou_last, 0));
+  };
   if (writer) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) xo[3 * g] = xh[g];
@@ -527,8 +609,9 @@ __device__ __forceinline__ void simulate_quad_body(const quattro_model_params& p
   r1.load(ref, N > 1 ? 1 : 0);
   rN.load(ref, N);
   double J = 0.0;
-  const unsigned long long live_mask = __builtin_amdgcn_ballot_w64(live);
-  float u0 = ub[0], u1 = ub[(size_t)(N > 1 ? 1 : 0) * NU];
+  const unsigned long long live_mask = barrier_lanes(p, live);
+  float u0 = control(0), u1 = control(NU * 4);
+  int ou = 2 * (NU * 4);
   auto step = [&](float ut, const RefLane& rt, int t) __attribute__((always_inline)) {
     J += (double)lane_stage_cost(p, with_ref<RefS>(L, rt), xh, ut, live_mask);
     float xn[4];
@@ -543,9 +626,11 @@ __device__ __forceinline__ void simulate_quad_body(const quattro_model_params& p
     // No exec-mask branch around the stores — which matters beyond the branch: with the stores behind a branch the compiler's
     // wait-count pass must assume they may NOT have been issued, and the wait for the next control (loaded BEFORE them) comes out
     // as vmcnt(1) instead of vmcnt(5) — every step then waits for the previous step's stores to be acknowledged.
+    // (round 6: the row is ONE scalar offset and the four states' 0 / 12 / 24 / 36 ride in the instruction's immediate field; as
+    //  part of the scalar offset each store had a scalar add of its own per step)
 #pragma unroll
     for (int g = 0; g < 4; ++g)
-      __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(xn[g]), rsx, vox, (t + 1) * (NX * 4) + 12 * g, 0);
+      __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(xn[g]), rsx, vox + 12 * g, (t + 1) * (NX * 4), 0);
 #pragma unroll
     for (int g = 0; g < 4; ++g) xh[g] = xn[g];
   };
@@ -563,10 +648,12 @@ __device__ __forceinline__ void simulate_quad_body(const quattro_model_params& p
   int t = 0;
   for (; t + 1 < N; t += 2) {
     step(u0, r0, t);
-    u0 = ub[(size_t)(t + 2 < N ? t + 2 : N - 1) * NU];
+    u0 = control(ou);
+    ou += NU * 4;
     r0.load(ref, t + 2 < N ? t + 2 : N - 1);
     step(u1, r1, t + 1);
-    u1 = ub[(size_t)(t + 3 < N ? t + 3 : N - 1) * NU];
+    u1 = control(ou);
+    ou += NU * 4;
     r1.load(ref, t + 3 < N ? t + 3 : N - 1);
   }
   if (t < N) step(u0, r0, t);
@@ -634,8 +721,9 @@ __device__ __forceinline__ void linesearch_quad_body(const quattro_model_params&
     float* dst = isx ? xn + NX + e : un + (e - 12);
     const int dstride = isx ? NX : NU;
     // COPY_U records per lane in flight: all of a block's loads are issued before its first store (a dword load / wait / store
-    // per record, as the plain loop compiles, is a round trip to L2 per four records: 10 % of the kernel by ablation)
-    constexpr int COPY_U = 13;
+    // per record, as the plain loop compiles, is a round trip to L2 per four records: 10 % of the kernel by ablation).  25 = the
+    // headline's N = 50 in ONE round (13 took two, behind the wait above); the rollout's registers are dead here, there is room.
+    constexpr int COPY_U = 25;
     for (int t0 = half; t0 < N; t0 += 2 * COPY_U) {
       float v[COPY_U];
 #pragma unroll
