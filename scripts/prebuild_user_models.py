@@ -15,6 +15,8 @@ for W in (5, 8):          # tests/test_user_model_gpu.py::test_user_model_at_the
     built.append(q.compile_model(f"chain{2 * W}x{W}", 2 * W, W, rate=t.CHAIN_RATE, dt=0.02, integrator="rk4", phys=(2.0, 0.3, 1.5)).lib_path)
 import dual_probe                   # tests/test_dual_algebra_gpu.py: the probe and seeded random libraries of csrc/dual.h
 built += [L.model().lib_path for L in dual_probe.all_libs()]
+import user_grid_cases              # tests/test_user_grid_gpu.py: one library per (n, m) of the grid
+built += [md.lib_path for md in user_grid_cases.all_models()]
 print("\n".join(sorted(set(built))))
 # entries of earlier source / flag states (the cache key covers both) are dead weight in every snapshot sent to a GPU box
 import shutil
