@@ -206,11 +206,12 @@ def riccati_sweep_batched(d, reg=QUU_REG, dtype=np.float64, quu_out=None):
     return k_out, K_out
 
 
-def backward_pass(f, L, Lf, x_seq, u_seq, t_start=0):
+def backward_pass(f, L, Lf, x_seq, u_seq, t_start=0, reg=QUU_REG):
     """FD linearisation + sweep for t in [t_start, N): lists of k (m,), K (m,n), index t - t_start.
-    t_start=0 is the reference's backward_pass, t_start>0 its backward_pass_segment."""
+    t_start=0 is the reference's backward_pass, t_start>0 its backward_pass_segment.  reg: what riccati_sweep puts on the
+    diagonal of Q_uu before the inversion (the reference's literal 1e-6)."""
     d = linearize_fd(f, L, Lf, x_seq, u_seq, t_start)
-    k, K = riccati_sweep(d)
+    k, K = riccati_sweep(d, reg=reg)
     return [k[s] for s in range(k.shape[0])], [K[s] for s in range(K.shape[0])]
 
 
@@ -249,10 +250,11 @@ def unpack_prediction(pred_flat, m, n):
 
 # ----------------------------------------------------------------------------- outer loop
 def optimize(f, L, Lf, x0, u_init, horizon, x_ref=None, max_iter=100, tol=1e-3,
-             tf_predict=None, tf_window=10, state_offset=None, keep_logs=True):
+             tf_predict=None, tf_window=10, state_offset=None, keep_logs=True, reg=QUU_REG):
     """One call of the reference's optimize().  Pure iLQR when tf_predict is None, otherwise the
     hybrid: gains for t < N - tf_window come from tf_predict(x_seq - x_ref + offset, prompt),
-    the last tf_window steps from the sweep.  Returns (u_seq, final_x_seq, logs)."""
+    the last tf_window steps from the sweep.  reg reaches every backward pass (default: the
+    reference's 1e-6).  Returns (u_seq, final_x_seq, logs)."""
     u_seq = list(u_init)
     logs = []
     n = len(x0)
@@ -263,12 +265,12 @@ def optimize(f, L, Lf, x0, u_init, horizon, x_ref=None, max_iter=100, tol=1e-3,
         J = trajectory_cost(L, Lf, x_seq, u_seq)
         rec = dict(iteration=it, x_seq=x_seq, current_cost=J)
         if tf_predict is None:
-            k_seq, K_seq = backward_pass(f, L, Lf, x_seq, u_seq, 0)
+            k_seq, K_seq = backward_pass(f, L, Lf, x_seq, u_seq, 0, reg=reg)
             k_full, K_full = k_seq, K_seq
             rec.update(k_seq=k_seq, K_seq=K_seq)
         else:
             t0 = horizon - tf_window
-            k_seg, K_seg = backward_pass(f, L, Lf, x_seq, u_seq, t0)
+            k_seg, K_seg = backward_pass(f, L, Lf, x_seq, u_seq, t0, reg=reg)
             prompt = pack_prompt(k_seg, K_seg)
             x_err = x_seq - x_ref + state_offset
             pred = tf_predict(x_err, prompt)

@@ -312,15 +312,17 @@ def solve_bounds(model):
     return {key: max(SOLVE_START[key], 4.0 * SOLVE_E[model][key]) for key in SOLVE_START}
 
 
-def solve_optimize(sp, x0, u0):
-    """oracle.ilqr.optimize on the spec's callables for one trajectory -> u (N, m), x (N+1, n), cost, iterations."""
-    u, x, logs = o_ilqr.optimize(sp.f, sp.L, sp.Lf, x0, list(u0), u0.shape[0], max_iter=SOLVE_MAX_ITER, tol=SOLVE_TOL)
+def solve_optimize(sp, x0, u0, reg=o_ilqr.QUU_REG):
+    """oracle.ilqr.optimize on the spec's callables for one trajectory -> u (N, m), x (N+1, n), cost, iterations.  reg: the
+    Q_uu regularisation of every backward pass (tests/reg_cases.py moves it; the default is the reference's)."""
+    u, x, logs = o_ilqr.optimize(sp.f, sp.L, sp.Lf, x0, list(u0), u0.shape[0], max_iter=SOLVE_MAX_ITER, tol=SOLVE_TOL,
+                                 reg=reg)
     return np.array(u), x, float(o_ilqr.trajectory_cost(sp.L, sp.Lf, x, u)), len(logs)
 
 
-def solve_emulated(sp, x0, u0, dtype=np.float32):
+def solve_emulated(sp, x0, u0, dtype=np.float32, reg=o_ilqr.QUU_REG):
     """The algorithm of optimize() for one trajectory with exact derivatives and `dtype` storage: x, u and every candidate are
-    rounded to dtype, the sweep runs in dtype, costs are summed in fp64 as on the device."""
+    rounded to dtype, the sweep runs in dtype (at `reg`), costs are summed in fp64 as on the device."""
     r = lambda a: np.asarray(a).astype(dtype).astype(np.float64)
     x0, u = x0[None], r(u0[None])
     xs = r(o_lin.rollout_batched(sp, x0, u)[0])
@@ -329,7 +331,7 @@ def solve_emulated(sp, x0, u0, dtype=np.float32):
     for _ in range(SOLVE_MAX_ITER):
         its += 1
         blocks = o_lin.linearize_analytic(sp, xs, u)
-        k, K = o_ilqr.riccati_sweep_batched({k_: v.astype(dtype) for k_, v in blocks.items()}, dtype=dtype)
+        k, K = o_ilqr.riccati_sweep_batched({k_: v.astype(dtype) for k_, v in blocks.items()}, reg=reg, dtype=dtype)
         k, K = k.astype(np.float64), K.astype(np.float64)
         found = False
         for a in SOLVE_ALPHAS:

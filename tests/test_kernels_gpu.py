@@ -102,6 +102,15 @@ def test_sweep_layouts_agree_and_active_mask():
     assert np.array_equal(Kb[1::3], out[layout][0][1::3])
 
 
+def _zero_quu_blocks(reg, name="sweep_cartpole_N30.npz"):
+    """Q_uu + reg I exactly zero at every step: l_uu = -reg I, B = 0, on one golden trajectory."""
+    g = load_golden(name)
+    blocks = {k: g[k][:1].copy() for k in BLOCKS + ["VxN", "VxxN"]}
+    blocks["B"][:] = 0.0
+    blocks["luu"][:] = -reg * np.eye(blocks["luu"].shape[-1])
+    return blocks
+
+
 def test_sweep_status_flags_singular_and_nonfinite():
     _lib, models, ops = _ops()
     g = load_golden("sweep_cartpole_N30.npz")
@@ -111,10 +120,7 @@ def test_sweep_status_flags_singular_and_nonfinite():
     _, _, st = ops.riccati_sweep(rec, dev32(blocks["VxN"]), dev32(blocks["VxxN"]), 4, 1, layout)
     st = st.cpu().numpy()
     assert st[0] == 0 and (st[1] & _lib.TRAJ_NONFINITE)
-    # Q_uu + reg I exactly zero: l_uu = -reg, B = 0
-    blocks = {k: g[k][:1].copy() for k in BLOCKS + ["VxN", "VxxN"]}
-    blocks["B"][:] = 0.0
-    blocks["luu"][:] = -1e-6
+    blocks = _zero_quu_blocks(1e-6)
     rec, layout = ops.pack_derivs(*[dev32(blocks[k]) for k in BLOCKS])
     _, _, st = ops.riccati_sweep(rec, dev32(blocks["VxN"]), dev32(blocks["VxxN"]), 4, 1, layout,
                                  reg=float(np.float32(1e-6)))
@@ -461,14 +467,9 @@ def test_line_search_rejects_non_finite_and_exploding_candidates(model):
     assert not bool(torch.isfinite(cand[:, 1]).any()) and not bool(torch.isfinite(cand[:, 3]).any())
 
 
-def test_indefinite_and_ill_conditioned_quu_through_pack_derivs():
-    """Foreign records (quattro_pack_derivs_f32) with a Q_uu + reg I the unpivoted TILE16 elimination must not be trusted
-    on: (1) indefinite but well conditioned (eigenvalues of both signs) at three steps — the reference's np.linalg.inv
-    (LAPACK, partial pivoting; quattro_ilqr_tf.py:306) handles it, so must we: the TILE16 kernel raises TRAJ_ILLCOND, the
-    ROWMAJOR kernel (which pivots) matches the fp64 oracle, and ops.riccati_sweep(repair=True) reroutes exactly the
-    flagged trajectories; (2) positive definite with condition number ~1e8 — beyond fp32 whatever the pivoting: flagged,
-    values not compared; (0) the untouched golden trajectory stays unflagged and bit-identical."""
-    _lib, models, ops = _ops()
+def _indefinite_and_ill_conditioned_blocks():
+    """Three golden quadrotor trajectories: 0 untouched, 1 with an indefinite, well conditioned l_uu at three steps, 2 with
+    l_uu + 2.5e6 at two steps (condition number ~1e8).  -> the blocks, and the same rounded to fp32 and widened to fp64."""
     g = load_golden("sweep_quadrotor_N50.npz")
     blocks = {k: g[k][:3].copy() for k in BLOCKS + ["VxN", "VxxN"]}
     rng = np.random.default_rng(3)
@@ -479,6 +480,18 @@ def test_indefinite_and_ill_conditioned_quu_through_pack_derivs():
     for s in (49, 30):
         blocks["luu"][2, s] = blocks["luu"][2, s] + 2.5e6 * np.ones((4, 4))
     d64 = {k: blocks[k].astype(np.float32).astype(np.float64) for k in blocks}
+    return blocks, d64
+
+
+def test_indefinite_and_ill_conditioned_quu_through_pack_derivs():
+    """Foreign records (quattro_pack_derivs_f32) with a Q_uu + reg I the unpivoted TILE16 elimination must not be trusted
+    on: (1) indefinite but well conditioned (eigenvalues of both signs) at three steps — the reference's np.linalg.inv
+    (LAPACK, partial pivoting; quattro_ilqr_tf.py:306) handles it, so must we: the TILE16 kernel raises TRAJ_ILLCOND, the
+    ROWMAJOR kernel (which pivots) matches the fp64 oracle, and ops.riccati_sweep(repair=True) reroutes exactly the
+    flagged trajectories; (2) positive definite with condition number ~1e8 — beyond fp32 whatever the pivoting: flagged,
+    values not compared; (0) the untouched golden trajectory stays unflagged and bit-identical."""
+    _lib, models, ops = _ops()
+    blocks, d64 = _indefinite_and_ill_conditioned_blocks()
     ko, Ko = o_ilqr.riccati_sweep_batched(d64)
     Quu = d64["luu"][1, 49] + d64["B"][1, 49].T @ d64["VxxN"][1] @ d64["B"][1, 49]
     ev = np.linalg.eigvalsh(0.5 * (Quu + Quu.T))
@@ -785,16 +798,22 @@ def test_tile_sweep_on_rowmajor_records_of_any_dims_against_the_fp64_oracle(n, m
         assert per_step_rel(K[live].cpu().numpy().reshape(-1, S, m * n).transpose(1, 0, 2), Kg[live].cpu().numpy().reshape(-1, S, m * n).transpose(1, 0, 2)) < 5e-6
 
 
+def _indefinite_rowmajor_problem(B=6, S=5, n=12, m=4):
+    """A random convex problem whose trajectory 2 has an indefinite l_uu (and a small B) at its last step."""
+    rng = np.random.default_rng(9)
+    d = _random_lq_problem(rng, B, S, n, m)
+    d["luu"][2, S - 1] = np.diag([1.0, -0.8, 1.0, 0.5])          # indefinite at the last step of trajectory 2
+    d["B"][2, S - 1] *= 0.01
+    return d
+
+
 def test_tile_sweep_on_rowmajor_records_flags_what_needs_pivoting():
     """An indefinite Q_uu + reg I: flagged ILLCOND by the tile sweep; ops.riccati_sweep(repair=True) sends exactly the flagged
     trajectories through the pivoting kernel ON THE SAME RECORDS (no repacking) and matches the fp64 oracle there."""
     _lib, models, ops = _ops()
     n, m = 12, 4
-    rng = np.random.default_rng(9)
     B, S = 6, 5
-    d = _random_lq_problem(rng, B, S, n, m)
-    d["luu"][2, S - 1] = np.diag([1.0, -0.8, 1.0, 0.5])          # indefinite at the last step of trajectory 2
-    d["B"][2, S - 1] *= 0.01
+    d = _indefinite_rowmajor_problem(B, S, n, m)
     k_o, K_o = o_ilqr.riccati_sweep_batched(d)
     rec = dev32(_rowmajor_records(d, n, m))
     K, k, status = ops.riccati_sweep(rec, dev32(d["VxN"]), dev32(d["VxxN"]), n, m, _lib.LAYOUT_ROWMAJOR_TILE)
