@@ -528,6 +528,36 @@ int quattro_score_f32(const quattro_model_params* p, const float* x, const float
                       const float* x_ref_rows, int ref_rows, int ref_hold, const float* cost_rows, int flags, float* stage,
                       double* total, void* stream);
 
+/* COST GRADIENT: dJ/du and dJ/dx0 of the trajectory cost J(x0, u) = sum_t L(x_t, u_t) + Lf(x_N) with x_{t+1} = f(x_t, u_t), by the
+ * adjoint sweep.  Differentiates iLQR_TF.simulate (quattro_ilqr_tf.py:127-132) composed with compute_total_cost (:138-143); the
+ * reference has no counterpart (it never forms the gradient of the cost it minimises: a first-order optimality measure for a solve,
+ * a gradient method over the controls, or a loss through the device model all start here).
+ *   x [B][N+1][n], u [B][N][m] : x is meant to be the rollout of u (quattro_simulate_f32); as for quattro_linearize_f32 this is
+ *                       not checked, and for other sequences the outputs are the recursion below about the given points
+ *   lambda_N = Lf_x(x_N);  for t = N-1 .. 0:  g_t = L_u(x_t, u_t) + B_t^T lambda_{t+1},  lambda_t = L_x(x_t, u_t) + A_t^T lambda_{t+1}
+ *                       with [A_t | B_t] the derivative of the whole integrator step (Euler or RK4, p->integrator) at (x_t, u_t)
+ *   grad_u [B][N][m]  = g          grad_x0 [B][n] = lambda_0 (may be NULL)          costate [B][N+1][n] = lambda (may be NULL)
+ *                       all fp32, the recursion runs in fp32; grad_x0[b] and costate[b][0] are the same value, bit for bit
+ *   model_phys [B][8], x_ref_rows [B][ref_rows][n], cost_rows [B][QUATTRO_COST_ROW_FLOATS] : the arrays of the *_phys / *_ref / *_cost
+ *                       entries, the same layouts, 16-byte aligned; each may be NULL on its own (p's values then).  model_phys
+ *                       reaches the dynamics as well as a user model's cost.  Horizon step t takes its cost against row
+ *                       min(t, ref_rows - 1) of trajectory b's reference rows and the terminal term against the row of t = N: the
+ *                       solves' row rule for a plan that starts at step 0.  Every model takes every kind of row, the built-in
+ *                       quadrotor's cost rows included (as for scoring, the model's step and cost are all that is needed)
+ * A group of 8, 16 or 32 adjacent lanes (by n + m; 16 for both built-in models) owns one trajectory and lane j direction j of
+ * z = (x, u): column j of [A_t | B_t] and entry j of l_z are formed off the serial chain for QUATTRO_GRAD_BLOCK steps at a time and
+ * staged in LDS; the chain is one n-term dot product per lane and step plus the exchange of lambda inside the group
+ * (csrc/cost_gradient.hip).  The barrier part of L_u is evaluated with a softplus accurate relative to itself, so it is not the l_u of
+ * quattro_linearize_f32's records bit for bit (they differ by up to about 1e-6 relative where the barrier is inactive).
+ * Nothing is allocated and no workspace is taken.  The results of trajectory b are those of a call with
+ * B = 1 and p's fields set to row b, bit for bit.  Before any launch: the model check of quattro_total_cost_f32 first; then
+ * QUATTRO_ERR_BAD_ARG for a NULL x, u or grad_u, B <= 0, N <= 0, reference rows with ref_rows < 1 (not looked at without rows), or a
+ * row array that is not 16-byte aligned. */
+#define QUATTRO_GRAD_BLOCK 3
+int quattro_cost_gradient_f32(const quattro_model_params* p, const float* x, const float* u, int B, int N,
+                              const float* model_phys, const float* x_ref_rows, int ref_rows, const float* cost_rows,
+                              float* grad_u, float* grad_x0, float* costate, void* stream);
+
 /* Transformer gain predictor: weights of the reference's TransformerPredictor (quattro_ilqr_tf/transformer_model.py:85-138)
  * as DEVICE pointers, plus the DataNormalizer vectors (:15-50).  Matrices are PyTorch Linear layout [out][in];
  * the `w_*` matrices are 16-bit (raw uint16 bit patterns: bf16, or IEEE half when `precision` says so), everything else

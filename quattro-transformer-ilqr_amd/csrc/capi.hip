@@ -23,6 +23,8 @@ int quattro_launch_simulate(const quattro_model_params&, const float*, const flo
 int quattro_launch_total_cost(const quattro_model_params&, const float*, const float*, int, int, double*, hipStream_t);
 int quattro_launch_score(const quattro_model_params&, const float*, const float*, int, int, const float*, const float*, int, int,
                          const float*, int, float*, double*, hipStream_t);
+int quattro_launch_cost_gradient(const quattro_model_params&, const float*, const float*, int, int, const float*, const float*, int,
+                                 const float*, float*, float*, float*, hipStream_t);
 int quattro_launch_rollout(const quattro_model_params&, const float*, const float*, const float*, const float*,
                            const float*, int, int, int, float*, float*, double*, const int32_t*, hipStream_t);
 int quattro_launch_linesearch(const quattro_model_params&, float*, float*, const float*, const float*, const float*,
@@ -237,6 +239,17 @@ int quattro_score_f32(const quattro_model_params* p, const float* x, const float
   if ((((uintptr_t)model_phys | (uintptr_t)x_ref_rows | (uintptr_t)cost_rows) & 15) != 0) return QUATTRO_ERR_BAD_ARG;
   return quattro_launch_score(*p, x, u, B, S, model_phys, x_ref_rows, ref_rows, ref_hold, cost_rows,
                               (flags & QUATTRO_SCORE_TERMINAL) != 0 ? 1 : 0, stage, total, (hipStream_t)stream);
+}
+
+int quattro_cost_gradient_f32(const quattro_model_params* p, const float* x, const float* u, int B, int N,
+                              const float* model_phys, const float* x_ref_rows, int ref_rows, const float* cost_rows,
+                              float* grad_u, float* grad_x0, float* costate, void* stream) {
+  if (!model_ok(p)) return p ? QUATTRO_ERR_UNSUPPORTED : QUATTRO_ERR_BAD_ARG;
+  if (!x || !u || !grad_u || B <= 0 || N <= 0) return QUATTRO_ERR_BAD_ARG;
+  if (x_ref_rows != nullptr && ref_rows < 1) return QUATTRO_ERR_BAD_ARG;
+  if ((((uintptr_t)model_phys | (uintptr_t)x_ref_rows | (uintptr_t)cost_rows) & 15) != 0) return QUATTRO_ERR_BAD_ARG;
+  return quattro_launch_cost_gradient(*p, x, u, B, N, model_phys, x_ref_rows, ref_rows, cost_rows, grad_u, grad_x0, costate,
+                                      (hipStream_t)stream);
 }
 
 int quattro_rollout_f32(const quattro_model_params* p, const float* x_nom, const float* u_nom, const float* K,

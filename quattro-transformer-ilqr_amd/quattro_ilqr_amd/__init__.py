@@ -10,3 +10,5 @@ from .solver import QuattroILQR, iLQR_TF  # noqa: F401,E402
 from .mpc import BatchedMPC, CartPoleMPC, ControllerSwitcher, QuadrotorMPC  # noqa: F401,E402
 from .transformer import TransformerILQR  # noqa: F401,E402
 from . import datagen, training  # noqa: F401,E402
+from . import autograd  # noqa: F401,E402
+from .autograd import trajectory_cost  # noqa: F401,E402

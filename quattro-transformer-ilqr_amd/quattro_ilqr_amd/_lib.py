@@ -17,6 +17,7 @@ INTEGRATOR_EULER, INTEGRATOR_RK4 = 0, 1
 LAYOUT_ROWMAJOR, LAYOUT_TILE16, LAYOUT_TILE16C, LAYOUT_TILE16R, LAYOUT_ROWMAJOR_TILE = 0, 1, 2, 3, 4
 SOLVE_SIMULATE, SOLVE_FIXED_ITERS, SOLVE_RESET, SOLVE_ENQUEUE, SOLVE_PERSISTENT = 1, 2, 4, 8, 16
 SCORE_TERMINAL = 1
+GRAD_BLOCK = 3                                    # QUATTRO_GRAD_BLOCK: steps the gradient kernel stages in LDS per pass
 LOG_TRAJ, LOG_GAINS = 1, 2
 LOG_FIELD_X, LOG_FIELD_U, LOG_FIELD_K, LOG_FIELD_KFF = 0, 1, 2, 3
 LOG_PHASE_BEGIN, LOG_PHASE_BACKWARD_DONE, LOG_PHASE_GAINS_DONE, LOG_PHASE_END = 0, 1, 2, 3
@@ -101,6 +102,7 @@ SIGNATURES = {
     "quattro_simulate_f32": (c_int, [POINTER(ModelParams), _P, _P, c_int, c_int, _P, _P, _P]),
     "quattro_total_cost_f32": (c_int, [POINTER(ModelParams), _P, _P, c_int, c_int, _P, _P]),
     "quattro_score_f32": (c_int, [POINTER(ModelParams), _P, _P, c_int, c_int, _P, _P, c_int, c_int, _P, c_int, _P, _P, _P]),
+    "quattro_cost_gradient_f32": (c_int, [POINTER(ModelParams), _P, _P, c_int, c_int, _P, _P, c_int, _P, _P, _P, _P, _P]),
     "quattro_rollout_f32": (c_int, [POINTER(ModelParams), _P, _P, _P, _P, POINTER(c_float), c_int, c_int, c_int, _P,
                                     _P, _P, _P, _P]),
     "quattro_linesearch_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),

@@ -710,6 +710,46 @@ def score(model, x, u, targets=None, weights=None, model_phys=None, terminal=Fal
     return total, stage
 
 
+def cost_gradient(model, x, u, targets=None, weights=None, model_phys=None, want_x0=True, want_costate=False):
+    """Gradient of the trajectory cost J(x0, u) = sum_t L(x_t, u_t) + Lf(x_N), x_{t+1} = f(x_t, u_t), by the adjoint sweep on the
+    device (quattro_cost_gradient_f32) about x (B, N+1, n), u (B, N, m): -> dict with "grad_u" (B, N, m) = dJ/du, and "grad_x0"
+    (B, n) = dJ/dx0 with want_x0, "costate" (B, N+1, n) with want_costate (costate[:, 0] is grad_x0), all float32.  x is meant to
+    be the rollout of u (ops.simulate, or ops.track(..., feedback=False, plant_phys=model_phys) under model_phys); as for
+    ops.linearize this is not checked.  Each trajectory under rows of its own, in the forms the solves and ops.score take, every
+    model (the built-in quadrotor's weights too):
+      targets     as x_ref_rows_tensor takes them: horizon step t against row min(t, R - 1) of trajectory b, t = N the terminal term
+      weights     as cost_rows_tensor takes them: q, qf, r of row b
+      model_phys  as model_phys_tensor takes them: phys of row b, in the dynamics and in a user model's cost
+    None: the model's own x_ref / q, qf, r / phys.  Nothing is differentiated with respect to rows or model parameters.  ValueError
+    for a wrong shape, before anything touches the device."""
+    if len(np.shape(x)) != 3 or len(np.shape(u)) != 3:
+        raise ValueError(f"x must have shape (B, N + 1, n) and u (B, N, m) (got {tuple(np.shape(x))} and {tuple(np.shape(u))})")
+    Bt, N, m = (int(v) for v in u.shape)
+    if Bt < 1 or N < 1 or m != model.m or tuple(x.shape) != (Bt, N + 1, model.n):
+        raise ValueError(f"x must have shape (B, N + 1, {model.n}) and u (B, N, {model.m}) with B, N >= 1 "
+                         f"(got {tuple(x.shape)} and {tuple(u.shape)})")
+    check_phys_rows(model, model_phys, Bt, "model_phys")
+    check_ref_rows(model, targets, Bt, name="targets")
+    check_cost_rows(model, weights, Bt, name="weights")
+    f32 = torch.float32
+    _req(x, (Bt, N + 1, model.n), f32, "x"); _req(u, (Bt, N, model.m), f32, "u")
+    model_phys = model_phys_tensor(model, model_phys, Bt, u.device)
+    rows = x_ref_rows_tensor(model, targets, Bt, u.device, name="targets")
+    cost_rows = cost_rows_tensor(model, weights, Bt, u.device, name="weights")
+    out = {"grad_u": torch.empty((Bt, N, model.m), dtype=f32, device=u.device)}
+    if want_x0:
+        out["grad_x0"] = torch.empty((Bt, model.n), dtype=f32, device=u.device)
+    if want_costate:
+        out["costate"] = torch.empty((Bt, N + 1, model.n), dtype=f32, device=u.device)
+    p = model.c_params()
+    check(_lib.load_for(model).quattro_cost_gradient_f32(ctypes.byref(p), _ptr(x), _ptr(u), Bt, N, _ptr(model_phys), _ptr(rows),
+                                                         0 if rows is None else rows.shape[1], _ptr(cost_rows),
+                                                         _ptr(out["grad_u"]), _ptr(out.get("grad_x0")), _ptr(out.get("costate")),
+                                                         _stream()),
+          "quattro_cost_gradient_f32")
+    return out
+
+
 def track(model, x0, x_nom, u_nom, K, steps, plant=None, plant_phys=None, feedback=True, disturbance=None):
     """`steps` <= N plant steps from x0 (B,n) along the first rows of a nominal with its gains (quattro_track_f32):
     u = u_nom[j] + (feedback ? K[j] (x - x_nom[j]) : 0), x <- f_plant(x, u) + disturbance[j].  plant: a DeviceModel like `model`

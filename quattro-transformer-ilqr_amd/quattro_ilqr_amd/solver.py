@@ -388,7 +388,7 @@ class QuattroILQR:
         ops.check_cost_rows(self.model, weights, B)
 
     def solve(self, x0, u_init=None, x_ref=None, max_iter=None, fixed_iters=False, log=None, want_alpha=True,
-              upload_guard=True, model_phys=None, targets=None, weights=None):
+              upload_guard=True, model_phys=None, targets=None, weights=None, want_grad=False):
         """x0 (B,n), u_init (B,N,m) (zeros if None).  Returns a dict of device tensors:
         K (B,N,m,n), k (B,N,m), x (B,N+1,n), u (B,N,m), cost (B,) fp64, iters (B,), alpha (B,) last accepted step
         (-1: none), status (B,).  fixed_iters=True runs exactly max_iter iterations (benchmarking: stop flags off).
@@ -416,7 +416,12 @@ class QuattroILQR:
         given, and a row that makes Q_uu singular shows in that trajectory's status alone.  The same kernel rule, refusals and
         order as model_phys, with which and with targets it combines.  The cart-pole and user-compiled models take weights; the
         built-in quadrotor's persistent kernel has no such form yet and refuses like a model without a kernel
-        (NotImplementedError).  Out of scope: per-step weights, ShardedILQR."""
+        (NotImplementedError).  Out of scope: per-step weights, ShardedILQR.
+        want_grad=True: one ops.cost_gradient launch after the solve, on the returned x, u under this call's model_phys, targets
+        and weights, adds "grad_u" (B,N,m) = dJ/du and "grad_norm" (B,) = max |grad_u| per trajectory (computed on the device): a
+        first-order optimality measure, which tells a stationary point from a stalled line search (alpha = -1 says only that no
+        step was found).  Works in every mode, since it only reads x, u.  Without the keyword nothing new is launched and the
+        dict is what it always was; the stop test does not use the gradient."""
         n, m, N, dev = self.model.n, self.model.m, self.horizon, self.device
         if not isinstance(x0, torch.Tensor):
             x0 = np.asarray(x0)
@@ -433,6 +438,7 @@ class QuattroILQR:
         self._log = log
         max_iter = self.max_iter if max_iter is None else int(max_iter)
         x_ref_t = None
+        rows = dict(model_phys=None, targets=None, weights=None)
         if self.tf is not None:
             xr = np.asarray(self.model.x_ref if x_ref is None else x_ref, dtype=np.float64).reshape(-1)
             off = np.asarray(self.state_offset, dtype=np.float64).reshape(-1)
@@ -459,6 +465,7 @@ class QuattroILQR:
             self._weights = ops.cost_rows_tensor(self.model, weights, B, dev)
             self._solve_call(self.tol, max_iter, fixed_iters=fixed_iters, log=log, persistent=self.device_loop == "always",
                              model_phys=self._model_phys, x_ref_rows=self._targets, cost_rows=self._weights)
+            rows = dict(model_phys=self._model_phys, targets=self._targets, weights=self._weights)
             max_iter = 0
         else:
             self._ints.copy_(self._ints_init)          # active = 1, iters = 0, alpha_idx = -1, status = 0
@@ -476,6 +483,9 @@ class QuattroILQR:
             alphas_t = self._alphas_t
             out["alpha"] = torch.where(self.alpha_idx >= 0, alphas_t[self.alpha_idx.clamp(min=0).long()],
                                        torch.full_like(alphas_t[:1], -1.0).expand(B))
+        if want_grad:
+            out["grad_u"] = ops.cost_gradient(self.model, self.x, self.u, want_x0=False, **rows)["grad_u"]
+            out["grad_norm"] = out["grad_u"].abs().amax(dim=(1, 2))
         return out
 
 

@@ -57,7 +57,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # (the quadrotor / cart-pole specialisations, the transformer) is resolved from libquattro_hip.so
 # (no implicit fma contraction anywhere in a user library: its device-resident loop, solve_user.hip, inlines the same device
 #  functions as the stand-alone kernels and must round like them to reproduce the host-driven loop bit for bit)
-_UNITS = {u: ["-ffp-contract=off"] for u in ("capi", "linearize", "rollout", "sweep_generic", "solve_user")}
+_UNITS = {u: ["-ffp-contract=off"] for u in ("capi", "linearize", "rollout", "cost_gradient", "sweep_generic", "solve_user")}
 _UNITS["solve_user"] = _UNITS["solve_user"] + ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]      # (the tile sweep's accumulators: Makefile)
 _FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wall", "-Wno-unused-function", "-fno-slp-vectorize"]   # (csrc/Makefile)
 
