@@ -35,7 +35,12 @@
 
 namespace {
 
-template <int MODE>
+// ROTATE (MODE_FUSED): a favourite among the waves of a SIMD, by wave slot and refill batch (sweep_tile16_body.h, above the priority
+// notes).  A launch that leaves every wave a SIMD of its own has nothing to arbitrate and takes the plain instantiation, whose code
+// is what it was (a lone wave measured 0.5 us slower through the two-bodied one).
+constexpr int ROTATE_ABOVE_B = 256 * 4;   // trajectories = waves; SIMDs of an MI355X
+
+template <int MODE, bool ROTATE = false>
 __global__ __launch_bounds__(QT_WAVE * WPB, 4) void sweep_tile16_kernel(const float* __restrict__ rec,
                                                                const float* __restrict__ VxN,
                                                                const float* __restrict__ VxxN, int S, float reg,
@@ -53,8 +58,8 @@ __global__ __launch_bounds__(QT_WAVE * WPB, 4) void sweep_tile16_kernel(const fl
   // MODE_FUSED: [header record (TILE16) | FUSED_BATCH compact records (TILE16F)]
   constexpr int LIN_FLOATS = sweep_lin_floats<MODE>();
   __shared__ __attribute__((aligned(16))) float s_lin_all[WPB * LIN_FLOATS];
-  sweep_tile16_body<MODE>(rec, VxN, VxxN, S, reg, Kout, kout, status, fa, b, lane, s_t_all + wv * 16 * LD, s_vx_all + wv * 64,
-                          s_lin_all + wv * LIN_FLOATS);
+  sweep_tile16_body<MODE, false, false, ROTATE>(rec, VxN, VxxN, S, reg, Kout, kout, status, fa, b, lane, s_t_all + wv * 16 * LD, s_vx_all + wv * 64,
+                                                s_lin_all + wv * LIN_FLOATS);
 }
 
 }  // namespace
@@ -88,8 +93,12 @@ int quattro_launch_sweep_fused(const quattro_model_params& p, const float* x, co
                                float reg, float* K, float* k, int k_rows, int32_t* status, const int32_t* active,
                                hipStream_t stream) {
   const FusedArgs fa = fused_args(p, x, u, B, N, t_start, nullptr, k_rows);
-  hipLaunchKernelGGL(sweep_tile16_kernel<MODE_FUSED>, dim3((B + WPB - 1) / WPB), dim3(QT_WAVE * WPB), 0, stream, nullptr, nullptr, nullptr,
-                     N - t_start, reg, K, k, status, active, fa);
+  if (B > ROTATE_ABOVE_B)
+    hipLaunchKernelGGL((sweep_tile16_kernel<MODE_FUSED, true>), dim3((B + WPB - 1) / WPB), dim3(QT_WAVE * WPB), 0, stream, nullptr, nullptr,
+                       nullptr, N - t_start, reg, K, k, status, active, fa);
+  else
+    hipLaunchKernelGGL(sweep_tile16_kernel<MODE_FUSED>, dim3((B + WPB - 1) / WPB), dim3(QT_WAVE * WPB), 0, stream, nullptr, nullptr, nullptr,
+                       N - t_start, reg, K, k, status, active, fa);
   return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;
 }
 

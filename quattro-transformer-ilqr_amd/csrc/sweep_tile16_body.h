@@ -103,6 +103,25 @@ __device__ __forceinline__ void gj_step(float& R, const float S, int r, int c4, 
 // B = 4096, persistent loop 97.4 -> 90.8 us per iteration (A/B on one box; a lone wave pays ~1 us per iteration for the three
 // s_setprio per step).  Other placements measured: pivots only 60.7, pivots .. row sum 60.6, pivots .. end of step 60.5, the MFMA
 // block raised instead 64.0, three levels (pivots 3, transposition 2, rest 1) 60.1 us.
+//
+// A favourite among the four waves of a SIMD (ROTATE; the stand-alone fused kernel).  At equal priority the SIMD issues by age, and
+// the launch at B = 4096 is exactly one residency round — every SIMD takes its four waves within 0.5 us and keeps them to the end —
+// so the oldest wave of a SIMD (wave slot 0) wins every tie of the whole sweep and the youngest (slot 3) loses every one.  Measured
+// with a stamp build (s_memrealtime and HW_ID at the end of every wave): the four finish at 0.84 / 0.88 / 0.93 / 0.97 of the
+// kernel's time, in slot order on all 1 024 SIMDs.  The three levels of a step are immediates of s_setprio, so the step exists
+// twice — StepPrio<2, 1, 0> and the favourite's StepPrio<3, 3, 2> — and ONE wave-uniform branch per refill batch (an epoch is the
+// FUSED_BATCH steps between two refills, where the loop is entered anyway; the refill itself runs at the level the MFMA block left)
+// picks one: in batch e, counted from the end of the horizon, the wave in slot (3 - e) & 3 is the favourite — the youngest first, then
+// the next youngest.  The spread of the finish times falls from 13 % to 5 % of the kernel and the sweep from 55.1 to 53.9 us (A/B on
+// one box, five blocks); the favourites' gain is mostly the other waves' loss (mean wave lifetime 48.1 -> 50.6 us), which is why the
+// whole spread does not come back.  Measured and not kept: the oldest slot first (slower than no favourite), favourite
+// levels 3/2/1, 3/2/2, 3/3/1, 3/3/3 and 3/2/0, one slot or two slots raised for the whole sweep, a second tier, and epochs shorter
+// than a batch — inside the unrolled-by-3 loop a branch per epoch (1, 2, 5, 10 steps, or per 3 / 6 / 12 / 24) costs 0.5 - 2.6 us
+// before any priority moves.  Launches that leave a wave a SIMD of its own take the instantiation without it (sweep_tile16.hip).
+template <int PIVOTS, int CHAIN, int MFMA>
+struct StepPrio {
+  static constexpr int pivots = PIVOTS, chain = CHAIN, mfma = MFMA;
+};
 
 constexpr int LD = 20;  // LDS row pitch (floats) of the 16x16 transpose tile: 16-B aligned rows, conflict-free b128 writes
 
@@ -330,13 +349,15 @@ __device__ __forceinline__ Rk4Entry rk4_m_entry(const float* ph, int row_tile, i
 // row of rr that step reads (qt_ref_row) instead of fa.p.x_ref.  The trajectory's block of rows has a wave-uniform base
 // (readfirstlane(b), like the PHYS row); which row a lane reads depends on the step it linearises, so the rows themselves are vector
 // loads: twelve floats per step, fetched where the step's (x_t, u_t) are.  l_xx, V_xx(N) and everything else stay the problem's.
-template <int MODE, bool PHYS = false, bool REF = false>
+// ROTATE (MODE_FUSED): a favourite among a SIMD's waves, by wave slot and refill batch (above the priority notes).
+template <int MODE, bool PHYS = false, bool REF = false, bool ROTATE = false>
 __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec, const float* __restrict__ VxN,
                                                   const float* __restrict__ VxxN, int S, float reg,
                                                   float* __restrict__ Kout, float* __restrict__ kout,
                                                   int32_t* __restrict__ status, const FusedArgs& fa, const int b,
                                                   const int lane, float* s_t, float* s_vx, float* s_lin,
                                                   const float* model_phys = nullptr, const RefRows& rr = RefRows{}) {
+  static_assert(!ROTATE || MODE == MODE_FUSED, "the favourite changes at the refills of the fused Euler mode");
   static_assert(!(PHYS || REF) || MODE == MODE_FUSED || MODE == MODE_FUSED_RK4, "per-trajectory parameters: the fused modes only");
   const float* rows_b = nullptr;              // REF: the rows of this trajectory
   if constexpr (REF) rows_b = rr.rows + (size_t)__builtin_amdgcn_readfirstlane(b) * rr.R * 12;
@@ -531,11 +552,16 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
   }
   unsigned a_tw = lds_addr(s_t + c * LD + 4 * r);   // where this lane writes its quad of the transposed tile
   asm volatile("" : "+v"(a_tw));
+  // ROTATE: the wave slot this wave sits in on its SIMD (HW_ID bits 1:0: distinct among the four a SIMD holds) and the refill batches behind it
+  int slot = 0, batches = 0;
+  if constexpr (ROTATE) slot = __builtin_amdgcn_s_getreg(4 | (1 << 11));
   bool bad = false, illc = false;
   unsigned pivz = ~0u;      // smallest pivot bit pattern seen, without its sign (wave-uniform): 0 marks a singular Q_uu + reg I
 
   // one step of the recursion on the record held in `cur`
-  auto step = [&](const StepRegs& cur, int s) __attribute__((always_inline)) {
+  // (`prio`: a StepPrio, the three levels as immediates)
+  auto step = [&](auto prio, const StepRegs& cur, int s) __attribute__((always_inline)) {
+    using Prio = decltype(prio);
     // P = V_xx F   (tile rows 4r+s <-> x_{3r+s}; the control slot s = 3 contributes nothing)
     f32x4 P = {0.0f, 0.0f, 0.0f, 0.0f};
     P = __builtin_amdgcn_mfma_f32_16x16x4f32(vA0, cur.f0, P, 0, 0, 0);
@@ -570,7 +596,7 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
     // and after the last pivot lane (r, 3) holds (Q_uu + reg I)^-1 Q_u.  Same operations on Q_u as the separate register got
     // (bit-identical k), sixteen vector instructions fewer per step — the elimination is 23 % of the kernel.
     R = (c == 3) ? qu : R;
-    __builtin_amdgcn_s_setprio(2);          // the pivots
+    __builtin_amdgcn_s_setprio(Prio::pivots);   // the pivots
     gj_step<0, CHECK_PIVOTS>(R, R0, r, c4, pivz, R0, illc);
     gj_step<1, CHECK_PIVOTS>(R, R, r, c4, pivz, R0, illc);
     gj_step<2, CHECK_PIVOTS>(R, R, r, c4, pivz, R0, illc);
@@ -578,7 +604,7 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
     // In the control columns of the tile the three values below are meaningless (they hold -I, Q_uu - reg I): they
     // are left as they are.  Every product that follows only ever combines state-column lanes with state-row
     // registers into the state-state entries that survive, so nothing is spent on zeroing the rest.
-    __builtin_amdgcn_s_setprio(1);          // the rest of the step's chain
+    __builtin_amdgcn_s_setprio(Prio::chain);    // the rest of the step's chain
     const float Kv = -R;                                  // K[r][j]; in tile column 3: k[r]
     const float kr = bcast_col<3>(Kv);                    // k[r] in every lane of group r
     const float E = fmaf(-reg, Kv, q3);                   // (Q_ux - reg K)[r][j]
@@ -610,7 +636,7 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
     vA0 = ucol ? vxq[0] : 0.5f * (Vn[0] + t0);
     vA1 = ucol ? vxq[1] : 0.5f * (Vn[1] + t1);
     vA2 = ucol ? vxq[2] : 0.5f * (Vn[2] + t2);
-    __builtin_amdgcn_s_setprio(0);          // the next step's P / Q MFMA block (and the loads around it)
+    __builtin_amdgcn_s_setprio(Prio::mfma);     // the next step's P / Q MFMA block (and the loads around it)
   };
 
   // record of local step `ls` (global step base + ls)
@@ -704,22 +730,22 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
   };
   // Steps base + cnt - 1 ... base.  Three record buffers rotate through an unrolled-by-3 loop, so a record is requested
   // three steps before it is consumed and no register copies (which would force the loads to land early) are needed.
-  auto run = [&](int cnt, int base) __attribute__((always_inline)) {
+  auto run = [&](auto prio, int cnt, int base) __attribute__((always_inline)) {
     StepRegs b0, b1, b2;
     b0 = load(cnt - 1);
     b1 = load(cnt > 1 ? cnt - 2 : 0);
     b2 = load(cnt > 2 ? cnt - 3 : 0);
     int s = cnt - 1;
     for (; s >= 2; s -= 3) {
-      step(b0, base + s);
+      step(prio, b0, base + s);
       b0 = load(s >= 3 ? s - 3 : 0);
-      step(b1, base + s - 1);
+      step(prio, b1, base + s - 1);
       b1 = load(s >= 4 ? s - 4 : 0);
-      step(b2, base + s - 2);
+      step(prio, b2, base + s - 2);
       b2 = load(s >= 5 ? s - 5 : 0);
     }
-    if (s >= 0) step(b0, base + s);
-    if (s >= 1) step(b1, base + s - 1);
+    if (s >= 0) step(prio, b0, base + s);
+    if (s >= 1) step(prio, b1, base + s - 1);
   };
   if constexpr (RK4F) {
     float* coef = fa.coef + (size_t)b * S * Rk4Coef::STRIDE;
@@ -757,7 +783,7 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
         *reinterpret_cast<float4*>(dst) = v;
       }
       wave_sync();
-      run(cnt, base);
+      run(StepPrio<2, 1, 0>{}, cnt, base);
     }
   } else if constexpr (FUSED) {
     float* stage = s_lin + Tile16Rec::STRIDE;
@@ -829,10 +855,18 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
       }
       if (base > 0) fetch(base - FUSED_BATCH);
       wave_sync();
-      run(cnt, base);
+      if constexpr (ROTATE) {
+        // the same steps under either set of levels: one scalar branch per batch
+        const bool favourite = ((batches + slot) & 3) == 3;
+        ++batches;
+        if (favourite) run(StepPrio<3, 3, 2>{}, cnt, base);
+        else run(StepPrio<2, 1, 0>{}, cnt, base);
+      } else {
+        run(StepPrio<2, 1, 0>{}, cnt, base);
+      }
     }
   } else {
-    run(S, 0);
+    run(StepPrio<2, 1, 0>{}, S, 0);
   }
   const bool singular = pivz == 0u;
   if (status != nullptr) {
