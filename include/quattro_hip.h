@@ -558,6 +558,45 @@ int quattro_cost_gradient_f32(const quattro_model_params* p, const float* x, con
                               const float* model_phys, const float* x_ref_rows, int ref_rows, const float* cost_rows,
                               float* grad_u, float* grad_x0, float* costate, void* stream);
 
+/* COST GRADIENT WITH RESPECT TO THE ROWS: dJ/d(model_phys), dJ/d(cost_rows) and dJ/d(x_ref_rows) of the same trajectory cost, per
+ * trajectory, for the built-in cart-pole and quadrotor (Euler and RK4).  What system identification (fit each vehicle's mass or
+ * inertia to a logged trajectory), weight tuning and set-point optimisation descend along.  The serial work is the costate of
+ * quattro_cost_gradient_f32; given it, every (trajectory, step) item stands alone.  The reference has no counterpart (its model
+ * parameters, weights and targets live inside the Python callables it is handed).
+ *   x [B][N+1][n], u [B][N][m] : as for quattro_cost_gradient_f32 (x is meant to be the rollout of u under the same rows; not checked)
+ *   costate [B][N+1][n] : fp32, the `costate` output of quattro_cost_gradient_f32 under the same rows; may be NULL when grad_phys is
+ *   model_phys [B][8], x_ref_rows [B][ref_rows][n], cost_rows [B][QUATTRO_COST_ROW_FLOATS] : exactly as quattro_cost_gradient_f32 takes
+ *                       them, each may be NULL on its own (p's values then)
+ * Outputs, all fp64, each may be NULL on its own, at least one must be given:
+ *   grad_phys [B][8]  : entry k < NP (4: cart-pole, 7: quadrotor) = sum_{t=0}^{N-1} sum_i lambda_{t+1,i} d f_i / d theta_k (x_t, u_t),
+ *                       f the whole integrator step (p->integrator, zero-order-hold u) at trajectory b's own phys; entries
+ *                       k >= NP are +0.0
+ *   grad_cost_rows [B][QUATTRO_COST_ROW_FLOATS], in the layout of a cost row:
+ *                       q_i  at float 0  : sum_{t<N} (x_{t,i} - ref_{t,i})^2
+ *                       qf_i at float 16 : (x_{N,i} - ref_{N,i})^2
+ *                       r_a  at float 32 : sum_{t<N} u_{t,a}^2           and +0.0 beyond n / m
+ *   grad_ref_rows [B][R][n], R = ref_rows, or R = 1 when x_ref_rows is NULL (the gradient with respect to a per-trajectory copy
+ *                       of p->x_ref): row rho = sum_{t<N, min(t,R-1)=rho} -2 q_i (x_{t,i} - ref_{rho,i}), plus the terminal term
+ *                       -2 qf_i (x_{N,i} - ref_{rho,i}) in the row with min(N, R-1) = rho: the row rule of
+ *                       quattro_cost_gradient_f32.  Rows past the horizon are +0.0
+ * Not differentiated: dt, the barrier (it has no weight in a row and contributes nothing to grad_cost_rows), anything of a user
+ * model.  d f / d theta comes from forward-mode duals through a scalar-generic statement of the two rates and the integrator
+ * (csrc/models_generic.h): its derivative part is used, its value part is not the rollouts' bits.
+ * One wave per trajectory, a step per lane, 64 steps a pass (csrc/cost_param_gradient.hip).  Per-step terms are fp32 (the
+ * cart-pole's are formed in fp64 and rounded once: its d f / d length cancels where the pole balances under the force, and fp32
+ * sines and products lose the bound there), every sum is
+ * fp64 and runs over t = 0 .. N in that order whatever B or the launch geometry: no atomics, nothing allocated, no workspace.  An
+ * entry with no non-zero term is +0.0.  The results of trajectory b are those of a call with B = 1 and p's fields set to row b, bit
+ * for bit, and an output does not depend on which other outputs are asked for.
+ * Before any launch: the model check of quattro_total_cost_f32 first; QUATTRO_ERR_UNSUPPORTED for QUATTRO_MODEL_USER (a user-model
+ * library exports the entry and answers this); then QUATTRO_ERR_BAD_ARG for a NULL x or u, all three outputs NULL, grad_phys without
+ * costate, B <= 0, N <= 0, reference rows with ref_rows < 1 (not looked at without rows), or a row array that is not 16-byte
+ * aligned. */
+int quattro_cost_param_gradient_f32(const quattro_model_params* p, const float* x, const float* u, int B, int N,
+                                    const float* costate, const float* model_phys, const float* x_ref_rows, int ref_rows,
+                                    const float* cost_rows, double* grad_phys, double* grad_cost_rows, double* grad_ref_rows,
+                                    void* stream);
+
 /* Transformer gain predictor: weights of the reference's TransformerPredictor (quattro_ilqr_tf/transformer_model.py:85-138)
  * as DEVICE pointers, plus the DataNormalizer vectors (:15-50).  Matrices are PyTorch Linear layout [out][in];
  * the `w_*` matrices are 16-bit (raw uint16 bit patterns: bf16, or IEEE half when `precision` says so), everything else

@@ -25,6 +25,10 @@ int quattro_launch_score(const quattro_model_params&, const float*, const float*
                          const float*, int, float*, double*, hipStream_t);
 int quattro_launch_cost_gradient(const quattro_model_params&, const float*, const float*, int, int, const float*, const float*, int,
                                  const float*, float*, float*, float*, hipStream_t);
+#ifndef QT_USER_MODEL_HEADER   // (built-in models only: a user-model library answers for its model without the kernel unit)
+int quattro_launch_cost_param_gradient(const quattro_model_params&, const float*, const float*, int, int, const float*, const float*,
+                                       const float*, int, const float*, double*, double*, double*, hipStream_t);
+#endif
 int quattro_launch_rollout(const quattro_model_params&, const float*, const float*, const float*, const float*,
                            const float*, int, int, int, float*, float*, double*, const int32_t*, hipStream_t);
 int quattro_launch_linesearch(const quattro_model_params&, float*, float*, const float*, const float*, const float*,
@@ -250,6 +254,24 @@ int quattro_cost_gradient_f32(const quattro_model_params* p, const float* x, con
   if ((((uintptr_t)model_phys | (uintptr_t)x_ref_rows | (uintptr_t)cost_rows) & 15) != 0) return QUATTRO_ERR_BAD_ARG;
   return quattro_launch_cost_gradient(*p, x, u, B, N, model_phys, x_ref_rows, ref_rows, cost_rows, grad_u, grad_x0, costate,
                                       (hipStream_t)stream);
+}
+
+int quattro_cost_param_gradient_f32(const quattro_model_params* p, const float* x, const float* u, int B, int N,
+                                    const float* costate, const float* model_phys, const float* x_ref_rows, int ref_rows,
+                                    const float* cost_rows, double* grad_phys, double* grad_cost_rows, double* grad_ref_rows,
+                                    void* stream) {
+  if (!model_ok(p)) return p ? QUATTRO_ERR_UNSUPPORTED : QUATTRO_ERR_BAD_ARG;
+  if (p->model_id == QUATTRO_MODEL_USER) return QUATTRO_ERR_UNSUPPORTED;
+  if (!x || !u || (!grad_phys && !grad_cost_rows && !grad_ref_rows) || (grad_phys && !costate) || B <= 0 || N <= 0)
+    return QUATTRO_ERR_BAD_ARG;
+  if (x_ref_rows != nullptr && ref_rows < 1) return QUATTRO_ERR_BAD_ARG;
+  if ((((uintptr_t)model_phys | (uintptr_t)x_ref_rows | (uintptr_t)cost_rows) & 15) != 0) return QUATTRO_ERR_BAD_ARG;
+#ifdef QT_USER_MODEL_HEADER
+  return QUATTRO_ERR_UNSUPPORTED;      // (this library holds one user model's kernels; the built-in models' are the main library's)
+#else
+  return quattro_launch_cost_param_gradient(*p, x, u, B, N, costate, model_phys, x_ref_rows, ref_rows, cost_rows, grad_phys,
+                                            grad_cost_rows, grad_ref_rows, (hipStream_t)stream);
+#endif
 }
 
 int quattro_rollout_f32(const quattro_model_params* p, const float* x_nom, const float* u_nom, const float* K,

@@ -7,6 +7,10 @@ of the gradient by the incoming one (one torch multiplication per output) and, u
 ops.track asks for (x_nom and K: not read with the feedback off).  The placeholders of the LAST shape and device are kept, so that a
 loop over one problem does not fill them again: (B, N, m, n) floats of device memory for K, 39 MB for the quadrotor at B = 4096,
 N = 50.  autograd.release_placeholders() gives them back.
+
+The rows -- model_phys, weights, targets -- are differentiable too where they are passed as torch tensors that require a gradient:
+the backward pass then adds ONE ops.cost_param_gradient launch on the costate of the adjoint sweep (system identification, weight
+tuning, goal optimisation; built-in models).  Without such a tensor nothing changes: the same launches, the same bits.
 """
 import torch
 
@@ -68,25 +72,96 @@ class _TrajectoryCost(torch.autograd.Function):
         return grad_x0, grad_u, None, None, None, None
 
 
+def _row_grad(g, like, pad_cols=None):
+    """A gradient in the layout ops.cost_param_gradient returns -> the shape, dtype and device `like` of the tensor that was passed
+    as the row.  pad_cols: for a row passed in the C ABI's padded form, (width, column index of every entry of g); the padding is zero."""
+    shape, dtype, device = like
+    if pad_cols is not None and shape[-1] == pad_cols[0] and g.shape[-1] != pad_cols[0]:
+        full = torch.zeros((g.shape[0], pad_cols[0]), dtype=g.dtype, device=g.device)
+        full[:, pad_cols[1]] = g
+        g = full
+    return g.reshape(shape).to(device=device, dtype=dtype)
+
+
+class _TrajectoryCostRows(torch.autograd.Function):
+    """_TrajectoryCost with the rows as inputs of the function: the same forward pass; the backward pass adds one
+    ops.cost_param_gradient launch for the rows that ask for a gradient (and skips the adjoint sweep when nothing needs it)."""
+
+    @staticmethod
+    def forward(ctx, x0, u, row_phys, row_weights, row_targets, model, targets, weights, model_phys):
+        x0d, ud = x0.detach().contiguous(), u.detach().contiguous()
+        x, cost = _forward(model, x0d, ud, targets, weights, model_phys)
+        ctx.save_for_backward(x, ud)
+        ctx.call = (model, targets, weights, model_phys)
+        ctx.like = tuple(None if r is None else (tuple(r.shape), r.dtype, r.device) for r in (row_phys, row_weights, row_targets))
+        return cost
+
+    @staticmethod
+    def backward(ctx, grad_cost):
+        x, u = ctx.saved_tensors
+        model, targets, weights, model_phys = ctx.call
+        want_x0, want_u, want_phys, want_w, want_t = ctx.needs_input_grad[:5]
+        like_phys, like_w, like_t = ctx.like
+        n, m = model.n, model.m
+        g = None
+        if want_x0 or want_u or want_phys:
+            g = ops.cost_gradient(model, x, u, targets=targets, weights=weights, model_phys=model_phys, want_x0=want_x0,
+                                  want_costate=want_phys)
+        w = grad_cost.to(torch.float32)
+        grad_u = g["grad_u"] * w[:, None, None] if want_u else None
+        grad_x0 = g["grad_x0"] * w[:, None] if want_x0 else None
+        want = tuple(name for name, on in (("phys", want_phys), ("weights", want_w), ("targets", want_t)) if on)
+        pg = ops.cost_param_gradient(model, x, u, targets=targets, weights=weights, model_phys=model_phys, want=want,
+                                     costate=g["costate"] if want_phys else None) if want else {}
+        w64 = grad_cost.to(torch.float64)
+        grad_phys = grad_w = grad_t = None
+        if want_phys:
+            grad_phys = _row_grad(pg["grad_phys"] * w64[:, None], like_phys, (8, list(range(len(model.phys)))))
+        if want_w:
+            MX = ops._lib.MAX_NX
+            cols = list(range(n)) + list(range(MX, MX + n)) + list(range(2 * MX, 2 * MX + m))
+            grad_w = _row_grad(pg["grad_weights"] * w64[:, None], like_w, (ops.COST_ROW_FLOATS, cols))
+        if want_t:
+            grad_t = _row_grad(pg["grad_targets"] * w64[:, None, None], like_t)
+        return grad_x0, grad_u, grad_phys, grad_w, grad_t, None, None, None, None
+
+
+def _wants_grad(row):
+    return isinstance(row, torch.Tensor) and row.requires_grad
+
+
 def trajectory_cost(model, x0, u, targets=None, weights=None, model_phys=None):
     """J(x0, u) per trajectory: x0 (B, n), u (B, N, m), float32 device tensors -> cost (B,) float64, differentiable with respect to
-    x0 and u (torch.autograd.Function).
+    x0 and u, and with respect to the rows or the model's parameters where a row is a torch tensor that requires a gradient
+    (torch.autograd.Function).
       forward   without rows: ops.simulate, whose cost is returned.  With rows: the rollout under model_phys
                 (ops.track(..., feedback=False, plant_phys=model_phys)) when that row is given, otherwise ops.simulate; the cost is
                 ops.score(..., terminal=True) under the same rows
       backward  one ops.cost_gradient launch on the saved x, u under the same rows, scaled per trajectory by the incoming gradient
-                (cast to float32: the gradients are float32 like x0 and u)
-    targets, weights, model_phys: per-trajectory rows in the forms ops.score and ops.cost_gradient take.  NOTHING is differentiable
-    with respect to the rows or the model's parameters: they are constants of the function, and a tensor passed for them receives
-    no gradient.  Second derivatives are not available either (the backward pass is not itself differentiable)."""
+                (cast to float32: the gradients are float32 like x0 and u); for rows that require a gradient one
+                ops.cost_param_gradient launch more, on the costate of the first (which is skipped when neither x0, u nor model_phys
+                needs it)
+    targets, weights, model_phys: per-trajectory rows in the forms ops.score and ops.cost_gradient take.  A torch tensor among them
+    with requires_grad -- model_phys (B, len(phys)), weights (B, 2n + m), targets (B, R, n) or (B, n), or the padded device forms
+    of the C ABI -- receives dJ/d(row) in its own shape, dtype and device: ops.cost_param_gradient's fp64 result times the incoming
+    gradient, cast; padding entries are zero.  Anything else (a dict of weights, arrays, tensors without requires_grad) is a constant
+    of the function, and then the function makes the launches and returns the bits it always has.  Built-in models only for the
+    row gradients (NotImplementedError from the backward pass of a user-compiled model).  dt and the barrier are not
+    differentiated.  Second derivatives are not available either (the backward pass is not itself differentiable)."""
     # the rows are converted once, so that forward and backward see the same device arrays
+    rows_in = (model_phys, None if isinstance(weights, dict) else weights, targets)
     Bt = int(u.shape[0]) if hasattr(u, "shape") and len(u.shape) == 3 else 0
     if Bt > 0:
         ops.check_phys_rows(model, model_phys, Bt, "model_phys")
         ops.check_ref_rows(model, targets, Bt, name="targets")
         ops.check_cost_rows(model, weights, Bt, name="weights")
         if u.is_cuda:
-            model_phys = ops.model_phys_tensor(model, model_phys, Bt, u.device)
-            targets = ops.x_ref_rows_tensor(model, targets, Bt, u.device, name="targets")
-            weights = ops.cost_rows_tensor(model, weights, Bt, u.device, name="weights")
-    return _TrajectoryCost.apply(x0, u, model, targets, weights, model_phys)
+            with torch.no_grad():
+                model_phys = ops.model_phys_tensor(model, model_phys, Bt, u.device)
+                targets = ops.x_ref_rows_tensor(model, targets, Bt, u.device, name="targets")
+                weights = ops.cost_rows_tensor(model, weights, Bt, u.device, name="weights")
+    if not any(_wants_grad(r) for r in rows_in):
+        return _TrajectoryCost.apply(x0, u, model, targets, weights, model_phys)
+    detach = lambda t: t.detach() if isinstance(t, torch.Tensor) else t
+    rows_in = tuple(r if _wants_grad(r) else None for r in rows_in)
+    return _TrajectoryCostRows.apply(x0, u, *rows_in, model, detach(targets), detach(weights), detach(model_phys))

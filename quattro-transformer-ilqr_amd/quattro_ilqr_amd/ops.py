@@ -750,6 +750,73 @@ def cost_gradient(model, x, u, targets=None, weights=None, model_phys=None, want
     return out
 
 
+PARAM_GRADIENT_WANTS = ("phys", "weights", "targets")
+
+
+def cost_param_gradient(model, x, u, targets=None, weights=None, model_phys=None, want=PARAM_GRADIENT_WANTS, costate=None):
+    """Gradient of the trajectory cost of ops.cost_gradient with respect to what a trajectory's rows hold, on the device
+    (quattro_cost_param_gradient_f32) about x (B, N+1, n), u (B, N, m): -> dict of float64 device tensors, by `want`:
+      "phys"     "grad_phys" (B, len(model.phys)): sum_t lambda_{t+1}^T df/dtheta_k (x_t, u_t), f the whole integrator step at
+                 trajectory b's own parameters
+      "weights"  "grad_weights" (B, 2n + m) in the order [q | qf | r]: sum_t (x_t - ref_t)^2, (x_N - ref_N)^2, sum_t u_t^2
+      "targets"  "grad_targets" (B, R, n): row rho collects -2 q (x_t - ref_rho) of the steps that read it (min(t, R - 1) = rho) and
+                 -2 qf (x_N - ref_rho) where the terminal term reads it; R = 1 without targets (the gradient with respect to a
+                 per-trajectory copy of model.x_ref); rows past the horizon are zero
+    targets, weights, model_phys: the rows the gradient is taken about, in the forms ops.cost_gradient takes; None: the model's own
+    values.  costate (B, N+1, n) float32: ops.cost_gradient(..., want_costate=True)["costate"] under the same rows, used as it is;
+    None with "phys" wanted: that call is made first (two launches).  The barrier and dt are not differentiated.  Built-in models
+    only: NotImplementedError for a user-compiled model.  ValueError for a wrong shape or an unknown entry of `want`, before
+    anything touches the device."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    unknown = [w for w in want if w not in PARAM_GRADIENT_WANTS]
+    if unknown or not want:
+        raise ValueError(f"want must name at least one of {list(PARAM_GRADIENT_WANTS)} (got {list(want)})")
+    if len(np.shape(x)) != 3 or len(np.shape(u)) != 3:
+        raise ValueError(f"x must have shape (B, N + 1, n) and u (B, N, m) (got {tuple(np.shape(x))} and {tuple(np.shape(u))})")
+    Bt, N, m = (int(v) for v in u.shape)
+    if Bt < 1 or N < 1 or m != model.m or tuple(x.shape) != (Bt, N + 1, model.n):
+        raise ValueError(f"x must have shape (B, N + 1, {model.n}) and u (B, N, {model.m}) with B, N >= 1 "
+                         f"(got {tuple(x.shape)} and {tuple(u.shape)})")
+    check_phys_rows(model, model_phys, Bt, "model_phys")
+    check_ref_rows(model, targets, Bt, name="targets")
+    check_cost_rows(model, weights, Bt, name="weights")
+    if costate is not None and tuple(np.shape(costate)) != (Bt, N + 1, model.n):
+        raise ValueError(f"costate must have shape {(Bt, N + 1, model.n)} (got {tuple(np.shape(costate))})")
+    if model.model_id == _lib.MODEL_USER:
+        raise NotImplementedError("cost_param_gradient runs only for the built-in models: a user-compiled model reads its parameters "
+                                  "as float and its cost is arbitrary")
+    f32, f64 = torch.float32, torch.float64
+    _req(x, (Bt, N + 1, model.n), f32, "x"); _req(u, (Bt, N, model.m), f32, "u")
+    n, dev = model.n, u.device
+    model_phys = model_phys_tensor(model, model_phys, Bt, dev)
+    rows = x_ref_rows_tensor(model, targets, Bt, dev, name="targets")
+    cost_rows = cost_rows_tensor(model, weights, Bt, dev, name="weights")
+    if "phys" in want:
+        if costate is None:
+            costate = cost_gradient(model, x, u, targets=rows, weights=cost_rows, model_phys=model_phys, want_x0=False,
+                                    want_costate=True)["costate"]
+        _req(costate, (Bt, N + 1, n), f32, "costate")
+    R = 1 if rows is None else int(rows.shape[1])
+    g_phys = torch.empty((Bt, 8), dtype=f64, device=dev) if "phys" in want else None
+    g_cost = torch.empty((Bt, COST_ROW_FLOATS), dtype=f64, device=dev) if "weights" in want else None
+    g_ref = torch.empty((Bt, R, n), dtype=f64, device=dev) if "targets" in want else None
+    p = model.c_params()
+    check(_lib.load_for(model).quattro_cost_param_gradient_f32(ctypes.byref(p), _ptr(x), _ptr(u), Bt, N,
+                                                               _ptr(costate) if "phys" in want else None, _ptr(model_phys),
+                                                               _ptr(rows), 0 if rows is None else R, _ptr(cost_rows), _ptr(g_phys),
+                                                               _ptr(g_cost), _ptr(g_ref), _stream()),
+          "quattro_cost_param_gradient_f32")
+    out = {}
+    if g_phys is not None:
+        out["grad_phys"] = g_phys[:, :len(model.phys)].contiguous()
+    if g_cost is not None:
+        out["grad_weights"] = torch.cat([g_cost[:, :n], g_cost[:, _lib.MAX_NX:_lib.MAX_NX + n],
+                                         g_cost[:, 2 * _lib.MAX_NX:2 * _lib.MAX_NX + m]], dim=1)
+    if g_ref is not None:
+        out["grad_targets"] = g_ref
+    return out
+
+
 def track(model, x0, x_nom, u_nom, K, steps, plant=None, plant_phys=None, feedback=True, disturbance=None):
     """`steps` <= N plant steps from x0 (B,n) along the first rows of a nominal with its gains (quattro_track_f32):
     u = u_nom[j] + (feedback ? K[j] (x - x_nom[j]) : 0), x <- f_plant(x, u) + disturbance[j].  plant: a DeviceModel like `model`
