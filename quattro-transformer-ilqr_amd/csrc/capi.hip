@@ -44,6 +44,10 @@ size_t quattro_solve_log_offset_impl(int, int, int, int, int);
 int quattro_launch_solve_log_record(const quattro_solve_log&, int, const float*, const float*, const float*, const float*,
                                     const double*, const int32_t*, const int32_t*, const int32_t*, int, int, int, int, int,
                                     hipStream_t);
+#ifdef QT_USER_PARAM_GRAD      // (a user-model library built with compile_model(..., param_grad=True): user_param_gradient.hip)
+int quattro_launch_user_param_gradient(const quattro_model_params&, const float*, const float*, int, int, const float*, const float*,
+                                       const float*, int, const float*, double*, double*, double*, hipStream_t);
+#endif
 #ifdef QT_USER_MODEL_HEADER
 int quattro_launch_sweep_rowpad_user(const float*, const float*, const float*, int, int, int, int, float, float*, float*, int32_t*,
                                      const int32_t*, bool, hipStream_t);
@@ -261,12 +265,18 @@ int quattro_cost_param_gradient_f32(const quattro_model_params* p, const float* 
                                     const float* cost_rows, double* grad_phys, double* grad_cost_rows, double* grad_ref_rows,
                                     void* stream) {
   if (!model_ok(p)) return p ? QUATTRO_ERR_UNSUPPORTED : QUATTRO_ERR_BAD_ARG;
+#ifndef QT_USER_PARAM_GRAD
   if (p->model_id == QUATTRO_MODEL_USER) return QUATTRO_ERR_UNSUPPORTED;
+#endif
   if (!x || !u || (!grad_phys && !grad_cost_rows && !grad_ref_rows) || (grad_phys && !costate) || B <= 0 || N <= 0)
     return QUATTRO_ERR_BAD_ARG;
   if (x_ref_rows != nullptr && ref_rows < 1) return QUATTRO_ERR_BAD_ARG;
   if ((((uintptr_t)model_phys | (uintptr_t)x_ref_rows | (uintptr_t)cost_rows) & 15) != 0) return QUATTRO_ERR_BAD_ARG;
-#ifdef QT_USER_MODEL_HEADER
+#ifdef QT_USER_PARAM_GRAD
+  if (p->model_id != QUATTRO_MODEL_USER) return QUATTRO_ERR_UNSUPPORTED;
+  return quattro_launch_user_param_gradient(*p, x, u, B, N, costate, model_phys, x_ref_rows, ref_rows, cost_rows, grad_phys,
+                                            grad_cost_rows, grad_ref_rows, (hipStream_t)stream);
+#elif defined(QT_USER_MODEL_HEADER)
   return QUATTRO_ERR_UNSUPPORTED;      // (this library holds one user model's kernels; the built-in models' are the main library's)
 #else
   return quattro_launch_cost_param_gradient(*p, x, u, B, N, costate, model_phys, x_ref_rows, ref_rows, cost_rows, grad_phys,

@@ -14,6 +14,9 @@
 // default_final_cost are the built-in diagonal forms).  In a solve or closed loop with reference rows (quattro_ilqr_solve_ref_f32,
 // quattro_mpc_run_ref_f32) stage_cost at horizon step t and final_cost see that step's row of x_ref_rows as p.x_ref[0 .. n-1],
 // whatever they do with it; the model itself needs no change.  Compiled with -DQT_USER_MODEL_HEADER="..." -DQT_USER_NX=n -DQT_USER_NU=m.
+// compile_model(..., param_grad=True) generates the three templates over the parameter block as well
+// (template <class T, class PB = quattro_model_params> rate(const PB& p, ...)) and adds -DQT_USER_PARAM_GRAD=1 -DQT_USER_NP=len(phys)
+// and the unit user_param_gradient.hip, which instantiates them over a block of duals; every other kernel calls them as before.
 #pragma once
 #include "dual.h"
 
@@ -31,8 +34,10 @@ constexpr int NX = QT_USER_NX, NU = QT_USER_NU;
 
 // L = sum_i q_i (x_i - x_ref_i)^2 + sum_a r_a u_a^2 + barrier_alpha sum_a softplus_beta(-u_a)^2, Lf = sum_i qf_i (x_i - x_ref_i)^2:
 // the cost form of both shipped problems (include/quattro_hip.h), for any scalar type
-template <class T>
-__device__ __forceinline__ T default_stage_cost(const quattro_model_params& p, const T* x, const T* u) {
+// (PB: the parameter block, quattro_model_params everywhere but in user_param_gradient.hip, whose block holds x_ref and the weights
+//  as dual numbers; with PB = quattro_model_params these are the functions they always were)
+template <class T, class PB = quattro_model_params>
+__device__ __forceinline__ T default_stage_cost(const PB& p, const T* x, const T* u) {
   T c(0.0f);
 #pragma unroll
   for (int i = 0; i < NX; ++i) {
@@ -50,8 +55,8 @@ __device__ __forceinline__ T default_stage_cost(const quattro_model_params& p, c
   }
   return c;
 }
-template <class T>
-__device__ __forceinline__ T default_final_cost(const quattro_model_params& p, const T* x) {
+template <class T, class PB = quattro_model_params>
+__device__ __forceinline__ T default_final_cost(const PB& p, const T* x) {
   T c(0.0f);
 #pragma unroll
   for (int i = 0; i < NX; ++i) {
@@ -67,8 +72,8 @@ __device__ __forceinline__ T default_final_cost(const quattro_model_params& p, c
 // rollouts of a user model go through (qt_step), but NOT its bits: this one is generic over dual numbers and written as
 // x + k * (0.5f * dt) without fmaf, so a linearisation's value part may differ from the rollout in the last bit.  Moving it onto
 // rk4_step would change user-model records; it stays a copy.
-template <class T, bool RK4>
-__device__ __forceinline__ void step(const quattro_model_params& p, const T* x, const T* u, T* xn) {
+template <class T, bool RK4, class PB = quattro_model_params>
+__device__ __forceinline__ void step(const PB& p, const T* x, const T* u, T* xn) {
   const float dt = p.dt;
   T k1[NX];
   rate<T>(p, x, u, k1);

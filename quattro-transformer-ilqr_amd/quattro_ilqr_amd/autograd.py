@@ -10,7 +10,7 @@ N = 50.  autograd.release_placeholders() gives them back.
 
 The rows -- model_phys, weights, targets -- are differentiable too where they are passed as torch tensors that require a gradient:
 the backward pass then adds ONE ops.cost_param_gradient launch on the costate of the adjoint sweep (system identification, weight
-tuning, goal optimisation; built-in models).  Without such a tensor nothing changes: the same launches, the same bits.
+tuning, goal optimisation; the built-in models and user models compiled with param_grad=True).  Without such a tensor nothing changes: the same launches, the same bits.
 """
 import torch
 
@@ -145,8 +145,9 @@ def trajectory_cost(model, x0, u, targets=None, weights=None, model_phys=None):
     with requires_grad -- model_phys (B, len(phys)), weights (B, 2n + m), targets (B, R, n) or (B, n), or the padded device forms
     of the C ABI -- receives dJ/d(row) in its own shape, dtype and device: ops.cost_param_gradient's fp64 result times the incoming
     gradient, cast; padding entries are zero.  Anything else (a dict of weights, arrays, tensors without requires_grad) is a constant
-    of the function, and then the function makes the launches and returns the bits it always has.  Built-in models only for the
-    row gradients (NotImplementedError from the backward pass of a user-compiled model).  dt and the barrier are not
+    of the function, and then the function makes the launches and returns the bits it always has.  The row gradients run for
+    the built-in models and for a user model compiled with compile_model(..., param_grad=True), whose own costs and dynamics are
+    then differentiated (NotImplementedError from the backward pass of any other user-compiled model).  dt and the barrier are not
     differentiated.  Second derivatives are not available either (the backward pass is not itself differentiable)."""
     # the rows are converted once, so that forward and backward see the same device arrays
     rows_in = (model_phys, None if isinstance(weights, dict) else weights, targets)

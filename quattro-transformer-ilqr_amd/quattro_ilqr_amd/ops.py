@@ -764,8 +764,11 @@ def cost_param_gradient(model, x, u, targets=None, weights=None, model_phys=None
                  per-trajectory copy of model.x_ref); rows past the horizon are zero
     targets, weights, model_phys: the rows the gradient is taken about, in the forms ops.cost_gradient takes; None: the model's own
     values.  costate (B, N+1, n) float32: ops.cost_gradient(..., want_costate=True)["costate"] under the same rows, used as it is;
-    None with "phys" wanted: that call is made first (two launches).  The barrier and dt are not differentiated.  Built-in models
-    only: NotImplementedError for a user-compiled model.  ValueError for a wrong shape or an unknown entry of `want`, before
+    None with "phys" wanted: that call is made first (two launches).  The barrier and dt are not differentiated.  The built-in
+    models, and a user model compiled with compile_model(..., param_grad=True): its costs are arbitrary, so every entry is then the
+    derivative of the whole cost -- "phys" adds dL/dtheta_k and dLf/dtheta_k of a cost that reads P, each weight collects its partial
+    of both L and Lf, each target row those of the slots that read it (for a default cost these are the forms above).
+    NotImplementedError for any other user-compiled model.  ValueError for a wrong shape or an unknown entry of `want`, before
     anything touches the device."""
     want = (want,) if isinstance(want, str) else tuple(want)
     unknown = [w for w in want if w not in PARAM_GRADIENT_WANTS]
@@ -782,9 +785,9 @@ def cost_param_gradient(model, x, u, targets=None, weights=None, model_phys=None
     check_cost_rows(model, weights, Bt, name="weights")
     if costate is not None and tuple(np.shape(costate)) != (Bt, N + 1, model.n):
         raise ValueError(f"costate must have shape {(Bt, N + 1, model.n)} (got {tuple(np.shape(costate))})")
-    if model.model_id == _lib.MODEL_USER:
-        raise NotImplementedError("cost_param_gradient runs only for the built-in models: a user-compiled model reads its parameters "
-                                  "as float and its cost is arbitrary")
+    if model.model_id == _lib.MODEL_USER and not getattr(model, "param_grad", False):
+        raise NotImplementedError("cost_param_gradient runs only for the built-in models and for user models compiled with "
+                                  "compile_model(..., param_grad=True): without it a user-compiled model reads its parameters as float")
     f32, f64 = torch.float32, torch.float64
     _req(x, (Bt, N + 1, model.n), f32, "x"); _req(u, (Bt, N, model.m), f32, "u")
     n, dev = model.n, u.device

@@ -17,6 +17,9 @@ import dual_probe                   # tests/test_dual_algebra_gpu.py: the probe 
 built += [L.model().lib_path for L in dual_probe.all_libs()]
 import user_grid_cases              # tests/test_user_grid_gpu.py: one library per (n, m) of the grid
 built += [md.lib_path for md in user_grid_cases.all_models()]
+import upgrad_cases                 # tests/test_user_param_gradient_gpu.py: the param_grad=True libraries
+built += [md.lib_path for md in upgrad_cases.all_models()]
+built.append(user_model.example_planar_model(param_grad=True).lib_path)      # scripts/time_cost_param_gradient.py
 print("\n".join(sorted(set(built))))
 # entries of earlier source / flag states (the cache key covers both) are dead weight in every snapshot sent to a GPU box
 import shutil

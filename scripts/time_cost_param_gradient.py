@@ -2,10 +2,13 @@
 `rounds` repetitions in which the contenders alternate:
     cost_gradient        the adjoint sweep it sits beside (one quattro_cost_gradient_f32 call, costate output included): the yardstick
     param_gradient       ONE quattro_cost_param_gradient_f32 call, all three outputs, on a given costate
+    param_gradient_phys  the same call with grad_phys alone
     param_gradient_ops   the two-launch form: ops.cost_param_gradient without a costate (the sweep, then the call above)
-at quadrotor Euler and RK4 (B = 4096, N = 50) and cart-pole Euler and RK4 (B = 1024, N = 50), under per-trajectory weights, targets
-(R = N + 1) and parameters.  x is the rollout of u from a seeded batch of starts about the model's x_ref.  `not_slower`: in how many
-rounds the param_gradient's time was at most the cost_gradient's of the same round (the Euler cases are the gated ones: 6 of 7).
+at quadrotor Euler and RK4 (B = 4096, N = 50), cart-pole Euler and RK4 (B = 1024, N = 50) and the user-compiled planar example
+(user_model.example_planar_model(param_grad=True), Euler and RK4, B = 4096, N = 50; --only planar runs these alone), under
+per-trajectory weights, targets (R = N + 1) and parameters.  x is the rollout of u from a seeded batch of starts about the model's x_ref.  `not_slower`: in how many
+rounds the param_gradient's time was at most the cost_gradient's of the same round (the Euler cases are the gated ones: 6 of 7);
+`phys_not_slower`: the same for param_gradient_phys (the planar model's gate).
 Prints one JSON line; median (min - max) in microseconds per call."""
 import argparse
 import ctypes
@@ -23,15 +26,19 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--inner", type=int, default=200)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--only", default="", help="run the cases whose name starts with this")
     args = ap.parse_args()
     import numpy as np
     import torch
-    from quattro_ilqr_amd import models, ops
+    from quattro_ilqr_amd import models, ops, user_model
     assert torch.cuda.is_available(), "time_cost_param_gradient.py needs a GPU"
     dev = args.device
     N = 50
     cases = [("quadrotor euler", models.quadrotor_model(), 4096), ("quadrotor rk4", models.quadrotor_model(integrator="rk4"), 4096),
-             ("cartpole euler", models.cartpole_model(), 1024), ("cartpole rk4", models.cartpole_model(integrator="rk4"), 1024)]
+             ("cartpole euler", models.cartpole_model(), 1024), ("cartpole rk4", models.cartpole_model(integrator="rk4"), 1024),
+             ("planar euler", user_model.example_planar_model(integrator="euler", param_grad=True), 4096),
+             ("planar rk4", user_model.example_planar_model(integrator="rk4", param_grad=True), 4096)]
+    cases = [c for c in cases if c[0].startswith(args.only)]
 
     def timed(forms, rounds, inner):
         for f in forms.values():                      # warm: code objects, the allocator's blocks
@@ -58,7 +65,7 @@ def main():
         n, m = md.n, md.m
         g = torch.Generator(device=dev).manual_seed(B + N)
         ref = torch.as_tensor(np.asarray(md.x_ref, dtype=np.float32), device=dev)
-        hover = md.phys[0] * md.phys[5] / 4.0 if md.name == "quadrotor" else 0.0
+        hover = md.phys[0] * md.phys[5] / 4.0 if md.name == "quadrotor" else md.phys[0] * md.phys[3] / 2.0 if name.startswith("planar") else 0.0
         scale = 0.05 if md.name == "quadrotor" else 0.2
         x0 = (ref + scale * torch.randn((B, n), generator=g, device=dev)).contiguous()
         u = (hover + 0.1 * torch.randn((B, N, m), generator=g, device=dev)).contiguous()
@@ -85,11 +92,17 @@ def main():
             ops.check(lib.quattro_cost_param_gradient_f32(ctypes.byref(p), P(x), P(u), B, N, P(lam), *tail, P(gp), P(gw), P(gr), st),
                       "param")
 
-        forms = {"cost_gradient": c_sweep, "param_gradient": c_param,
+        def c_param_phys():
+            ops.check(lib.quattro_cost_param_gradient_f32(ctypes.byref(p), P(x), P(u), B, N, P(lam), *tail, P(gp), None, None, st),
+                      "param phys")
+
+        forms = {"cost_gradient": c_sweep, "param_gradient": c_param, "param_gradient_phys": c_param_phys,
                  "param_gradient_ops": lambda: ops.cost_param_gradient(md, x, u, **rows)}
         times = timed(forms, args.rounds, args.inner)
         wins = sum(1 for a, b in zip(times["param_gradient"], times["cost_gradient"]) if a <= b)
-        out[f"{name} B={B} N={N}"] = dict(not_slower=f"{wins}/{args.rounds}", **{k: stats(v) for k, v in times.items()})
+        wins_phys = sum(1 for a, b in zip(times["param_gradient_phys"], times["cost_gradient"]) if a <= b)
+        out[f"{name} B={B} N={N}"] = dict(not_slower=f"{wins}/{args.rounds}", phys_not_slower=f"{wins_phys}/{args.rounds}",
+                                          **{k: stats(v) for k, v in times.items()})
     print(json.dumps(out))
 
 
