@@ -597,6 +597,43 @@ int quattro_cost_param_gradient_f32(const quattro_model_params* p, const float* 
                                     const float* cost_rows, double* grad_phys, double* grad_cost_rows, double* grad_ref_rows,
                                     void* stream);
 
+/* GRADIENT OF THE TRACKED CLOSED-LOOP COST: dJ/dK, dJ/du_nom, dJ/dx_nom, dJ/dx0 and the closed-loop costate of n_steps <= N steps of
+ * quattro_track_f32 composed with quattro_score_f32 at ref_hold = 1,
+ *   u_t = u_nom_t + K_t (x_t - x_nom_t)   (K == NULL: feedback off, u_t = u_nom_t),   x_{t+1} = f_plant(x_t, u_t) + d_t,
+ *   J = sum_{t < n_steps} L(x_t, u_t) + [QUATTRO_SCORE_TERMINAL] Lf(x_{n_steps}).
+ * The law differentiated is iLQR_TF.forward_pass (quattro_ilqr_tf.py:377-390) with k = 0 and alpha = 1 (a feed-forward k or a step
+ * size alpha is an expression in front of u_nom and K, whose chain rule is the caller's); the reference has no counterpart (it never
+ * differentiates its forward pass).  What tuning the gains or the nominal, training a gain predictor on the cost its gains produce,
+ * and fitting a plant to a logged closed-loop run descend along.
+ *   x [B][n_steps+1][n], u [B][n_steps][m] : the outputs of quattro_track_f32 (the realised run; not checked)
+ *   x_nom [B][N+1][n], K [B][N][m][n] : the arrays that call was given; only rows < n_steps are read.  K == NULL: feedback off, x_nom is
+ *                       then not read, and grad_K and grad_x_nom must be NULL
+ *   p                 : the cost fields, and the integrator and phys the PLANT steps with (the host composes it)
+ *   model_phys [B][8] : per-trajectory plant rows (a user model's cost bodies see the same row); x_ref_rows [B][ref_rows][n], cost_rows
+ *                       [B][QUATTRO_COST_ROW_FLOATS] : exactly as quattro_cost_gradient_f32 takes them.  Step t is costed against row
+ *                       min(t, ref_rows - 1), the terminal term against the row of t = n_steps
+ *   flags             : QUATTRO_SCORE_TERMINAL or 0
+ *   lambda_S = terminal ? Lf_x(x_S) : 0;  for t = S-1 .. 0:  g_t = L_u + B_t^T lambda_{t+1},  lambda_t = L_x + A_t^T lambda_{t+1} + K_t^T g_t
+ *                       with [A_t | B_t] the derivative of the plant's whole integrator step at (x_t, u_t), S = n_steps
+ *   grad_u_nom [B][N][m] = g_t          grad_K [B][N][m][n] = g_t (x_t - x_nom_t)^T          grad_x_nom [B][N+1][n] = -K_t^T g_t
+ *                       the inputs' shapes; rows the tracked steps did not read (t >= n_steps) are written as +0.0
+ *   grad_x0 [B][n] = lambda_0           costate [B][n_steps+1][n] = lambda;  costate[b][t+1] is dJ/dd_t, and the multiplier
+ *                       quattro_cost_param_gradient_f32 takes (N = n_steps, the realised x, u) for the plant-parameter, weight and
+ *                       target gradients of the tracked cost.  All fp32; any output but grad_u_nom may be NULL
+ * The mapping of quattro_cost_gradient_f32 (csrc/track_gradient.hip).  The feedback is folded into what is staged off the chain: state
+ * lane j pushes the direction (e_j, K_t[:, j]) through the step (column j of A_t + B_t K_t, one tangent) and stages it with
+ * l_x[j] + K_t[:, j]^T l_u, so the chain stays one n-term dot product per lane and ONE exchange of lambda per step; grad_K and
+ * grad_x_nom are formed after each block of QUATTRO_GRAD_BLOCK steps from the g_t parked in LDS (one fp32 subtraction and one product
+ * per entry of grad_K).  No atomics, nothing allocated, no workspace; the results of trajectory b are those of a call with B = 1 and
+ * p's fields set to row b, bit for bit, and an output does not depend on which others are asked for.
+ * Before any launch: the model check of quattro_total_cost_f32 first; then QUATTRO_ERR_BAD_ARG for a NULL x, u or grad_u_nom, B, N or
+ * n_steps <= 0, n_steps > N, K without x_nom, grad_K or grad_x_nom without K, reference rows with ref_rows < 1, a row array that is not
+ * 16-byte aligned, or unknown bits in flags. */
+int quattro_track_gradient_f32(const quattro_model_params* p, const float* x, const float* u, int B, int N, int n_steps,
+                               const float* x_nom, const float* K, const float* model_phys, const float* x_ref_rows, int ref_rows,
+                               const float* cost_rows, int flags, float* grad_u_nom, float* grad_K, float* grad_x_nom,
+                               float* grad_x0, float* costate, void* stream);
+
 /* Transformer gain predictor: weights of the reference's TransformerPredictor (quattro_ilqr_tf/transformer_model.py:85-138)
  * as DEVICE pointers, plus the DataNormalizer vectors (:15-50).  Matrices are PyTorch Linear layout [out][in];
  * the `w_*` matrices are 16-bit (raw uint16 bit patterns: bf16, or IEEE half when `precision` says so), everything else

@@ -25,6 +25,9 @@ int quattro_launch_score(const quattro_model_params&, const float*, const float*
                          const float*, int, float*, double*, hipStream_t);
 int quattro_launch_cost_gradient(const quattro_model_params&, const float*, const float*, int, int, const float*, const float*, int,
                                  const float*, float*, float*, float*, hipStream_t);
+int quattro_launch_track_gradient(const quattro_model_params&, const float*, const float*, int, int, int, const float*, const float*,
+                                  const float*, const float*, int, const float*, int, float*, float*, float*, float*, float*,
+                                  hipStream_t);
 #ifndef QT_USER_MODEL_HEADER   // (built-in models only: a user-model library answers for its model without the kernel unit)
 int quattro_launch_cost_param_gradient(const quattro_model_params&, const float*, const float*, int, int, const float*, const float*,
                                        const float*, int, const float*, double*, double*, double*, hipStream_t);
@@ -282,6 +285,22 @@ int quattro_cost_param_gradient_f32(const quattro_model_params* p, const float* 
   return quattro_launch_cost_param_gradient(*p, x, u, B, N, costate, model_phys, x_ref_rows, ref_rows, cost_rows, grad_phys,
                                             grad_cost_rows, grad_ref_rows, (hipStream_t)stream);
 #endif
+}
+
+int quattro_track_gradient_f32(const quattro_model_params* p, const float* x, const float* u, int B, int N, int n_steps,
+                               const float* x_nom, const float* K, const float* model_phys, const float* x_ref_rows, int ref_rows,
+                               const float* cost_rows, int flags, float* grad_u_nom, float* grad_K, float* grad_x_nom,
+                               float* grad_x0, float* costate, void* stream) {
+  if (!model_ok(p)) return p ? QUATTRO_ERR_UNSUPPORTED : QUATTRO_ERR_BAD_ARG;
+  if (!x || !u || !grad_u_nom || B <= 0 || N <= 0 || n_steps <= 0 || n_steps > N) return QUATTRO_ERR_BAD_ARG;
+  if (K != nullptr && x_nom == nullptr) return QUATTRO_ERR_BAD_ARG;
+  if (K == nullptr && (grad_K != nullptr || grad_x_nom != nullptr)) return QUATTRO_ERR_BAD_ARG;
+  if (x_ref_rows != nullptr && ref_rows < 1) return QUATTRO_ERR_BAD_ARG;
+  if ((((uintptr_t)model_phys | (uintptr_t)x_ref_rows | (uintptr_t)cost_rows) & 15) != 0) return QUATTRO_ERR_BAD_ARG;
+  if ((flags & ~QUATTRO_SCORE_TERMINAL) != 0) return QUATTRO_ERR_BAD_ARG;
+  return quattro_launch_track_gradient(*p, x, u, B, N, n_steps, K != nullptr ? x_nom : nullptr, K, model_phys, x_ref_rows, ref_rows,
+                                       cost_rows, (flags & QUATTRO_SCORE_TERMINAL) != 0 ? 1 : 0, grad_u_nom, grad_K, grad_x_nom,
+                                       grad_x0, costate, (hipStream_t)stream);
 }
 
 int quattro_rollout_f32(const quattro_model_params* p, const float* x_nom, const float* u_nom, const float* K,

@@ -11,4 +11,4 @@ from .mpc import BatchedMPC, CartPoleMPC, ControllerSwitcher, QuadrotorMPC  # no
 from .transformer import TransformerILQR  # noqa: F401,E402
 from . import datagen, training  # noqa: F401,E402
 from . import autograd  # noqa: F401,E402
-from .autograd import trajectory_cost  # noqa: F401,E402
+from .autograd import tracking_cost, trajectory_cost  # noqa: F401,E402

@@ -11,7 +11,12 @@ N = 50.  autograd.release_placeholders() gives them back.
 The rows -- model_phys, weights, targets -- are differentiable too where they are passed as torch tensors that require a gradient:
 the backward pass then adds ONE ops.cost_param_gradient launch on the costate of the adjoint sweep (system identification, weight
 tuning, goal optimisation; the built-in models and user models compiled with param_grad=True).  Without such a tensor nothing changes: the same launches, the same bits.
+
+tracking_cost(model, x0, x_nom, u_nom, K) is the cost of the run the gain law u = u_nom + K (x - x_nom) produces on a plant (ops.track
++ ops.score); its backward pass is ONE ops.track_gradient launch: gradients for the gains, the nominal, the start and the disturbance,
+and through one ops.cost_param_gradient launch on the closed-loop costate for the plant's parameters, the weights and the targets.
 """
+import numpy as np
 import torch
 
 from . import ops
@@ -166,3 +171,106 @@ def trajectory_cost(model, x0, u, targets=None, weights=None, model_phys=None):
     detach = lambda t: t.detach() if isinstance(t, torch.Tensor) else t
     rows_in = tuple(r if _wants_grad(r) else None for r in rows_in)
     return _TrajectoryCostRows.apply(x0, u, *rows_in, model, detach(targets), detach(weights), detach(model_phys))
+
+
+class _TrackingCost(torch.autograd.Function):
+    """tracking_cost: ops.track + ops.score forward, one ops.track_gradient launch backward, and one ops.cost_param_gradient launch
+    more on the closed-loop costate where a row asks for a gradient."""
+
+    @staticmethod
+    def forward(ctx, x0, x_nom, u_nom, K, disturbance, row_phys, row_weights, row_targets, model, steps, plant, plant_phys, targets,
+                weights, terminal, feedback):
+        c = lambda t: t.detach().contiguous()
+        x_nomd, Kd = c(x_nom), c(K)
+        dist = None if disturbance is None else c(disturbance)
+        x, u = ops.track(model, c(x0), x_nomd, c(u_nom), Kd, steps, plant=plant, plant_phys=plant_phys, feedback=feedback,
+                         disturbance=dist)
+        cost, _ = ops.score(model, x, u, targets=targets, weights=weights, model_phys=plant_phys, terminal=terminal, ref_hold=1,
+                            want_stage=False)
+        ctx.save_for_backward(x, u, x_nomd, Kd)
+        ctx.call = (model, plant, plant_phys, targets, weights, terminal, feedback)
+        ctx.like = tuple(None if r is None else (tuple(r.shape), r.dtype, r.device) for r in (row_phys, row_weights, row_targets))
+        return cost
+
+    @staticmethod
+    def backward(ctx, grad_cost):
+        x, u, x_nom, K = ctx.saved_tensors
+        model, plant, plant_phys, targets, weights, terminal, feedback = ctx.call
+        want_x0, want_xn, want_un, want_K, want_d, want_phys, want_w, want_t = ctx.needs_input_grad[:8]
+        like_phys, like_w, like_t = ctx.like
+        n, m = model.n, model.m
+        want = tuple(name for name, on in (("K", want_K and feedback), ("x_nom", want_xn and feedback), ("x0", want_x0)) if on)
+        g = ops.track_gradient(model, x, u, x_nom if feedback else None, K if feedback else None, plant=plant, plant_phys=plant_phys,
+                               targets=targets, weights=weights, terminal=terminal, want=want, want_costate=want_d or want_phys)
+        w = grad_cost.to(torch.float32)
+        grad_x0 = g["grad_x0"] * w[:, None] if want_x0 else None
+        grad_xn = g["grad_x_nom"] * w[:, None, None] if "x_nom" in want else None
+        grad_un = None
+        if want_un:
+            grad_un = g["grad_u_nom"] * w[:, None, None]
+            if grad_un.shape[1] < K.shape[1]:       # feedback off: the entry was not told N, and the rows past `steps` are zero
+                grad_un = torch.cat([grad_un, grad_un.new_zeros((grad_un.shape[0], K.shape[1] - grad_un.shape[1], m))], dim=1)
+        grad_K = g["grad_K"] * w[:, None, None, None] if "K" in want else None
+        grad_d = (g["costate"][:, 1:] * w[:, None, None]).transpose(0, 1).contiguous() if want_d else None
+        rows = tuple(name for name, on in (("phys", want_phys), ("weights", want_w), ("targets", want_t)) if on)
+        grad_phys = grad_w = grad_t = None
+        if rows:
+            # the rows' gradient of the tracked cost: the open-loop kernel on the realised run (N = steps), under the plant's integrator
+            # and parameters, with the CLOSED-LOOP costate as the multiplier
+            pm = model if plant is None else model.with_(integrator=plant.integrator, phys=tuple(plant.phys))
+            pg = ops.cost_param_gradient(pm, x, u, targets=targets, weights=weights, model_phys=plant_phys, want=rows,
+                                         costate=g["costate"] if want_phys else None)
+            w64 = grad_cost.to(torch.float64)
+            if want_phys:
+                grad_phys = _row_grad(pg["grad_phys"] * w64[:, None], like_phys, (8, list(range(len(model.phys)))))
+            if want_w:
+                MX = ops._lib.MAX_NX
+                cols = list(range(n)) + list(range(MX, MX + n)) + list(range(2 * MX, 2 * MX + m))
+                grad_w = _row_grad(pg["grad_weights"] * w64[:, None], like_w, (ops.COST_ROW_FLOATS, cols))
+            if want_t:
+                grad_t = _row_grad(pg["grad_targets"] * w64[:, None, None], like_t)
+        return (grad_x0, grad_xn, grad_un, grad_K, grad_d, grad_phys, grad_w, grad_t) + (None,) * 8
+
+
+def tracking_cost(model, x0, x_nom, u_nom, K, steps=None, plant=None, plant_phys=None, disturbance=None, targets=None, weights=None,
+                  terminal=True, feedback=True):
+    """The cost of a tracked closed-loop run, per trajectory: x0 (B, n), x_nom (B, N+1, n), u_nom (B, N, m), K (B, N, m, n), float32
+    device tensors -> cost (B,) float64, differentiable with respect to x0, x_nom, u_nom, K and disturbance (steps, B, n).
+      forward   ops.track(model, x0, x_nom, u_nom, K, steps, plant=, plant_phys=, feedback=, disturbance=) -- `steps` <= N plant steps
+                (None: N) of u = u_nom[t] + K[t] (x - x_nom[t]) -- followed by ops.score(..., terminal=terminal, ref_hold=1,
+                model_phys=plant_phys) on the realised run under targets and weights
+      backward  ONE ops.track_gradient launch on the saved run, scaled per trajectory by the incoming gradient (cast to float32); rows
+                of x_nom, u_nom and K past `steps` receive zero; the disturbance's gradient is the closed-loop costate[:, 1:]
+    A feed-forward k or a line-search step alpha is a torch expression in front of u_nom and K (u_nom + alpha * k, alpha * K): torch's
+    chain rule covers it.  With feedback=False the cost does not depend on x_nom and K, which receive no gradient.
+    plant_phys, weights, targets that are torch tensors requiring a gradient receive dJ/d(row) as in trajectory_cost: one
+    ops.cost_param_gradient launch more, on the closed-loop costate, under the plant's integrator (the built-in models and user models
+    compiled with param_grad=True; NotImplementedError from the backward pass of any other user-compiled model).  That kernel always
+    includes the terminal slot, so terminal=False together with such a row raises NotImplementedError here.  Without such a tensor no
+    extra launch is made.  A plant with parameters of its own and no plant_phys rows: a user model's cost that reads P is scored with
+    the model's parameters but differentiated with the plant's (the built-in costs read none)."""
+    if not hasattr(u_nom, "shape") or len(u_nom.shape) != 3:
+        raise ValueError(f"u_nom must have shape (B, N, m) (got {tuple(np.shape(u_nom))})")
+    Bt, N = int(u_nom.shape[0]), int(u_nom.shape[1])
+    steps = N if steps is None else int(steps)
+    if not 1 <= steps <= N:
+        raise ValueError("steps must be in 1..N")
+    rows_in = (plant_phys, None if isinstance(weights, dict) else weights, targets)
+    if any(_wants_grad(r) for r in rows_in) and not terminal:
+        raise NotImplementedError("tracking_cost(terminal=False) cannot differentiate plant_phys, weights or targets: "
+                                  "ops.cost_param_gradient always includes the terminal slot")
+    if disturbance is not None and tuple(disturbance.shape) != (steps, Bt, model.n):
+        raise ValueError(f"disturbance must have shape {(steps, Bt, model.n)} (got {tuple(disturbance.shape)})")
+    ops.check_plant(model, plant)
+    ops.check_phys_rows(model, plant_phys, Bt, "plant_phys")
+    ops.check_ref_rows(model, targets, Bt, name="targets")
+    ops.check_cost_rows(model, weights, Bt, name="weights")
+    if u_nom.is_cuda:
+        with torch.no_grad():
+            plant_phys = ops.plant_phys_tensor(model, plant_phys, Bt, u_nom.device)
+            targets = ops.x_ref_rows_tensor(model, targets, Bt, u_nom.device, name="targets")
+            weights = ops.cost_rows_tensor(model, weights, Bt, u_nom.device, name="weights")
+    detach = lambda t: t.detach() if isinstance(t, torch.Tensor) else t
+    rows_in = tuple(r if _wants_grad(r) else None for r in rows_in)
+    return _TrackingCost.apply(x0, x_nom, u_nom, K, disturbance, *rows_in, model, steps, plant, detach(plant_phys), detach(targets),
+                               detach(weights), bool(terminal), bool(feedback))

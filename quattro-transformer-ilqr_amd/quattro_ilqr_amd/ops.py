@@ -848,6 +848,76 @@ def track(model, x0, x_nom, u_nom, K, steps, plant=None, plant_phys=None, feedba
     return x, u
 
 
+TRACK_GRADIENT_WANTS = ("K", "x_nom", "x0")
+
+
+def track_gradient(model, x, u, x_nom=None, K=None, plant=None, plant_phys=None, targets=None, weights=None, terminal=True,
+                   want=TRACK_GRADIENT_WANTS, want_costate=False):
+    """Gradient of the tracked closed-loop cost on the device (quattro_track_gradient_f32): S steps of ops.track,
+    u_t = u_nom_t + K_t (x_t - x_nom_t), x_{t+1} = f_plant(x_t, u_t) + d_t, scored by ops.score(..., ref_hold=1, terminal=terminal),
+    about the realised x (B, S+1, n), u (B, S, m) that ops.track returned.  x_nom (B, N+1, n), K (B, N, m, n), N >= S: the arrays
+    that call was given; K None: the feedback was off (x_nom is then not looked at, and "grad_K" and "grad_x_nom" are not returned:
+    the cost does not depend on either).
+    -> dict of float32 device tensors: "grad_u_nom" (B, N, m) always, and by `want`: "K" -> "grad_K" (B, N, m, n) = g_t (x_t - x_nom_t)^T,
+    "x_nom" -> "grad_x_nom" (B, N+1, n) = -K_t^T g_t, "x0" -> "grad_x0" (B, n); want_costate: "costate" (B, S+1, n), the closed-loop
+    costate (costate[:, t+1] is the gradient with respect to the disturbance of step t, and the multiplier ops.cost_param_gradient
+    takes for the plant-parameter gradient of the tracked cost).  Rows t >= S of the full-shape outputs are +0.0.  With K None and
+    N taken as S, "grad_u_nom" is ops.cost_gradient's "grad_u".
+    plant / plant_phys: as ops.track takes them; the struct the entry is given carries the model's cost fields and the plant's
+    integrator and phys (which a user model's cost bodies then see too).  targets, weights: as ops.cost_gradient takes them.
+    ValueError for a wrong shape or an unknown entry of `want`, before anything touches the device."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    unknown = [w for w in want if w not in TRACK_GRADIENT_WANTS]
+    if unknown:
+        raise ValueError(f"want may name {list(TRACK_GRADIENT_WANTS)} (got {list(want)})")
+    if len(np.shape(x)) != 3 or len(np.shape(u)) != 3:
+        raise ValueError(f"x must have shape (B, S + 1, n) and u (B, S, m) (got {tuple(np.shape(x))} and {tuple(np.shape(u))})")
+    Bt, S, m = (int(v) for v in u.shape)
+    n = model.n
+    if Bt < 1 or S < 1 or m != model.m or tuple(x.shape) != (Bt, S + 1, n):
+        raise ValueError(f"x must have shape (B, S + 1, {n}) and u (B, S, {model.m}) with B, S >= 1 "
+                         f"(got {tuple(x.shape)} and {tuple(u.shape)})")
+    if K is None:
+        want = tuple(w for w in want if w == "x0")          # nothing depends on K or x_nom
+        N = S
+    else:
+        kshape = tuple(np.shape(K))
+        if len(kshape) != 4 or kshape[0] != Bt or kshape[1] < S or kshape[2:] != (m, n):
+            raise ValueError(f"K must have shape ({Bt}, N, {m}, {n}) with N >= {S} (got {kshape})")
+        N = int(kshape[1])
+        if x_nom is None or tuple(np.shape(x_nom)) != (Bt, N + 1, n):
+            raise ValueError(f"x_nom must have shape {(Bt, N + 1, n)} (got {None if x_nom is None else tuple(np.shape(x_nom))})")
+    check_plant(model, plant)
+    check_phys_rows(model, plant_phys, Bt, "plant_phys")
+    check_ref_rows(model, targets, Bt, name="targets")
+    check_cost_rows(model, weights, Bt, name="weights")
+    f32 = torch.float32
+    _req(x, (Bt, S + 1, n), f32, "x"); _req(u, (Bt, S, m), f32, "u")
+    if K is not None:
+        _req(K, (Bt, N, m, n), f32, "K"); _req(x_nom, (Bt, N + 1, n), f32, "x_nom")
+    dev = u.device
+    pphys = plant_phys_tensor(model, plant_phys, Bt, dev)
+    rows = x_ref_rows_tensor(model, targets, Bt, dev, name="targets")
+    cost_rows = cost_rows_tensor(model, weights, Bt, dev, name="weights")
+    out = {"grad_u_nom": torch.empty((Bt, N, m), dtype=f32, device=dev)}
+    if "K" in want:
+        out["grad_K"] = torch.empty((Bt, N, m, n), dtype=f32, device=dev)
+    if "x_nom" in want:
+        out["grad_x_nom"] = torch.empty((Bt, N + 1, n), dtype=f32, device=dev)
+    if "x0" in want:
+        out["grad_x0"] = torch.empty((Bt, n), dtype=f32, device=dev)
+    if want_costate:
+        out["costate"] = torch.empty((Bt, S + 1, n), dtype=f32, device=dev)
+    # the cost fields of the model, the integrator and phys of the plant
+    p = (model if plant is None else model.with_(integrator=plant.integrator, phys=tuple(plant.phys))).c_params()
+    check(_lib.load_for(model).quattro_track_gradient_f32(
+        ctypes.byref(p), _ptr(x), _ptr(u), Bt, N, S, _ptr(x_nom) if K is not None else None, _ptr(K), _ptr(pphys), _ptr(rows),
+        0 if rows is None else rows.shape[1], _ptr(cost_rows), _lib.SCORE_TERMINAL if terminal else 0, _ptr(out["grad_u_nom"]),
+        _ptr(out.get("grad_K")), _ptr(out.get("grad_x_nom")), _ptr(out.get("grad_x0")), _ptr(out.get("costate")), _stream()),
+        "quattro_track_gradient_f32")
+    return out
+
+
 def _mpc_args(model, x_cur, x_nom, u_nom, K, k, cost, tol, max_iter, n_steps, workspace, traj_x, traj_u, traj_iters, disturbance,
               alphas, reg, alpha_idx, active, iters, status):
     """-> (the arguments the three MPC entries share, in the order of quattro_mpc_run_f32 without its stream; what they point to,

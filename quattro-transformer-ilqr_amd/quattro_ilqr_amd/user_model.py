@@ -68,6 +68,16 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 #  functions as the stand-alone kernels and must round like them to reproduce the host-driven loop bit for bit)
 _UNITS = {u: ["-ffp-contract=off"] for u in ("capi", "linearize", "rollout", "cost_gradient", "sweep_generic", "solve_user")}
 _UNITS["solve_user"] = _UNITS["solve_user"] + ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]      # (the tile sweep's accumulators: Makefile)
+# the unit of the tracked closed-loop cost's gradient (quattro_track_gradient_f32): in every library like the ones above, named on its
+# own because the six entries of _UNITS are held fixed by a test of the plain build list
+_TRACK_UNIT = "track_gradient"
+
+
+def _all_units():
+    """Every translation unit of a plain user-model library with its flags."""
+    return {**_UNITS, _TRACK_UNIT: ["-ffp-contract=off"]}
+
+
 # the unit of compile_model(..., param_grad=True) alone (kept out of _UNITS: a plain library is built from the same units as ever)
 _PARAM_GRAD_UNIT = "user_param_gradient"
 _PARAM_GRAD_RULE = ("param_grad=True: a local that holds a parameter or a weight (P[k], p.q[i], p.qf[i], p.r[a], p.x_ref[i]) must be "
@@ -148,7 +158,7 @@ def _toolchain_id():
             abi = str(_lib.load().quattro_version())
         except Exception:           # (the main library is missing: build_library says so itself)
             abi = "no main library"
-        _TOOLCHAIN = hashlib.sha1(f"{ver}\n{_FLAGS}\n{sorted(_UNITS.items())}\n{abi}".encode()).hexdigest()
+        _TOOLCHAIN = hashlib.sha1(f"{ver}\n{_FLAGS}\n{sorted(_all_units().items())}\n{abi}".encode()).hexdigest()
     return _TOOLCHAIN
 
 
@@ -159,7 +169,7 @@ def _sources_digest(param_grad=False):
         return None
     h = hashlib.sha1()
     for fn in sorted(os.listdir(CSRC)):
-        if fn.endswith((".h", ".hip")) and (fn.endswith(".h") or fn[:-4] in _UNITS or (param_grad and fn[:-4] == _PARAM_GRAD_UNIT)):
+        if fn.endswith((".h", ".hip")) and (fn.endswith(".h") or fn[:-4] in _all_units() or (param_grad and fn[:-4] == _PARAM_GRAD_UNIT)):
             with open(os.path.join(CSRC, fn), "rb") as f:
                 h.update(fn.encode()); h.update(f.read())
     with open(os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "quattro_hip.h"), "rb") as f:
@@ -193,7 +203,7 @@ def build_library(name, n, m, header_text, verbose=False, param_grad=None):
         if so is None:
             raise _lib.QuattroError(f"user model {name!r}: no cached library and no kernel sources at {CSRC} to build one from")
         return so
-    units = dict(_UNITS)
+    units = _all_units()
     defs_pg = []
     if param_grad is not None:
         units[_PARAM_GRAD_UNIT] = ["-ffp-contract=off"]
