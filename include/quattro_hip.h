@@ -777,6 +777,56 @@ int quattro_tf_train_step_f32(const quattro_tf_train_desc* desc, const float* pa
                               const float* target_norm, const float* pe, int batch, uint64_t dropout_seed, int training,
                               float* loss, float* pred_out, void* stream);
 
+/* The backward half of quattro_tf_train_step_f32 on its own, started from a gradient the caller supplies: the gradient of ANY scalar
+ * with respect to the normalised prediction, not only the MSE's.  It is the backward of the mini-batch whose forward last filled
+ * this workspace, i.e. of quattro_tf_train_step_f32(desc, params, grads = NULL, workspace, ..., pred_out != NULL, ...) with the same
+ * desc, params, x_norm, prompt_norm, batch, dropout_seed and training flag (the dropout masks are recomputed from the seed; the saved
+ * activations are read from the workspace, which nothing may have written in between).
+ *   d_pred [B][T][c]     : d(scalar) / d(pred_out)
+ *   grads                : flat gradient array, overwritten, as the step overwrites it
+ * The step itself is forward half, MSE kernel, this backward half on its own d_pred buffer: the same launches in the same order.
+ * Return codes as the step's: QUATTRO_ERR_BAD_ARG (a NULL pointer, batch <= 0), QUATTRO_ERR_UNSUPPORTED (shape),
+ * QUATTRO_ERR_WORKSPACE, QUATTRO_ERR_LAUNCH.                                                                             */
+int quattro_tf_train_backward_f32(const quattro_tf_train_desc* desc, const float* params, float* grads, void* workspace,
+                                  size_t workspace_bytes, const float* x_norm, const float* prompt_norm, const float* d_pred,
+                                  int batch, uint64_t dropout_seed, int training, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Task loss of the gain predictor: between its output tokens and the gain stacks of a tracked run (csrc/tf_gain_loss.hip).
+ * A training step on the closed-loop cost of the predicted gains is: quattro_tf_train_step_f32 (grads = NULL, pred_out),
+ * quattro_tf_gains_unpack_f32, quattro_track_f32 (K_out, u_ff), quattro_score_f32, quattro_track_gradient_f32 (grad_K, grad_u_nom),
+ * quattro_tf_gains_pack_grad_f32, quattro_tf_train_backward_f32.
+ * Token layout, c = m (1 + n): element i (1 + n) is the feed-forward k_i, element i (1 + n) + 1 + j the gain K_ij -- the data set's
+ * layout (what quattro_tf_gains_* unpack), NOT the solver's prompt layout [k | K.flat].  Tn = min(T, N).
+ * Every fp32 value below is formed by the single rounded operations written, in that order, never contracted to an FMA.
+ *
+ * unpack:   raw = pred_norm * u_std[e] + u_mean[e]                       (product, then sum)
+ *           K_out[b][t] = t < Tn ? raw gains of token t : K_log[b][t]
+ *           u_ff[b][t]  = u_nom[b][t] + alpha * (t < Tn ? raw k of token t : k_log[b][t])      (product, then sum)
+ *   pred_norm [B][T][c]; u_mean, u_std [c]; K_log, K_out [B][N][m][n]; k_log, u_nom, u_ff [B][N][m].  Outputs must not alias inputs.
+ *
+ * pack_grad: with f_b = (float)((double)task_weight * (scale ? scale[b] : 1) / B), for rows t < Tn
+ *           d_pred[b][t][i (1 + n)]         = ((grad_u_nom[b][t][i] * alpha) * f_b) * u_std[e]
+ *           d_pred[b][t][i (1 + n) + 1 + j] = (grad_K[b][t][i][j] * f_b) * u_std[e]
+ *           rows Tn <= t < T are +0.0 (predicted rows that no step uses); with mse_weight != 0 every row additionally receives
+ *           mse_weight * ((2 * (pred_norm - target_norm)) * (1.0f / (float)(B T c)))             (the MSE kernel's gradient)
+ *           terms[b] = ((double)task_weight * scale[b] * cost[b]) / B + mse_weight * (sum over the block of (pred - target)^2, fp64) / (B T c)
+ *           loss = terms[0] + terms[1] + ... + terms[B - 1], fp64, in that order (one lane: no atomics, the same on every run)
+ *   A trajectory whose cost, factor f_b or any element of grad_K[b], grad_u_nom[b] is not finite is left out: diverged[b] = 1, its
+ *   whole block of d_pred is +0.0 and terms[b] = 0; this is decided by a vote of the one wave that owns the trajectory before it
+ *   writes anything.  Otherwise diverged[b] = 0.
+ *   grad_K [B][N][m][n], grad_u_nom [B][N][m] : what quattro_track_gradient_f32 wrote;  cost [B] fp64 : quattro_score_f32's totals
+ *   scale [B] or NULL (= 1); pred_norm, target_norm [B][T][c] : read only with mse_weight != 0 (QUATTRO_ERR_BAD_ARG if then NULL)
+ *   d_pred [B][T][c], diverged [B], terms [B] fp64, loss [1] fp64 : outputs
+ * Both: QUATTRO_ERR_BAD_ARG for a NULL pointer (other than the optional ones) or B, T, N, n, m <= 0.                    */
+int quattro_tf_gains_unpack_f32(const float* pred_norm, const float* u_mean, const float* u_std, const float* K_log,
+                                const float* k_log, const float* u_nom, float alpha, int B, int T, int N, int n, int m,
+                                float* K_out, float* u_ff, void* stream);
+int quattro_tf_gains_pack_grad_f32(const float* grad_K, const float* grad_u_nom, const double* cost, const float* scale,
+                                   const float* u_std, float alpha, float task_weight, const float* pred_norm,
+                                   const float* target_norm, float mse_weight, int B, int T, int N, int n, int m, float* d_pred,
+                                   int32_t* diverged, double* terms, double* loss, void* stream);
+
 /* torch.optim.Adam with its defaults as the reference uses it (transformer_ilqr.py:140; no weight decay, bias-corrected
  * moments), over the flat arrays; `step` counts from 1.                                                               */
 int quattro_tf_adam_f32(float* params, const float* grads, float* m, float* v, size_t n, float lr, float beta1, float beta2,

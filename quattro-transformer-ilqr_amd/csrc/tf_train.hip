@@ -17,6 +17,10 @@
 //
 // Dropout masks are a counter hash of (seed, site, element index), recomputed wherever they are needed (forward and
 // backward see the same mask without storing it); quattro_tf_train_dropout_mask_f32 materialises one for tests.
+//
+// The step is written as two halves, train_forward and train_backward, with the MSE kernel between them.  quattro_tf_train_backward_f32
+// is the backward half on its own, started from a gradient d(scalar)/d(pred) the caller supplies (a task loss: csrc/tf_gain_loss.hip)
+// after a forward-only call of the step has filled the workspace.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -781,6 +785,125 @@ Ws carve(const quattro_tf_train_desc& D, int Bn, char* base) {
 size_t attn_mfma_fwd_lds() { return (size_t)(3 * LP * HDP + 4 * 32 * HDP) * sizeof(float); }
 size_t attn_mfma_bwd_lds() { return (size_t)(4 * LP * HDP + 4 * 32 * HDP + 3 * LP) * sizeof(float); }
 
+// the attention kernels' dynamic LDS exceeds the default limit: raised before the first launch of a call
+void raise_attn_lds() {
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                      (int)attn_mfma_fwd_lds());
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                      (int)attn_mfma_bwd_lds());
+}
+
+// The two halves of the step.  Both carve the same workspace for (D, batch): the forward half leaves every saved activation there,
+// the backward half reads them and the gradient `dpred` [B T][c] of a scalar with respect to the normalised prediction.
+void train_forward(const quattro_tf_train_desc& D, const float* params, void* workspace, const float* x_norm,
+                   const float* prompt_norm, const float* pe, int batch, uint64_t dropout_seed, int training, float* pred,
+                   hipStream_t st) {
+  const ParamOff po = param_offsets(D);
+  const Ws w = carve(D, batch, reinterpret_cast<char*>(workspace));
+  const int Bn = batch, NS = D.n_state_tok, P = D.prompt_len, T = D.target_len, L = NS + P + T, M = Bn * L, Mt = Bn * T;
+  const int d = D.d_model, ff = D.d_ff, c = D.control_dim, n = D.state_dim, H = D.nhead;
+  const int hd = d / H;
+  const float scale = 1.0f / sqrtf((float)hd);
+  Drop dr;
+  dr.seed = dropout_seed;
+  dr.p = (training && D.dropout > 0.0f) ? D.dropout : 0.0f;
+  dr.inv_keep = 1.0f / (1.0f - dr.p);
+  auto site = [](int layer, int kind) { return (uint32_t)(1 + 4 * layer + kind); };   // 0: positions; per layer: attention
+                                                                                       // weights, out-proj, ff hidden, ff out
+  // ---------------------------------------------------------------- forward
+  linear_fwd(st, x_norm, params + po.ws, params + po.bs, w.xe, Bn * NS, d, n);
+  linear_fwd(st, prompt_norm, params + po.wc, params + po.bc, w.ue, Bn * P, d, c);
+  hipLaunchKernelGGL(embed_fwd_kernel, dim3(ew_blocks((long)M * d)), dim3(256), 0, st, w.xe, w.ue, params + po.tgt, pe, w.h0, Bn,
+                     NS, P, T, d, dr);
+  const float* hin = w.h0;
+  for (int l = 0; l < D.n_layers; ++l) {
+    const LayerOff& q = po.layer[l];
+    const LayerWs& a = w.layer[l];
+    linear_fwd(st, hin, params + q.wqkv, params + q.bqkv, a.qkv, M, 3 * d, d);
+    hipLaunchKernelGGL(attn_fwd_mfma_kernel, dim3(H, Bn), dim3(256), attn_mfma_fwd_lds(), st, a.qkv, a.P, a.ao, L, d, H, hd, scale, dr,
+                       site(l, 0));
+    linear_fwd(st, a.ao, params + q.wo, params + q.bo, a.o, M, d, d);
+    hipLaunchKernelGGL(ln_fwd_kernel, dim3((M + 3) / 4), dim3(256), 0, st, hin, a.o, a.s1, a.h1, a.mean1, a.rstd1,
+                       params + q.g1, params + q.be1, M, d, dr, site(l, 1));
+    linear_fwd(st, a.h1, params + q.w1, params + q.b1, a.f1, M, ff, d);
+    hipLaunchKernelGGL(relu_drop_kernel, dim3(ew_blocks((long)M * ff)), dim3(256), 0, st, a.f1, (long)M * ff, dr, site(l, 2));
+    linear_fwd(st, a.f1, params + q.w2, params + q.b2, a.f2, M, d, ff);
+    hipLaunchKernelGGL(ln_fwd_kernel, dim3((M + 3) / 4), dim3(256), 0, st, a.h1, a.f2, a.s2, a.h2, a.mean2, a.rstd2,
+                       params + q.g2, params + q.be2, M, d, dr, site(l, 3));
+    hin = a.h2;
+  }
+  hipLaunchKernelGGL(tail_gather_kernel, dim3(ew_blocks((long)Mt * d)), dim3(256), 0, st, hin, w.tail, Bn, L, T, d);
+  linear_fwd(st, w.tail, params + po.wout, params + po.bout, pred, Mt, c, d);
+}
+
+void train_backward(const quattro_tf_train_desc& D, const float* params, float* grads, void* workspace, const float* x_norm,
+                    const float* prompt_norm, const float* dpred, int batch, uint64_t dropout_seed, int training,
+                    hipStream_t st) {
+  const ParamOff po = param_offsets(D);
+  const Ws w = carve(D, batch, reinterpret_cast<char*>(workspace));
+  const int Bn = batch, NS = D.n_state_tok, P = D.prompt_len, T = D.target_len, L = NS + P + T, M = Bn * L, Mt = Bn * T;
+  const int d = D.d_model, ff = D.d_ff, c = D.control_dim, n = D.state_dim, H = D.nhead;
+  const int hd = d / H;
+  const float scale = 1.0f / sqrtf((float)hd);
+  Drop dr;
+  dr.seed = dropout_seed;
+  dr.p = (training && D.dropout > 0.0f) ? D.dropout : 0.0f;
+  dr.inv_keep = 1.0f / (1.0f - dr.p);
+  auto site = [](int layer, int kind) { return (uint32_t)(1 + 4 * layer + kind); };   // 0: positions; per layer: attention
+                                                                                       // weights, out-proj, ff hidden, ff out
+  const bool dropping = dr.p > 0.0f;
+  // ---------------------------------------------------------------- backward
+  (void)hipMemsetAsync(grads, 0, (size_t)po.total * sizeof(float), st);
+  linear_bwd_weight(st, dpred, w.tail, grads + po.wout, grads + po.bout, Mt, c, d);
+  linear_bwd_input(st, dpred, params + po.wout, w.dtail, Mt, c, d, false);
+  hipLaunchKernelGGL(tail_scatter_kernel, dim3(ew_blocks((long)M * d)), dim3(256), 0, st, w.dtail, w.dh, Bn, L, T, d);
+  for (int l = D.n_layers - 1; l >= 0; --l) {
+    const LayerOff& q = po.layer[l];
+    const LayerWs& a = w.layer[l];
+    const float* lin = l == 0 ? w.h0 : w.layer[l - 1].h2;
+    // LayerNorm 2: dh -> ds2 (in dtmp); s2 = h1 + drop(f2)
+    hipLaunchKernelGGL(ln_bwd_kernel, dim3((M + LN_BWD_ROWS - 1) / LN_BWD_ROWS), dim3(256), 0, st, w.dh, a.s2, a.mean2, a.rstd2, params + q.g2, w.dtmp,
+                       w.lnpart, M, d);
+    hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3((2 * d + 255) / 256, LN_RED_SLICES), dim3(256), 0, st, w.lnpart, (M + LN_BWD_ROWS - 1) / LN_BWD_ROWS, d, grads + q.g2,
+                       grads + q.be2);
+    const float* df2 = w.dtmp;
+    if (dropping) {
+      hipLaunchKernelGGL(drop_bwd_kernel, dim3(ew_blocks((long)M * d)), dim3(256), 0, st, w.dbranch, w.dtmp, (long)M * d, dr,
+                         site(l, 3));
+      df2 = w.dbranch;
+    }
+    linear_bwd_weight(st, df2, a.f1, grads + q.w2, grads + q.b2, M, d, ff);
+    linear_bwd_input(st, df2, params + q.w2, w.df, M, d, ff, false);
+    hipLaunchKernelGGL(relu_drop_bwd_kernel, dim3(ew_blocks((long)M * ff)), dim3(256), 0, st, w.df, a.f1, (long)M * ff,
+                       dr.inv_keep);
+    linear_bwd_weight(st, w.df, a.h1, grads + q.w1, grads + q.b1, M, ff, d);
+    // dh1 = ds2 (residual) + da1 W1
+    linear_bwd_input(st, w.df, params + q.w1, w.dtmp, M, ff, d, true);
+    // LayerNorm 1: dh1 (dtmp) -> ds1 (dh); s1 = hin + drop(o)
+    hipLaunchKernelGGL(ln_bwd_kernel, dim3((M + LN_BWD_ROWS - 1) / LN_BWD_ROWS), dim3(256), 0, st, w.dtmp, a.s1, a.mean1, a.rstd1, params + q.g1, w.dh,
+                       w.lnpart, M, d);
+    hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3((2 * d + 255) / 256, LN_RED_SLICES), dim3(256), 0, st, w.lnpart, (M + LN_BWD_ROWS - 1) / LN_BWD_ROWS, d, grads + q.g1,
+                       grads + q.be1);
+    const float* dob = w.dh;
+    if (dropping) {
+      hipLaunchKernelGGL(drop_bwd_kernel, dim3(ew_blocks((long)M * d)), dim3(256), 0, st, w.dbranch, w.dh, (long)M * d, dr,
+                         site(l, 1));
+      dob = w.dbranch;
+    }
+    linear_bwd_weight(st, dob, a.ao, grads + q.wo, grads + q.bo, M, d, d);
+    linear_bwd_input(st, dob, params + q.wo, w.dao, M, d, d, false);
+    hipLaunchKernelGGL(attn_bwd_mfma_kernel, dim3(H, Bn), dim3(256), attn_mfma_bwd_lds(), st, a.qkv, a.P, a.ao, w.dao, w.dqkv, L, d,
+                       H, hd, scale, dr, site(l, 0));
+    linear_bwd_weight(st, w.dqkv, lin, grads + q.wqkv, grads + q.bqkv, M, 3 * d, d);
+    // d(lin) = ds1 (residual, in dh) + dqkv Wqkv
+    linear_bwd_input(st, w.dqkv, params + q.wqkv, w.dh, M, 3 * d, d, true);
+  }
+  hipLaunchKernelGGL(embed_bwd_kernel, dim3(ew_blocks((long)M * d)), dim3(256), 0, st, w.dh, w.dxe, w.due, grads + po.tgt, Bn, NS,
+                     P, T, d, dr);
+  linear_bwd_weight(st, w.dxe, x_norm, grads + po.ws, grads + po.bs, Bn * NS, d, n);
+  linear_bwd_weight(st, w.due, prompt_norm, grads + po.wc, grads + po.bc, Bn * P, d, c);
+}
+
 }  // namespace
 
 extern "C" {
@@ -835,107 +958,29 @@ int quattro_tf_train_step_f32(const quattro_tf_train_desc* D, const float* param
   if ((grads != nullptr || loss != nullptr) && !target_norm) return QUATTRO_ERR_BAD_ARG;
   if (((uintptr_t)workspace & 255) != 0 || workspace_bytes < carve(*D, batch, nullptr).total) return QUATTRO_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const ParamOff po = param_offsets(*D);
+  raise_attn_lds();
   const Ws w = carve(*D, batch, reinterpret_cast<char*>(workspace));
-  const int Bn = batch, NS = D->n_state_tok, P = D->prompt_len, T = D->target_len, L = NS + P + T, M = Bn * L, Mt = Bn * T;
-  const int d = D->d_model, ff = D->d_ff, c = D->control_dim, n = D->state_dim, H = D->nhead;
-  const int hd = d / H;
-  const float scale = 1.0f / sqrtf((float)hd);
-  Drop dr;
-  dr.seed = dropout_seed;
-  dr.p = (training && D->dropout > 0.0f) ? D->dropout : 0.0f;
-  dr.inv_keep = 1.0f / (1.0f - dr.p);
-  const bool dropping = dr.p > 0.0f;
-  auto site = [](int layer, int kind) { return (uint32_t)(1 + 4 * layer + kind); };   // 0: positions; per layer: attention
-                                                                                       // weights, out-proj, ff hidden, ff out
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                      (int)attn_mfma_fwd_lds());
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                      (int)attn_mfma_bwd_lds());
-
-  // ---------------------------------------------------------------- forward
-  linear_fwd(st, x_norm, params + po.ws, params + po.bs, w.xe, Bn * NS, d, n);
-  linear_fwd(st, prompt_norm, params + po.wc, params + po.bc, w.ue, Bn * P, d, c);
-  hipLaunchKernelGGL(embed_fwd_kernel, dim3(ew_blocks((long)M * d)), dim3(256), 0, st, w.xe, w.ue, params + po.tgt, pe, w.h0, Bn,
-                     NS, P, T, d, dr);
-  const float* hin = w.h0;
-  for (int l = 0; l < D->n_layers; ++l) {
-    const LayerOff& q = po.layer[l];
-    const LayerWs& a = w.layer[l];
-    linear_fwd(st, hin, params + q.wqkv, params + q.bqkv, a.qkv, M, 3 * d, d);
-    hipLaunchKernelGGL(attn_fwd_mfma_kernel, dim3(H, Bn), dim3(256), attn_mfma_fwd_lds(), st, a.qkv, a.P, a.ao, L, d, H, hd, scale, dr,
-                       site(l, 0));
-    linear_fwd(st, a.ao, params + q.wo, params + q.bo, a.o, M, d, d);
-    hipLaunchKernelGGL(ln_fwd_kernel, dim3((M + 3) / 4), dim3(256), 0, st, hin, a.o, a.s1, a.h1, a.mean1, a.rstd1,
-                       params + q.g1, params + q.be1, M, d, dr, site(l, 1));
-    linear_fwd(st, a.h1, params + q.w1, params + q.b1, a.f1, M, ff, d);
-    hipLaunchKernelGGL(relu_drop_kernel, dim3(ew_blocks((long)M * ff)), dim3(256), 0, st, a.f1, (long)M * ff, dr, site(l, 2));
-    linear_fwd(st, a.f1, params + q.w2, params + q.b2, a.f2, M, d, ff);
-    hipLaunchKernelGGL(ln_fwd_kernel, dim3((M + 3) / 4), dim3(256), 0, st, a.h1, a.f2, a.s2, a.h2, a.mean2, a.rstd2,
-                       params + q.g2, params + q.be2, M, d, dr, site(l, 3));
-    hin = a.h2;
-  }
-  hipLaunchKernelGGL(tail_gather_kernel, dim3(ew_blocks((long)Mt * d)), dim3(256), 0, st, hin, w.tail, Bn, L, T, d);
+  const long npred = (long)batch * D->target_len * D->control_dim;
   float* pred = pred_out ? pred_out : w.pred;
-  linear_fwd(st, w.tail, params + po.wout, params + po.bout, pred, Mt, c, d);
+  train_forward(*D, params, workspace, x_norm, prompt_norm, pe, batch, dropout_seed, training, pred, st);
   if (loss != nullptr || grads != nullptr) {
     float* lossp = loss ? loss : w.loss_pad;
     (void)hipMemsetAsync(lossp, 0, sizeof(float), st);
-    hipLaunchKernelGGL(mse_kernel, dim3(ew_blocks((long)Mt * c) > 256 ? 256 : ew_blocks((long)Mt * c)), dim3(256), 0, st, pred,
-                       target_norm, (long)Mt * c, grads ? w.dpred : nullptr, lossp);
+    hipLaunchKernelGGL(mse_kernel, dim3(ew_blocks(npred) > 256 ? 256 : ew_blocks(npred)), dim3(256), 0, st, pred, target_norm,
+                       npred, grads ? w.dpred : nullptr, lossp);
   }
-  if (grads == nullptr) return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;
+  if (grads != nullptr) train_backward(*D, params, grads, workspace, x_norm, prompt_norm, w.dpred, batch, dropout_seed, training, st);
+  return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;
+}
 
-  // ---------------------------------------------------------------- backward
-  (void)hipMemsetAsync(grads, 0, (size_t)po.total * sizeof(float), st);
-  linear_bwd_weight(st, w.dpred, w.tail, grads + po.wout, grads + po.bout, Mt, c, d);
-  linear_bwd_input(st, w.dpred, params + po.wout, w.dtail, Mt, c, d, false);
-  hipLaunchKernelGGL(tail_scatter_kernel, dim3(ew_blocks((long)M * d)), dim3(256), 0, st, w.dtail, w.dh, Bn, L, T, d);
-  for (int l = D->n_layers - 1; l >= 0; --l) {
-    const LayerOff& q = po.layer[l];
-    const LayerWs& a = w.layer[l];
-    const float* lin = l == 0 ? w.h0 : w.layer[l - 1].h2;
-    // LayerNorm 2: dh -> ds2 (in dtmp); s2 = h1 + drop(f2)
-    hipLaunchKernelGGL(ln_bwd_kernel, dim3((M + LN_BWD_ROWS - 1) / LN_BWD_ROWS), dim3(256), 0, st, w.dh, a.s2, a.mean2, a.rstd2, params + q.g2, w.dtmp,
-                       w.lnpart, M, d);
-    hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3((2 * d + 255) / 256, LN_RED_SLICES), dim3(256), 0, st, w.lnpart, (M + LN_BWD_ROWS - 1) / LN_BWD_ROWS, d, grads + q.g2,
-                       grads + q.be2);
-    const float* df2 = w.dtmp;
-    if (dropping) {
-      hipLaunchKernelGGL(drop_bwd_kernel, dim3(ew_blocks((long)M * d)), dim3(256), 0, st, w.dbranch, w.dtmp, (long)M * d, dr,
-                         site(l, 3));
-      df2 = w.dbranch;
-    }
-    linear_bwd_weight(st, df2, a.f1, grads + q.w2, grads + q.b2, M, d, ff);
-    linear_bwd_input(st, df2, params + q.w2, w.df, M, d, ff, false);
-    hipLaunchKernelGGL(relu_drop_bwd_kernel, dim3(ew_blocks((long)M * ff)), dim3(256), 0, st, w.df, a.f1, (long)M * ff,
-                       dr.inv_keep);
-    linear_bwd_weight(st, w.df, a.h1, grads + q.w1, grads + q.b1, M, ff, d);
-    // dh1 = ds2 (residual) + da1 W1
-    linear_bwd_input(st, w.df, params + q.w1, w.dtmp, M, ff, d, true);
-    // LayerNorm 1: dh1 (dtmp) -> ds1 (dh); s1 = hin + drop(o)
-    hipLaunchKernelGGL(ln_bwd_kernel, dim3((M + LN_BWD_ROWS - 1) / LN_BWD_ROWS), dim3(256), 0, st, w.dtmp, a.s1, a.mean1, a.rstd1, params + q.g1, w.dh,
-                       w.lnpart, M, d);
-    hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3((2 * d + 255) / 256, LN_RED_SLICES), dim3(256), 0, st, w.lnpart, (M + LN_BWD_ROWS - 1) / LN_BWD_ROWS, d, grads + q.g1,
-                       grads + q.be1);
-    const float* dob = w.dh;
-    if (dropping) {
-      hipLaunchKernelGGL(drop_bwd_kernel, dim3(ew_blocks((long)M * d)), dim3(256), 0, st, w.dbranch, w.dh, (long)M * d, dr,
-                         site(l, 1));
-      dob = w.dbranch;
-    }
-    linear_bwd_weight(st, dob, a.ao, grads + q.wo, grads + q.bo, M, d, d);
-    linear_bwd_input(st, dob, params + q.wo, w.dao, M, d, d, false);
-    hipLaunchKernelGGL(attn_bwd_mfma_kernel, dim3(H, Bn), dim3(256), attn_mfma_bwd_lds(), st, a.qkv, a.P, a.ao, w.dao, w.dqkv, L, d,
-                       H, hd, scale, dr, site(l, 0));
-    linear_bwd_weight(st, w.dqkv, lin, grads + q.wqkv, grads + q.bqkv, M, 3 * d, d);
-    // d(lin) = ds1 (residual, in dh) + dqkv Wqkv
-    linear_bwd_input(st, w.dqkv, params + q.wqkv, w.dh, M, 3 * d, d, true);
-  }
-  hipLaunchKernelGGL(embed_bwd_kernel, dim3(ew_blocks((long)M * d)), dim3(256), 0, st, w.dh, w.dxe, w.due, grads + po.tgt, Bn, NS,
-                     P, T, d, dr);
-  linear_bwd_weight(st, w.dxe, x_norm, grads + po.ws, grads + po.bs, Bn * NS, d, n);
-  linear_bwd_weight(st, w.due, prompt_norm, grads + po.wc, grads + po.bc, Bn * P, d, c);
+int quattro_tf_train_backward_f32(const quattro_tf_train_desc* D, const float* params, float* grads, void* workspace,
+                                  size_t workspace_bytes, const float* x_norm, const float* prompt_norm, const float* d_pred,
+                                  int batch, uint64_t dropout_seed, int training, void* stream) {
+  if (!desc_ok(D)) return D ? QUATTRO_ERR_UNSUPPORTED : QUATTRO_ERR_BAD_ARG;
+  if (!params || !grads || !workspace || !x_norm || !prompt_norm || !d_pred || batch <= 0) return QUATTRO_ERR_BAD_ARG;
+  if (((uintptr_t)workspace & 255) != 0 || workspace_bytes < carve(*D, batch, nullptr).total) return QUATTRO_ERR_WORKSPACE;
+  raise_attn_lds();
+  train_backward(*D, params, grads, workspace, x_norm, prompt_norm, d_pred, batch, dropout_seed, training, (hipStream_t)stream);
   return hipGetLastError() == hipSuccess ? QUATTRO_OK : QUATTRO_ERR_LAUNCH;
 }
 

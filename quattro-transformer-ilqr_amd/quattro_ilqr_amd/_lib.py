@@ -163,6 +163,10 @@ SIGNATURES = {
     "quattro_tf_train_workspace_bytes": (c_size_t, [POINTER(TfTrainDesc), c_int]),
     "quattro_tf_train_step_f32": (c_int, [POINTER(TfTrainDesc), _P, _P, _P, c_size_t, _P, _P, _P, _P, c_int, c_uint64,
                                           c_int, _P, _P, _P]),
+    "quattro_tf_train_backward_f32": (c_int, [POINTER(TfTrainDesc), _P, _P, _P, c_size_t, _P, _P, _P, c_int, c_uint64, c_int, _P]),
+    "quattro_tf_gains_unpack_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_float, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "quattro_tf_gains_pack_grad_f32": (c_int, [_P, _P, _P, _P, _P, c_float, c_float, _P, _P, c_float, c_int, c_int, c_int, c_int,
+                                               c_int, _P, _P, _P, _P, _P]),
     "quattro_tf_adam_f32": (c_int, [_P, _P, _P, _P, c_size_t, c_float, c_float, c_float, c_float, c_int, _P]),
     "quattro_tf_train_dropout_mask_f32": (c_int, [c_uint64, c_float, c_int, c_size_t, _P, _P]),
 }

@@ -108,6 +108,32 @@ def collect(solver, x0, u_init=None, max_iter=None, ring_bytes=1 << 30):
     return IterationLog(**{k: np.concatenate(v, axis=0) for k, v in chunks.items()})
 
 
+def nominal_controls(log, u_init=None):
+    """The nominal controls (E, N, m) that belong to each entry's x_seq, i.e. the controls whose rollout x_seq is and about which the
+    entry's k_seq, K_seq were swept.  The log's u_seq holds the controls AFTER the accept, so for iteration i > 0 of a trajectory they
+    are the previous entry's u_seq (unchanged by an iteration without found_update), and for iteration 0 they are u_init[traj]
+    (u_init (B, N, m): what collect() was given), or zeros, the solver's default.  ValueError for an entry with iteration > 0 whose
+    predecessor (same trajectory, iteration - 1) is not the entry before it: a log cut by select() no longer carries them."""
+    E = len(log)
+    out = np.zeros_like(np.asarray(log.u_seq))
+    if u_init is not None:
+        u_init = np.asarray(u_init, dtype=out.dtype)
+        if u_init.ndim != 3 or u_init.shape[1:] != out.shape[1:]:
+            raise ValueError(f"u_init must have shape (B, {out.shape[1]}, {out.shape[2]}) (got {u_init.shape})")
+    for e in range(E):
+        it, tr = int(log.iteration[e]), int(log.traj[e])
+        if it == 0:
+            if u_init is not None:
+                if not 0 <= tr < u_init.shape[0]:
+                    raise ValueError(f"entry {e}: trajectory {tr} has no row in u_init of shape {u_init.shape}")
+                out[e] = u_init[tr]
+        elif e == 0 or int(log.traj[e - 1]) != tr or int(log.iteration[e - 1]) != it - 1:
+            raise ValueError(f"entry {e} (trajectory {tr}, iteration {it}) does not follow its predecessor in the log")
+        else:
+            out[e] = log.u_seq[e - 1]
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ on-disk formats
 def to_entries(log):
     """IterationLog -> list of dicts shaped like the reference's log entries (fp64 arrays; u_seq/k_seq/K_seq as lists of

@@ -125,7 +125,9 @@ class TransformerILQR:
     def fit(self, df, test_df=None, num_epochs=50, batch_size=16, learning_rate=1e-3, patience=5, **kw):
         """transformer_ilqr.py:102-208 on the GPU (backend="hip": the hand-written training step of csrc/tf_train.hip, the
         default there; "torch": autograd); the trained weights are staged for the HIP inference kernel.  `df` may also be
-        a datagen.IterationLog or an (x_data, kK_data) pair."""
+        a datagen.IterationLog or an (x_data, kK_data) pair.  Further keywords go to training.fit: loss="tracking" with task=dict(...)
+        trains on the closed-loop cost of the predicted gains instead of the MSE, init= starts from a state dict or a loaded
+        predictor."""
         from . import training
         return training.fit(self, df, test_df, num_epochs, batch_size, learning_rate, patience, **kw)
 
