@@ -98,8 +98,7 @@ template <bool WITH_JAC>
 __device__ __forceinline__ CartpoleTerms cartpole_terms(const quattro_model_params& p, float th, float thd, float F) {
   const float M = p.phys[0], mp = p.phys[1], l = p.phys[2], g = p.phys[3];
   float s, c;
-  if constexpr (WITH_JAC) qt_sincos(th, &s, &c);
-  else qt_sincos_chain(th, &s, &c);              // (the rollouts; same bits)
+  qt_sincos_chain(th, &s, &c);                   // (rollouts and record kernels alike; qt_sincos' bits)
   const float mt = M + mp;
   const float imt = 1.0f / mt;
   const float tmp = (F + mp * l * thd * thd * s) * imt;
@@ -140,9 +139,10 @@ __device__ __forceinline__ void quad_trig_finish(QuadTrig& t) {
 }
 __device__ __forceinline__ QuadTrig quad_trig(float phi, float th, float psi) {
   QuadTrig t;
-  qt_sincos(phi, &t.sph, &t.cph);
-  qt_sincos(th, &t.sth, &t.cth);
-  qt_sincos(psi, &t.sps, &t.cps);
+  // (the chain form: the same bits, the reduction behind a vote of the lanes that run this)
+  qt_sincos_chain(phi, &t.sph, &t.cph);
+  qt_sincos_chain(th, &t.sth, &t.cth);
+  qt_sincos_chain(psi, &t.sps, &t.cps);
   quad_trig_finish(t);
   return t;
 }
@@ -258,17 +258,49 @@ __device__ __forceinline__ float qt_final_cost(const quattro_model_params& p, co
 // the same entries are produced in kernels of different layouts and surroundings and must come out bit-identical (explicit fmaf
 // calls stay fused).  Two sites keep a copy of these expressions because their translation units contract implicitly and moving
 // them here would split an fma there: EulerRecord<CARTPOLE>::fill_state below and rk4_step_coefs (sweep_tile16_body.h).
-__device__ __forceinline__ void qt_control_cost_derivs(const quattro_model_params& p, float ra, float ua, float* lu_out,
+//
+// Exact short cut (qt_stage_cost's, for the derivatives).  With z = beta u > 20:
+//   sp = softplus_beta(-u) = log(1 + e^-z) / beta <= e^-z / |beta| < e^-20 / |beta|,   sg = sigmoid(-z) = 1 / (1 + e^z) < e^-20,
+// so the term the barrier adds to l_u,  alpha (-2 sp sg),  is below  2 |alpha| e^-40 / |beta|,  and the one it adds to l_uu,
+// alpha (2 sg^2 + 2 sp beta sg (1 - sg)),  below  |alpha| (2 e^-40 + 2 e^-40) = 4 |alpha| e^-40;  e^-40 < 4.25e-18.  (As computed,
+// sp is exactly 0 there -- 1 + e^-z rounds to 1 -- and sg is within 2e-6 of its value: the margin below covers it.)  Where a
+// bound is under half an ulp of the addend -- |addend| 2^-25, taken as 2.9e-8 -- the fmaf returns the addend unchanged, bit for
+// bit, and the exp / log / division behind it can be skipped.  The predicate comes as the MASK of the lanes it holds for; callers
+// AND the masks of their controls and compare with the lanes that run (qt_all_lanes: one scalar branch).  It fails, and the full
+// path runs, for: a NaN control (z > 20 is false), an infinite one (z <= FLT_MAX), r = 0 or u = 0 (a bound is never below 0), a
+// tiny r (the l_uu bound), a NaN or infinite alpha or beta.
+// (four lane masks combined on the scalar unit: as `a && b && c && d` the compiler nests four exec-mask branches around the compares)
+__device__ __forceinline__ unsigned long long qt_barrier_derivs_negligible(const quattro_model_params& p, float ra, float ua) {
+#pragma clang fp contract(off)
+  const float z = p.barrier_beta * ua;
+  const float e40 = fabsf(p.barrier_alpha) * 4.25e-18f;
+  const float lu = 2.0f * ra * ua, luu = 2.0f * ra;
+  return __builtin_amdgcn_ballot_w64(z > 20.0f) & __builtin_amdgcn_ballot_w64(z <= 3.4028234664e38f) &
+         __builtin_amdgcn_ballot_w64(2.0f * e40 / fabsf(p.barrier_beta) < fabsf(lu) * 2.9e-8f) &
+         __builtin_amdgcn_ballot_w64(4.0f * e40 < fabsf(luu) * 2.9e-8f);
+}
+__device__ __forceinline__ bool qt_all_lanes(unsigned long long m) { return m == __builtin_amdgcn_ballot_w64(true); }
+// `skip`: the caller's wave-uniform verdict that the barrier terms change nothing (every lane that runs this: negligible)
+__device__ __forceinline__ void qt_control_cost_derivs(const quattro_model_params& p, float ra, float ua, bool skip, float* lu_out,
                                                        float* luu_out) {
 #pragma clang fp contract(off)
   float lu = 2.0f * ra * ua, luu = 2.0f * ra;
-  if (p.barrier_alpha != 0.0f) {
+  if (p.barrier_alpha != 0.0f && !skip) {
     const float sp = qt_softplus(-ua, p.barrier_beta), sg = qt_sigmoid(-p.barrier_beta * ua);
     lu = fmaf(p.barrier_alpha, -2.0f * sp * sg, lu);
     luu = fmaf(p.barrier_alpha, 2.0f * sg * sg + 2.0f * sp * p.barrier_beta * sg * (1.0f - sg), luu);
   }
   *lu_out = lu;
   *luu_out = luu;
+}
+// the verdict for the NU controls of one step in a lane, over the lanes of the wave that run this (without a barrier it is true
+// and skips nothing: qt_control_cost_derivs tests barrier_alpha itself)
+template <int NU>
+__device__ __forceinline__ bool qt_barrier_derivs_skip(const quattro_model_params& p, const float* r, const float* u) {
+  unsigned long long m = ~0ull;
+#pragma unroll
+  for (int a = 0; a < NU; ++a) m &= qt_barrier_derivs_negligible(p, r[a], u[a]);
+  return qt_all_lanes(m);
 }
 
 // the terminal pair of the built-in cost: V_x(N)[i] = 2 Qf_i (x_N[i] - x_ref[i]) and the diagonal of V_xx(N) = 2 Qf (no product
@@ -313,9 +345,11 @@ struct EulerRecord<QUATTRO_MODEL_CARTPOLE, L> {
 #pragma unroll
     for (int i = 0; i < 4; ++i) rec[L::lx(i)] = 2.0f * p.q[i] * (x[i] - p.x_ref[i]);
     // (qt_control_cost_derivs' expressions, kept as a copy: this function is compiled with implicit contraction in linearize.hip
-    //  and without in sweep_lane.hip / solve_cartpole.hip, and the helper's contract(off) would split luu's fma in the former)
+    //  and without in sweep_lane.hip / solve_cartpole.hip, and the helper's contract(off) would split luu's fma in the former;
+    //  the helper's short cut stands in front of it: a guard around the block moves no operation inside it)
+    const bool skip = qt_barrier_derivs_skip<1>(p, p.r, u);
     float lu = 2.0f * p.r[0] * u[0], luu = 2.0f * p.r[0];
-    if (p.barrier_alpha != 0.0f) {
+    if (p.barrier_alpha != 0.0f && !skip) {
       const float sp = qt_softplus(-u[0], p.barrier_beta), sg = qt_sigmoid(-p.barrier_beta * u[0]);
       lu = fmaf(p.barrier_alpha, -2.0f * sp * sg, lu);
       luu = fmaf(p.barrier_alpha, 2.0f * sg * sg + 2.0f * sp * p.barrier_beta * sg * (1.0f - sg), luu);
@@ -377,8 +411,9 @@ struct EulerRecord<QUATTRO_MODEL_QUADROTOR, L> {
                                                     const float* u) {
     fill_dynamics(rec, p, quad_trig(x[6], x[7], x[8]), x, u);
     fill_lx(rec, p, x);
+    const bool skip = qt_barrier_derivs_skip<4>(p, p.r, u);    // one vote for the step's four controls
 #pragma unroll
-    for (int a = 0; a < 4; ++a) fill_control(rec, p, a, p.r[a], u[a]);
+    for (int a = 0; a < 4; ++a) fill_control(rec, p, a, p.r[a], u[a], skip);
   }
   // fill_state in parts that write exactly its entries with the same expressions (the fused sweep runs them on two lanes
   // per step): [A | B] at (x, u) from the sines and cosines of the Euler angles; l_x; l_u and l_uu of one control a, whose
@@ -451,9 +486,10 @@ struct EulerRecord<QUATTRO_MODEL_QUADROTOR, L> {
 #pragma unroll
     for (int i = 0; i < 12; ++i) rec[L::lx(i)] = 2.0f * p.q[i] * (x[i] - xr[i]);
   }
-  static __device__ __forceinline__ void fill_control(float* rec, const quattro_model_params& p, int a, float ra, float ua) {
+  // (`skip`: qt_control_cost_derivs' -- the wave's verdict, taken by the caller where every lane of the wave still runs)
+  static __device__ __forceinline__ void fill_control(float* rec, const quattro_model_params& p, int a, float ra, float ua, bool skip) {
     float lu, luu;
-    qt_control_cost_derivs(p, ra, ua, &lu, &luu);
+    qt_control_cost_derivs(p, ra, ua, skip, &lu, &luu);
     rec[L::lu(a)] = lu;
     rec[L::luu(a, a)] = luu;
   }
@@ -599,10 +635,11 @@ __device__ __forceinline__ void fill_cost_entries(float* rec, const quattro_mode
     rec[L::lx(i)] = 2.0f * p.q[i] * (x[i] - p.x_ref[i]);
     rec[L::lxx(i, i)] = 2.0f * p.q[i];
   }
+  const bool skip = qt_barrier_derivs_skip<NU>(p, p.r, u);
 #pragma unroll
   for (int a = 0; a < NU; ++a) {
     float lu, luu;
-    qt_control_cost_derivs(p, p.r[a], u[a], &lu, &luu);
+    qt_control_cost_derivs(p, p.r[a], u[a], skip, &lu, &luu);
     rec[L::lu(a)] = lu;
     rec[L::luu(a, a)] = luu;
   }

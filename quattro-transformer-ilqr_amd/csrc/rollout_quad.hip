@@ -30,6 +30,9 @@ namespace {
 // first.  Line search 36.7 -> 33.6 us, RK4 63.2 -> 54.7 us (A/B on one box; same instructions, same results).  The persistent
 // kernel keeps its line-search wave at one constant priority (solve_quad.hip: PRIO = false), where toggling inside the step
 // bought nothing.  Both kernels keep PF = 4 steps of nominal data requested ahead (quad_rollout_closed).
+// Round 8: the Euler candidates run lane_stage_cost without its barrier test (SHORTCUT = false: the test fails in 98 % of a
+// line-search wave's steps, line search 33.2 -> 32.4 us); the RK4 candidates keep it (without: 51.6 -> 57.7 us, the four stage
+// calls leave the cost no slot it does not pay for), as do simulate and the tracked plant, whose controls stay near the nominal's.
 // simulate: quad per trajectory, 16 trajectories per wave
 template <bool RK4>
 __global__ __launch_bounds__(64) void simulate_quad_kernel(const quattro_model_params p, const float* __restrict__ x0,
@@ -69,9 +72,9 @@ __global__ __launch_bounds__(64) void rollout_quad_kernel(const quattro_model_pa
 #pragma unroll
       for (int g = 0; g < 4; ++g) xo[3 * g + L.a] = xn[3 * g + L.a];
     }
-    J = quad_rollout_closed<RK4, 4, true>(p, L, nom, alpha, N, mine, ArrayStore(L, xo, uo, mine));
+    J = quad_rollout_closed<RK4, 4, true, RK4>(p, L, nom, alpha, N, mine, ArrayStore(L, xo, uo, mine));
   } else {
-    J = quad_rollout_closed<RK4, 4, true>(p, L, nom, alpha, N, mine, NoStore{});
+    J = quad_rollout_closed<RK4, 4, true, RK4>(p, L, nom, alpha, N, mine, NoStore{});
   }
   J = quad_sum(J);
   if (mine && L.j == 0) cost[(size_t)ai * B + b] = J;
@@ -85,7 +88,7 @@ __global__ __launch_bounds__(64) void linesearch_quad_kernel(const quattro_model
                                                              double* cost, int32_t* __restrict__ alpha_idx,
                                                              int32_t* active, int32_t* iters,
                                                              float* __restrict__ scratch) {
-  linesearch_quad_body<RK4, 4, true>(p, x_nom, u_nom, K, k, al, n_alpha, B, N, tol, cost, alpha_idx, active, iters, scratch,
+  linesearch_quad_body<RK4, 4, true, false, false, RK4>(p, x_nom, u_nom, K, k, al, n_alpha, B, N, tol, cost, alpha_idx, active, iters, scratch,
                                      blockIdx.x * blockDim.x + threadIdx.x, false);
 }
 

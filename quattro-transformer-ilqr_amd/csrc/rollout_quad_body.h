@@ -263,6 +263,12 @@ __device__ __forceinline__ unsigned long long barrier_lanes(const quattro_model_
 // rollout whose result is used (the wave-uniform barrier shortcut must not be vetoed by idle quads), as a lane mask the caller
 // takes once, outside its loop: barrier_lanes(p, counted), which is empty where p has no barrier -- the term is then never added,
 // as `if (p.barrier_alpha != 0.0f)` around it had it.
+// SHORTCUT = false (the line search's candidates, round 8): no test at all.  A wave of candidates takes the short cut in 8 % of its
+// steps (the large alphas push a control below 20 / beta almost at once), so the two compares, two ballots, the
+// multiply, the mask arithmetic and the branch that splits the step's block bought next to nothing there.  The term is computed in
+// every lane and kept where the problem has a barrier (`counted` non-empty: barrier_lanes' bit test; one select on a scalar
+// condition).  The same bits: that is what makes the short cut exact.
+template <bool SHORTCUT = true>
 __device__ __forceinline__ float lane_stage_cost(const quattro_model_params& p, const LaneConst& L, const float* xo,
                                                  float uo, unsigned long long counted) {
   float c = 0.0f;
@@ -272,6 +278,16 @@ __device__ __forceinline__ float lane_stage_cost(const quattro_model_params& p, 
     c = fmaf(L.qw[g] * d, d, c);
   }
   c = fmaf(L.rj * uo, uo, c);
+  if constexpr (!SHORTCUT) {
+    const float sp = qt_softplus(-uo, p.barrier_beta);
+    const float cb = fmaf(p.barrier_alpha, sp * sp, c);
+    float cost = counted != 0ull ? cb : c;
+    // (pinned to its step: without the branch nothing holds the cost in place, and left alone the compiler sinks the four costs
+    //  of the unrolled steps to the end of the group behind the last step's recurrence -- 25 registers more and the line search
+    //  34.4 instead of 32.5 us, against 33.2 with the test)
+    asm volatile("" : "+v"(cost));
+    return cost;
+  }
   // exact shortcut, per lane (see qt_stage_cost): with beta*u > 20 the lane's barrier term is below
   // alpha * 4.25e-18 / beta^2; when that is under half an ulp of c the fmaf below returns c unchanged
   const float ib = 1.0f / p.barrier_beta;
@@ -500,12 +516,16 @@ __device__ __forceinline__ void quad_track_body(const LaneConst& L, const bool r
 // What a step issues (round 6, Euler, gfx950, by the SQ counters per wave over N = 50, prologue and commit included): the line
 // search 136 vector / 19 scalar instructions and 5.4 branches per step (6 798 / 963 / 269 per wave), simulate_quad_body's step
 // 80 / 11 / 4.1 (4 008 / 565 / 205); of the line search's ~120 in the loop body 12 are K dx, ~16 the stage cost with its short
-// cut, ~48 the rate function including its in-quad broadcasts, 4 + 1 the record.
+// cut, ~48 the rate function including its in-quad broadcasts, 4 + 1 the record.  Round 8, SHORTCUT = false (the stand-alone line
+// search, without the barrier test): 130 vector / 16 scalar instructions per step (6 505 / 814 per wave) and one branch fewer in
+// every step; the stage cost is ~12 of the loop body's instructions.
 // PRIO: the state recurrence of a step at wave priority 1, the stage cost, the store and the loads that hang off it at 0
 // (rollout_quad.hip); without it the step runs at the caller's priority throughout and adds its stage cost ahead of the rate function.
 // RefS = RefSrc: stage and terminal cost against the step's row.  The row's four floats are requested with the step's nominal data,
 // PF steps ahead, and the terminal row before the loop: the cost is not on the recurrence, and neither are its loads.
-template <bool RK4, int PF, bool PRIO, class Store, class RefS = NoRefSrc>
+// SHORTCUT: lane_stage_cost's -- false for the Euler line-search candidates (linesearch_quad_kernel, rollout_quad_kernel, the
+// persistent loop's line-search phase); rollout_quad.hip has the numbers.
+template <bool RK4, int PF, bool PRIO, bool SHORTCUT, class Store, class RefS = NoRefSrc>
 __device__ __forceinline__ double quad_rollout_closed(const quattro_model_params& p, const LaneConst& L,
                                                       const NomSrc& src, float alpha, int N, bool counted, Store store,
                                                       const RefS& ref = RefS()) {
@@ -532,13 +552,13 @@ __device__ __forceinline__ double quad_rollout_closed(const quattro_model_params
     for (int g = 0; g < 4; ++g) dx[g] = xh[g] - b.x[g];
     const float du = gain_dot(b.K, dx, b.k);
     const float uh = fmaf(alpha, du, b.u);
-    if constexpr (!PRIO) J += (double)lane_stage_cost(p, with_ref<RefS>(L, rt), xh, uh, counted_mask);
+    if constexpr (!PRIO) J += (double)lane_stage_cost<SHORTCUT>(p, with_ref<RefS>(L, rt), xh, uh, counted_mask);
     float xnext[4];
     const QuadU U(uh, Store::ALL_U);
     quad_step<RK4>(L, xh, U, xnext);
     if constexpr (PRIO) {
       __builtin_amdgcn_s_setprio(0);
-      J += (double)lane_stage_cost(p, with_ref<RefS>(L, rt), xh, uh, counted_mask);
+      J += (double)lane_stage_cost<SHORTCUT>(p, with_ref<RefS>(L, rt), xh, uh, counted_mask);
     }
     store(L, t, U, xnext);
 #pragma unroll
@@ -668,7 +688,8 @@ __device__ __forceinline__ void simulate_quad_body(const quattro_model_params& p
 // `force` treats every trajectory as active whatever its flag says (fixed-iteration benchmarking runs).
 // PHYS: the candidates of trajectory b roll out under row b of model_phys (lane_const_phys); the cost stays p's
 // REF: every candidate's cost against the rows of rr (quad_rollout_closed with a RefSrc)
-template <bool RK4, int PF, bool PRIO, bool PHYS = false, bool REF = false>
+// SHORTCUT: lane_stage_cost's barrier test -- the callers switch it off for Euler (rollout_quad.hip)
+template <bool RK4, int PF, bool PRIO, bool PHYS = false, bool REF = false, bool SHORTCUT = true>
 __device__ __forceinline__ void linesearch_quad_body(const quattro_model_params& p, float* x_nom, float* u_nom,
                                                      const float* __restrict__ K, const float* __restrict__ k,
                                                      const AlphaList& al, int n_alpha, int B, int N, double tol,
@@ -694,7 +715,7 @@ __device__ __forceinline__ void linesearch_quad_body(const quattro_model_params&
   for (int i = 1; i < QUATTRO_MAX_ALPHAS; ++i) alpha = (aa == i) ? al.a[i] : alpha;
   const double J0 = live ? cost[bb] : 0.0;
   using RefS = std::conditional_t<REF, RefSrc, NoRefSrc>;
-  double J = quad_rollout_closed<RK4, PF, PRIO>(p, L, nom, alpha, N, mine, ScratchStore(L, sc + (size_t)aa * N * CS, mine),
+  double J = quad_rollout_closed<RK4, PF, PRIO, SHORTCUT>(p, L, nom, alpha, N, mine, ScratchStore(L, sc + (size_t)aa * N * CS, mine),
                                                 RefS(L, rr, wb, live ? b - wb : 0, 2));
   J = quad_sum(J);
   const bool ok = mine && (J <= J0);     // false for NaN, like the reference's comparison

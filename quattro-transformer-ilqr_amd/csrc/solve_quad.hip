@@ -249,7 +249,7 @@ __global__ __launch_bounds__(128, 4) void solve_quad_kernel(const SolveArgs) {
         asm volatile("" : "+v"(ln));
         __builtin_amdgcn_s_setprio(LS_PRIO);        // (one constant priority: toggling inside the step, as the stand-alone
                                                     //  line search does, bought nothing here)
-        linesearch_quad_body<RK4, 2, false, PHYS, REF>(args.fa.p, a.x, a.u, a.K, a.k, a.al, a.n_alpha, a.B, a.N, a.tol, a.cost,
+        linesearch_quad_body<RK4, 2, false, PHYS, REF, RK4>(args.fa.p, a.x, a.u, a.K, a.k, a.al, a.n_alpha, a.B, a.N, a.tol, a.cost,
                                                        a.alpha_idx, a.active, a.iters, a.scratch, 32 * b0 + ln, force, a.model_phys,
                                                        plan_ref_rows(a, cs));
         __builtin_amdgcn_s_setprio(0);

@@ -280,13 +280,16 @@ __device__ __forceinline__ void rk4_step_coefs(const quattro_model_params& p, co
   // implicit contraction of their translation units (sweep_tile16.hip, solve_quad.hip), where l_uu's barrier term is one fma more
   // than under qt_control_cost_derivs' contract(off); the fused RK4 sweep and the persistent loop agree with each other, and
   // moving the copy onto the helper would change their rounding.
+  // (with the helper's exact short cut in front, one vote of the lanes that run this for the step's four controls: a guard
+  //  around the block moves no operation inside it)
   float lz[16], luud[4];
 #pragma unroll
   for (int i = 0; i < NX; ++i) lz[i] = 2.0f * p.q[i] * (xs[i] - xr[i]);
+  const bool skip = qt_barrier_derivs_skip<4>(p, p.r, us);
 #pragma unroll
   for (int a = 0; a < 4; ++a) {
     float lu = 2.0f * p.r[a] * us[a], luu = 2.0f * p.r[a];
-    if (p.barrier_alpha != 0.0f) {
+    if (p.barrier_alpha != 0.0f && !skip) {
       const float sp = qt_softplus(-us[a], p.barrier_beta), sg = qt_sigmoid(-p.barrier_beta * us[a]);
       lu = fmaf(p.barrier_alpha, -2.0f * sp * sg, lu);
       luu = fmaf(p.barrier_alpha, 2.0f * sg * sg + 2.0f * sp * p.barrier_beta * sg * (1.0f - sg), luu);
@@ -834,11 +837,28 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
         }
         const float* const xr = REF ? xrv : fa.p.x_ref;
         // (all 64 lanes: the lanes past cnt hold a real step's (x, u), and the crossbar hop wants every lane active)
+        // Two exact short cuts, where the launch fills the chip (ROTATE: the instantiation for more trajectories than SIMDs): the
+        // chain form of the sines and cosines (the same bits; the range reduction behind a vote of all 64 lanes), and the wave's
+        // verdict on the barrier terms of its controls (qt_barrier_derivs_negligible), taken HERE, once per batch, where every
+        // lane runs: on a flying vehicle's nominal neither role below then executes any barrier code (190 vector instructions per
+        // wave and sweep fewer, -0.5 us at B = 4096).  A lone wave -- the plain kernel, the persistent loops -- is NOT given them: each
+        // vote is a vector compare, scalar mask arithmetic and a branch in a row, which a wave with nobody to hide behind pays for
+        // in full (lone-wave sweep 28.75 -> 29.0 us, persistent iteration 79.9 -> 80.8 us at B = 4096 and 49.4 -> 50.3 us at B = 1).
+        constexpr bool SHORT_CUTS = ROTATE;
         QuadTrig tr;
-        qt_sincos(dynl ? xs[6] : xs[8], &tr.sph, &tr.cph);
-        qt_sincos(xs[7], &tr.sth, &tr.cth);
+        if constexpr (SHORT_CUTS) {
+          qt_sincos_chain(dynl ? xs[6] : xs[8], &tr.sph, &tr.cph);
+          qt_sincos_chain(xs[7], &tr.sth, &tr.cth);
+        } else {
+          qt_sincos(dynl ? xs[6] : xs[8], &tr.sph, &tr.cph);
+          qt_sincos(xs[7], &tr.sth, &tr.cth);
+        }
         tr.sps = __int_as_float(__builtin_amdgcn_ds_bpermute(a32, __float_as_int(tr.sph)));
         tr.cps = __int_as_float(__builtin_amdgcn_ds_bpermute(a32, __float_as_int(tr.cph)));
+        const float uc0 = dynl ? us[0] : us[2], uc1 = dynl ? us[1] : us[3];
+        bool skip = false;
+        if constexpr (SHORT_CUTS)
+          skip = qt_all_lanes(qt_barrier_derivs_negligible(fa.p, ra0, uc0) & qt_barrier_derivs_negligible(fa.p, ra1, uc1));
         if (sl < cnt) {
           // fill_state's entries, over the constant image of the slot (the dynamic lanes' triples hold constants and
           // structural zeros too: what linearize_compact_kernel writes, bit for bit)
@@ -849,8 +869,8 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
           } else {
             ER::fill_lx(mine, fa.p, xr, xs);
           }
-          ER::fill_control(mine, fa.p, ca, ra0, dynl ? us[0] : us[2]);
-          ER::fill_control(mine, fa.p, ca + 1, ra1, dynl ? us[1] : us[3]);
+          ER::fill_control(mine, fa.p, ca, ra0, uc0, skip);
+          ER::fill_control(mine, fa.p, ca + 1, ra1, uc1, skip);
         }
       }
       if (base > 0) fetch(base - FUSED_BATCH);
