@@ -4,6 +4,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "../../include/quattro_hip.h"
 
 #define QT_WAVE 64
@@ -232,3 +234,63 @@ __device__ __forceinline__ float qt_sum_rows(float v) {
 }
 
 __device__ __forceinline__ bool qt_finite(float v) { return fabsf(v) <= 3.0e38f; }
+
+// f(0), f(1), ... f(N - 1) with the index a compile-time constant (std::integral_constant): written-out statements, not a loop that
+// the optimiser unrolls later -- an array indexed by it is scalars from the start
+template <int I, int N, class F>
+__device__ __forceinline__ void qt_static_for_from(F& f) {
+  if constexpr (I < N) {
+    f(std::integral_constant<int, I>{});
+    qt_static_for_from<I + 1, N>(f);
+  }
+}
+template <int N, class F>
+__device__ __forceinline__ void qt_static_for(F f) {
+  qt_static_for_from<0, N>(f);
+}
+
+// ----------------------------------------------------------------------------------------------
+// kernel arguments in one trip (round 9)
+// ----------------------------------------------------------------------------------------------
+// The compiler loads a kernel's arguments where it first needs them, a batch at a time, each batch behind an s_waitcnt of its own:
+// four to eight dependent trips to the scalar cache's backing memory before a rollout's first step, and every wave of a launch
+// starts at the same moment, so no other wave covers them.  qt_kernarg_prefetch<Args...>(), first thing in a kernel, issues ONE
+// scalar load per 64-byte line of the explicit kernel-argument segment (Args = the kernel's parameter types, in order: _of, below) and
+// waits for them together: one trip, after which the compiler's own batches are scalar-cache hits.  The values are not used -- the
+// empty asm only keeps the loads alive (and is where they are waited for).  (scripts/list_prologue_waits.py lists what is left.)
+template <class... Args>
+constexpr int qt_kernarg_bytes() {
+  int off = 0;
+  const int size[] = {(int)sizeof(Args)...}, align[] = {(int)alignof(Args)...};
+  for (int i = 0; i < (int)sizeof...(Args); ++i) off = (off + align[i] - 1) / align[i] * align[i] + size[i];
+  return off;
+}
+template <int LINES>
+__device__ __forceinline__ void qt_kernarg_touch(const uint32_t __attribute__((address_space(4))) * ka, int last) {
+  static_assert(LINES <= 12, "one operand of the asm statement per load");
+  uint32_t v[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) v[i] = ka[i + 1 < LINES ? 16 * i : last];   // (the last load at the segment's last dword: whatever the
+                                                                          //  base's alignment; the slots past LINES repeat it and fold)
+  asm volatile("" ::"s"(v[0]), "s"(v[1]), "s"(v[2]), "s"(v[3]), "s"(v[4]), "s"(v[5]), "s"(v[6]), "s"(v[7]), "s"(v[8]), "s"(v[9]),
+               "s"(v[10]), "s"(v[11]));
+}
+template <class... Args>
+__device__ __forceinline__ void qt_kernarg_prefetch() {
+  constexpr int BYTES = qt_kernarg_bytes<Args...>();
+  static_assert(BYTES >= 4 && BYTES % 4 == 0, "a segment of whole dwords");
+  typedef const uint32_t __attribute__((address_space(4))) * KernArg;
+  qt_kernarg_touch<(BYTES + 63) / 64 + 1>((KernArg)__builtin_amdgcn_kernarg_segment_ptr(), BYTES / 4 - 1);
+}
+// ... with the parameter types taken from the kernel itself, so that the extent follows its signature:
+//   qt_kernarg_prefetch_of<decltype(&my_kernel<...>)>();      first statement of my_kernel
+template <class Kernel>
+struct QtKernArgs;
+template <class... Args>
+struct QtKernArgs<void (*)(Args...)> {
+  static __device__ __forceinline__ void prefetch() { qt_kernarg_prefetch<Args...>(); }
+};
+template <class Kernel>
+__device__ __forceinline__ void qt_kernarg_prefetch_of() {
+  QtKernArgs<Kernel>::prefetch();
+}

@@ -33,13 +33,15 @@ namespace {
 // Round 8: the Euler candidates run lane_stage_cost without its barrier test (SHORTCUT = false: the test fails in 98 % of a
 // line-search wave's steps, line search 33.2 -> 32.4 us); the RK4 candidates keep it (without: 51.6 -> 57.7 us, the four stage
 // calls leave the cost no slot it does not pay for), as do simulate and the tracked plant, whose controls stay near the nominal's.
+// Round 9: simulate and the fused line search fetch their argument block in one trip, first thing (qt_kernarg_prefetch).
 // simulate: quad per trajectory, 16 trajectories per wave
 template <bool RK4>
 __global__ __launch_bounds__(64) void simulate_quad_kernel(const quattro_model_params p, const float* __restrict__ x0,
                                                            const float* __restrict__ u, int B, int N,
                                                            float* __restrict__ x, double* __restrict__ cost) {
+  qt_kernarg_prefetch_of<decltype(&simulate_quad_kernel<RK4>)>();
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-  simulate_quad_body<RK4>(p, x0, u, N, x, cost, gid, (gid >> 2) < B);
+  simulate_quad_body<RK4, false, false, SIM_RING, true>(p, x0, u, N, x, cost, gid, (gid >> 2) < B);
 }
 
 // costs (and optionally trajectories) of every (trajectory, alpha): 8 candidate quads per trajectory
@@ -88,7 +90,8 @@ __global__ __launch_bounds__(64) void linesearch_quad_kernel(const quattro_model
                                                              double* cost, int32_t* __restrict__ alpha_idx,
                                                              int32_t* active, int32_t* iters,
                                                              float* __restrict__ scratch) {
-  linesearch_quad_body<RK4, 4, true, false, false, RK4>(p, x_nom, u_nom, K, k, al, n_alpha, B, N, tol, cost, alpha_idx, active, iters, scratch,
+  qt_kernarg_prefetch_of<decltype(&linesearch_quad_kernel<RK4>)>();
+  linesearch_quad_body<RK4, 4, true, false, false, RK4, true>(p, x_nom, u_nom, K, k, al, n_alpha, B, N, tol, cost, alpha_idx, active, iters, scratch,
                                      blockIdx.x * blockDim.x + threadIdx.x, false);
 }
 

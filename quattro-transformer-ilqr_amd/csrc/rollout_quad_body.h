@@ -584,8 +584,18 @@ __device__ __forceinline__ double quad_rollout_closed(const quattro_model_params
 // `gid` = 4 * trajectory + lane-in-quad; `live` = this quad has a trajectory to roll out (idle quads run along on
 // trajectory 0 without storing: the DPP exchanges and the wave-uniform barrier shortcut need every quad on the same path)
 // PHYS: the quad's physical parameters are row b of model_phys (lane_const_phys); the cost stays p's
-// REF: the cost of step t against the row of rr that step reads (RefSrc), prefetched with the controls, two steps ahead
-template <bool RK4, bool PHYS = false, bool REF = false>
+// REF: the cost of step t against the row of rr that step reads (RefSrc), prefetched with the controls, RING steps ahead
+// RING (round 9; SIM_RING in the stand-alone kernel): the controls sit in a register ring this many steps deep, the loop unrolled to match.  At two steps ahead
+// (rounds 2 - 8) a control was waited for a step and a half after its load issued, ~700 cycles of cover against the 900 of a miss
+// to HBM -- and a 128-byte line holds eight steps of a trajectory's controls, so every wave of a launch misses together every
+// eighth step.  A step issues one control load and four state stores, so the wait for a control is vmcnt(5 SIM_RING - 1 or so):
+// inside the counter's six bits up to a ring of twelve.
+// The persistent loops run this body once per solve, as one phase among many in a kernel that is short of registers: they keep
+// RING = 2 and ENTRY = false, which compiles to the code of rounds 6 - 8 (the same instructions but for a commuted operand or two; a
+// ring of four there, with the other bodies' prologues, cost ten closed-loop control steps 0.7 %).
+// ENTRY: the body is a kernel's whole, its prologue on every wave's critical path -- x0's row is written after the prologue's wait.
+constexpr int SIM_RING = 4;
+template <bool RK4, bool PHYS = false, bool REF = false, int RING = 2, bool ENTRY = false>
 __device__ __forceinline__ void simulate_quad_body(const quattro_model_params& p, const float* __restrict__ x0,
                                                    const float* __restrict__ u, int N, float* __restrict__ x,
                                                    double* __restrict__ cost, const int gid, const bool live,
@@ -608,8 +618,8 @@ __device__ __forceinline__ void simulate_quad_body(const quattro_model_params& p
   // Round 6: the controls come the same way, NomSrc's: the wave's 16 trajectories as one wave-uniform resource, this lane's
   // loop-invariant byte offset, the (clamped) step as a SCALAR offset -- a 64-bit address per lane and step was a vector shift-add
   // and two scalar instructions of a kernel that pays for every issue slot.  An idle quad reads the wave's first trajectory's.
-  // The step is carried as a byte offset of its own (`ou`, two steps ahead, one add and one min per step), and the resource's flag
-  // word is pinned in a register of its own: sharing rsx's, the compiler copied it into place again in every step.
+  // The step is carried as a byte offset of its own (`ou`, RING steps ahead, one add and one min per step), and the resource's
+  // flag word is pinned in a register of its own: sharing rsx's, the compiler copied it into place again in every step.
   int uflags = 0x00020000;
   asm("" : "+s"(uflags));
   const __amdgpu_buffer_rsrc_t rsu =
@@ -619,19 +629,21 @@ __device__ __forceinline__ void simulate_quad_body(const quattro_model_params& p
   auto control = [&](int ofs) __attribute__((always_inline)) {     // the control at byte offset ofs of the row, clamped to the last
     return __int_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsu, vou, ofs < ou_last ? ofs : ou_last, 0));
   };
-  if (writer) {
+  if constexpr (!ENTRY) {
+    if (writer) {
 #pragma unroll
-    for (int g = 0; g < 4; ++g) xo[3 * g] = xh[g];
+      for (int g = 0; g < 4; ++g) xo[3 * g] = xh[g];
+    }
   }
   const RefS ref(L, rr, bw, live ? b - bw : 0, 16);
-  RefLane r0, r1, rN;
-  r0.load(ref, 0);
-  r1.load(ref, N > 1 ? 1 : 0);
+  RefLane rq[RING], rN;
+  qt_static_for<RING>([&](auto d) __attribute__((always_inline)) { rq[d].load(ref, d < N ? d : 0); });   // (a row past the horizon is requested and never read: row 0 will do, also for N = 0)
   rN.load(ref, N);
   double J = 0.0;
   const unsigned long long live_mask = barrier_lanes(p, live);
-  float u0 = control(0), u1 = control(NU * 4);
-  int ou = 2 * (NU * 4);
+  float uq[RING];
+  qt_static_for<RING>([&](auto d) __attribute__((always_inline)) { uq[d] = control(d * (NU * 4)); });
+  int ou = RING * (NU * 4);
   auto step = [&](float ut, const RefLane& rt, int t) __attribute__((always_inline)) {
     J += (double)lane_stage_cost(p, with_ref<RefS>(L, rt), xh, ut, live_mask);
     float xn[4];
@@ -645,7 +657,7 @@ __device__ __forceinline__ void simulate_quad_body(const quattro_model_params& p
     // that writes nothing (the quad's control lane, a lane past the batch) carries an out-of-range offset the range check drops.
     // No exec-mask branch around the stores — which matters beyond the branch: with the stores behind a branch the compiler's
     // wait-count pass must assume they may NOT have been issued, and the wait for the next control (loaded BEFORE them) comes out
-    // as vmcnt(1) instead of vmcnt(5) — every step then waits for the previous step's stores to be acknowledged.
+    // as vmcnt(1) instead of the full count — every step then waits for the previous step's stores to be acknowledged.
     // (round 6: the row is ONE scalar offset and the four states' 0 / 12 / 24 / 36 ride in the instruction's immediate field; as
     //  part of the scalar offset each store had a scalar add of its own per step)
 #pragma unroll
@@ -654,29 +666,52 @@ __device__ __forceinline__ void simulate_quad_body(const quattro_model_params& p
 #pragma unroll
     for (int g = 0; g < 4; ++g) xh[g] = xn[g];
   };
-  // Everything loaded so far (the lane's constants, x0, the first two controls) lands HERE, through the builtin the compiler's
-  // wait-count pass understands: otherwise the loop header inherits those loads as pending and every step carries the decreasing
-  // `s_waitcnt vmcnt(4..1)` the first one needs — which from the second step on wait for the PREVIOUS step's four state stores to
-  // be acknowledged (the counter retires in order): a store round trip on the chain of every step.
-  // (the empty asm "uses" the two prefetched controls, so their loads cannot sink below the wait)
-  asm volatile("" : "+v"(u0), "+v"(u1));
-  if constexpr (REF) {
+  // Everything loaded so far (the lane's constants, x0, the first RING controls: ONE batch of requests, round 9) lands HERE,
+  // through the builtin the compiler's wait-count pass understands: otherwise the loop header inherits those loads as pending and
+  // every step carries the decreasing `s_waitcnt vmcnt(4..1)` the first one needs — which from the second step on wait for the
+  // PREVIOUS step's four state stores to be acknowledged (the counter retires in order): a store round trip on the chain of every step.
+  // (the empty asm "uses" x0 and the prefetched controls, so their loads cannot sink below the wait)
+  if constexpr (ENTRY) {
+    asm volatile("" : "+v"(xh[0]), "+v"(xh[1]), "+v"(xh[2]), "+v"(xh[3]));
 #pragma unroll
-    for (int g = 0; g < 4; ++g) asm volatile("" : "+v"(r0.xr[g]), "+v"(r1.xr[g]), "+v"(rN.xr[g]));
+    for (int d = 0; d < RING; ++d) asm volatile("" : "+v"(uq[d]));      // (a loop: an asm operand does not capture in a lambda)
+  } else {
+    static_assert(ENTRY || RING == 2, "the persistent loops' form");
+    asm volatile("" : "+v"(uq[0]), "+v"(uq[1]));
+  }
+  if constexpr (REF) {
+    if constexpr (ENTRY) {
+#pragma unroll
+      for (int d = 0; d < RING; ++d)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) asm volatile("" : "+v"(rq[d].xr[g]));
+#pragma unroll
+      for (int g = 0; g < 4; ++g) asm volatile("" : "+v"(rN.xr[g]));
+    } else {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) asm volatile("" : "+v"(rq[0].xr[g]), "+v"(rq[1].xr[g]), "+v"(rN.xr[g]));
+    }
   }
   __builtin_amdgcn_s_waitcnt(0x0f70);        // vmcnt(0), nothing else
-  int t = 0;
-  for (; t + 1 < N; t += 2) {
-    step(u0, r0, t);
-    u0 = control(ou);
-    ou += NU * 4;
-    r0.load(ref, t + 2 < N ? t + 2 : N - 1);
-    step(u1, r1, t + 1);
-    u1 = control(ou);
-    ou += NU * 4;
-    r1.load(ref, t + 3 < N ? t + 3 : N - 1);
+  // Row 0 of x is x0, written AFTER that wait (round 9; it used to be requested before it, so that the loop was entered only once
+  // the store had been acknowledged: a third round trip behind the arguments and x0).  Stores carry no register the loop reads,
+  // so pending ones cost its waits nothing.  Through the steps' resource: a lane that writes nothing is dropped by the range check.
+  if constexpr (ENTRY) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) __builtin_amdgcn_raw_buffer_store_b32(__float_as_int(xh[g]), rsx, vox + 12 * g, 0, 0);
   }
-  if (t < N) step(u0, r0, t);
+  int t = 0;
+  for (; t + (RING - 1) < N; t += RING) {
+    qt_static_for<RING>([&](auto d) __attribute__((always_inline)) {
+      step(uq[d], rq[d], t + d);
+      uq[d] = control(ou);
+      ou += NU * 4;
+      rq[d].load(ref, t + d + RING < N ? t + d + RING : N - 1);
+    });
+  }
+  qt_static_for<RING - 1>([&](auto d) __attribute__((always_inline)) {
+    if (t + d < N) step(uq[d], rq[d], t + d);          // wave-uniform tail (N % RING steps)
+  });
   J += (double)lane_final_cost(with_ref<RefS>(L, rN), xh);
   J = quad_sum(J);
   if (live && L.j == 0 && cost != nullptr) cost[b] = J;
@@ -689,7 +724,9 @@ __device__ __forceinline__ void simulate_quad_body(const quattro_model_params& p
 // PHYS: the candidates of trajectory b roll out under row b of model_phys (lane_const_phys); the cost stays p's
 // REF: every candidate's cost against the rows of rr (quad_rollout_closed with a RefSrc)
 // SHORTCUT: lane_stage_cost's barrier test -- the callers switch it off for Euler (rollout_quad.hip)
-template <bool RK4, int PF, bool PRIO, bool PHYS = false, bool REF = false, bool SHORTCUT = true>
+// ENTRY: the body is a kernel's whole (linesearch_quad_kernel): the requests that need the arguments alone go out in one batch ahead
+// of the early exit.  The persistent loops, where this is one phase of an iteration, keep the order of rounds 2 - 8.
+template <bool RK4, int PF, bool PRIO, bool PHYS = false, bool REF = false, bool SHORTCUT = true, bool ENTRY = false>
 __device__ __forceinline__ void linesearch_quad_body(const quattro_model_params& p, float* x_nom, float* u_nom,
                                                      const float* __restrict__ K, const float* __restrict__ k,
                                                      const AlphaList& al, int n_alpha, int B, int N, double tol,
@@ -698,13 +735,39 @@ __device__ __forceinline__ void linesearch_quad_body(const quattro_model_params&
                                                      const bool force, const float* __restrict__ model_phys = nullptr,
                                                      const RefRows& rr = RefRows{}) {
   const int b = gid >> 5, ai = (gid >> 2) & 7, l32 = gid & 31;
-  const bool live = (b < B) && (force || active == nullptr || active[b < B ? b : 0] != 0);
+  // Round 9 (ENTRY): whatever the arguments alone address is requested in ONE batch, ahead of the early exit -- the trajectory's flag,
+  // its cost so far (as a value: which trajectory a lane works on is known only with the flag, but a live lane's is b) and, where the
+  // lane constants are the problem's, their lane-indexed entries.  The flag used to be fetched and waited for alone, then J0, then
+  // the constants.  The nominal data is NOT requested here: its addresses take `live`, and a wave with no live trajectory (most waves
+  // of a solve's late iterations) leaves below without having asked for any of it.
+  bool live;
+  double J0 = 0.0;
+  LaneConst L;
+  if constexpr (ENTRY) {
+    const int bc = b < B ? b : 0;
+    // (the flag from an address that is valid with or without an array of flags -- without, a word of the cost, read and ignored: a
+    //  load behind `active != nullptr` sits in a block of its own and is waited for there, alone.  A lane past the batch reads
+    //  trajectory 0's flag and cost, which that trajectory's wave may be writing at the same moment: an unsynchronised read whose
+    //  value is dropped -- `live` is false for such a lane whatever it read)
+    const int32_t* const fp = active != nullptr ? active + bc : reinterpret_cast<const int32_t*>(cost + bc);
+    const bool flag = (*fp != 0) | force | (active == nullptr);
+    J0 = cost[bc];
+    if constexpr (!PHYS) {
+      L = lane_const(p, gid & 3);
+      asm volatile("" : "+v"(L.rj));              // (the constant's load stays ahead of the exit, with the two above)
+    }
+    asm volatile("" : "+v"(J0));
+    live = (b < B) && flag;
+  } else {
+    live = (b < B) && (force || active == nullptr || active[b < B ? b : 0] != 0);
+  }
   if (!__any(live)) return;   // both trajectories of the wave converged / out of range: nothing to do (late iterations
                               // of a solve run mostly such waves)
   const bool mine = live && ai < n_alpha;
   const size_t bb = live ? b : 0;
   const int aa = mine ? ai : 0;
-  const LaneConst L = lane_const_of<PHYS>(p, model_phys, bb, gid & 3);
+  if constexpr (!ENTRY || PHYS) L = lane_const_of<PHYS>(p, model_phys, bb, gid & 3);
+  if constexpr (ENTRY) J0 = live ? J0 : 0.0;
   float* xn = x_nom + bb * (N + 1) * NX;
   float* un = u_nom + bb * N * NU;
   const int wb = __builtin_amdgcn_readfirstlane(b);    // the wave's first trajectory (gid grows with the lane; wb < B: a lane is live)
@@ -713,7 +776,7 @@ __device__ __forceinline__ void linesearch_quad_body(const quattro_model_params&
   float alpha = al.a[0];
 #pragma unroll
   for (int i = 1; i < QUATTRO_MAX_ALPHAS; ++i) alpha = (aa == i) ? al.a[i] : alpha;
-  const double J0 = live ? cost[bb] : 0.0;
+  if constexpr (!ENTRY) J0 = live ? cost[bb] : 0.0;
   using RefS = std::conditional_t<REF, RefSrc, NoRefSrc>;
   double J = quad_rollout_closed<RK4, PF, PRIO, SHORTCUT>(p, L, nom, alpha, N, mine, ScratchStore(L, sc + (size_t)aa * N * CS, mine),
                                                 RefS(L, rr, wb, live ? b - wb : 0, 2));

@@ -48,18 +48,25 @@ __global__ __launch_bounds__(QT_WAVE * WPB, 4) void sweep_tile16_kernel(const fl
                                                                int32_t* __restrict__ status,
                                                                const int32_t* __restrict__ active,
                                                                const FusedArgs fa) {
+  // (round 9) the argument block in one trip; the fused Euler mode tests the trajectory's flag inside the body, behind its first requests
+  qt_kernarg_prefetch_of<decltype(&sweep_tile16_kernel<MODE, ROTATE>)>();
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int b = blockIdx.x * WPB + wv;
   const int lane = threadIdx.x & 63;
   if (b >= fa.B) return;
-  if (active != nullptr && active[b] == 0) return;
+  const int32_t* flag = nullptr;
+  if constexpr (MODE == MODE_FUSED) {
+    if (active != nullptr) flag = active + b;
+  } else {
+    if (active != nullptr && active[b] == 0) return;
+  }
   __shared__ __attribute__((aligned(16))) float s_t_all[WPB * 16 * LD];
   __shared__ __attribute__((aligned(16))) float s_vx_all[WPB * 64];
   // MODE_FUSED: [header record (TILE16) | FUSED_BATCH compact records (TILE16F)]
   constexpr int LIN_FLOATS = sweep_lin_floats<MODE>();
   __shared__ __attribute__((aligned(16))) float s_lin_all[WPB * LIN_FLOATS];
-  sweep_tile16_body<MODE, false, false, ROTATE>(rec, VxN, VxxN, S, reg, Kout, kout, status, fa, b, lane, s_t_all + wv * 16 * LD, s_vx_all + wv * 64,
-                                                s_lin_all + wv * LIN_FLOATS);
+  sweep_tile16_body<MODE, false, false, ROTATE, MODE == MODE_FUSED>(rec, VxN, VxxN, S, reg, Kout, kout, status, fa, b, lane, s_t_all + wv * 16 * LD, s_vx_all + wv * 64,
+                                                s_lin_all + wv * LIN_FLOATS, nullptr, RefRows{}, flag);
 }
 
 }  // namespace

@@ -353,14 +353,24 @@ __device__ __forceinline__ Rk4Entry rk4_m_entry(const float* ph, int row_tile, i
 // (readfirstlane(b), like the PHYS row); which row a lane reads depends on the step it linearises, so the rows themselves are vector
 // loads: twelve floats per step, fetched where the step's (x_t, u_t) are.  l_xx, V_xx(N) and everything else stay the problem's.
 // ROTATE (MODE_FUSED): a favourite among a SIMD's waves, by wave slot and refill batch (above the priority notes).
-template <int MODE, bool PHYS = false, bool REF = false, bool ROTATE = false>
+// `flag` (MODE_FUSED, the stand-alone kernel; round 9): the trajectory's entry of `active`, or NULL.  The body tests it itself, once
+// the requests that need nothing but the arguments are out -- the first batch's (x, u), the terminal state, the lane's entries of
+// the argument block -- so that the flag, which needs the arguments too, travels with them instead of ahead of them: a trajectory
+// that is switched off returns false from there, having written nothing.
+// ENTRY (MODE_FUSED; round 9): the body is a kernel's whole and its prologue is on every wave's critical path: those requests go out at
+// the top, ahead of the LDS header, and the lane's entry of Qf is one load.  The persistent loops, which run this body once per
+// iteration in a kernel that is short of registers, keep the order of rounds 2 - 8 (their code is what it was).
+template <int MODE, bool PHYS = false, bool REF = false, bool ROTATE = false, bool ENTRY = false>
 __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec, const float* __restrict__ VxN,
                                                   const float* __restrict__ VxxN, int S, float reg,
                                                   float* __restrict__ Kout, float* __restrict__ kout,
                                                   int32_t* __restrict__ status, const FusedArgs& fa, const int b,
                                                   const int lane, float* s_t, float* s_vx, float* s_lin,
-                                                  const float* model_phys = nullptr, const RefRows& rr = RefRows{}) {
+                                                  const float* model_phys = nullptr, const RefRows& rr = RefRows{},
+                                                  const int32_t* __restrict__ flag = nullptr) {
   static_assert(!ROTATE || MODE == MODE_FUSED, "the favourite changes at the refills of the fused Euler mode");
+  static_assert(!ENTRY || MODE == MODE_FUSED, "the early requests are the fused Euler mode's");
+  constexpr bool EARLY = ENTRY;
   static_assert(!(PHYS || REF) || MODE == MODE_FUSED || MODE == MODE_FUSED_RK4, "per-trajectory parameters: the fused modes only");
   const float* rows_b = nullptr;              // REF: the rows of this trajectory
   if constexpr (REF) rows_b = rr.rows + (size_t)__builtin_amdgcn_readfirstlane(b) * rr.R * 12;
@@ -392,17 +402,68 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
   // it, which reorders the Euler kernels' loads and costs the register-bound RK4 persistent kernel 140 instructions of spills.
   float vA0 = 0.0f, vA1 = 0.0f, vA2 = 0.0f;
   float vx0, vx1, vx2;
-  if constexpr (FUSED || RK4F) {
-    const float* xN = fa.x + ((size_t)b * (fa.N + 1) + fa.N) * 12;
-    if (!ucol) {
-      vA0 = (xj == 3 * r + 0) ? 2.0f * fa.p.qf[xj] : 0.0f;
-      vA1 = (xj == 3 * r + 1) ? 2.0f * fa.p.qf[xj] : 0.0f;
-      vA2 = (xj == 3 * r + 2) ? 2.0f * fa.p.qf[xj] : 0.0f;
+  // MODE_FUSED: (x_t, u_t) of a batch's steps, both lanes of a stage slot (the refill below): requested a whole batch ahead (the loads
+  // of batch j - 1 fly while the steps of batch j run; waiting for them at the refill would expose an HBM round trip twice per sweep),
+  // and with EARLY the FIRST batch's first thing (round 9: otherwise they go out behind the header record, five waits into the kernel)
+  float4 xa, xb, xc, ua;
+  float4 ra, rb, rc;                                             // REF: the step's reference row, fetched with them
+  auto fetch = [&](int base) __attribute__((always_inline)) {
+    const int cnt = S - base < FUSED_BATCH ? S - base : FUSED_BATCH;
+    const int t = fa.t_start + base + ((lane & 31) < cnt ? (lane & 31) : 0);      // (lane & 31: the refill's stage slot, `sl` below)
+    const float4* px = reinterpret_cast<const float4*>(fa.x + ((size_t)b * (fa.N + 1) + t) * 12);
+    xa = px[0];
+    xb = px[1];
+    xc = px[2];
+    ua = *reinterpret_cast<const float4*>(fa.u + ((size_t)b * fa.N + t) * 4);
+    if constexpr (REF) {
+      const float4* pr = reinterpret_cast<const float4*>(rows_b + 12 * qt_ref_row(rr, t));
+      ra = pr[0];
+      rb = pr[1];
+      rc = pr[2];
     }
-    const float* const xrN = REF ? rows_b + 12 * qt_ref_row(rr, fa.N) : fa.p.x_ref;      // (the terminal cost is horizon step N)
-    vx0 = 2.0f * fa.p.qf[3 * r + 0] * (xN[3 * r + 0] - xrN[3 * r + 0]);
-    vx1 = 2.0f * fa.p.qf[3 * r + 1] * (xN[3 * r + 1] - xrN[3 * r + 1]);
-    vx2 = 2.0f * fa.p.qf[3 * r + 2] * (xN[3 * r + 2] - xrN[3 * r + 2]);
+  };
+  float ra0e = 0.0f, ra1e = 0.0f;            // EARLY: the weights of the two controls this lane refills (`dynl` below), requested here
+  if constexpr (FUSED || RK4F) {
+    if constexpr (EARLY) {
+      fetch(((S - 1) / FUSED_BATCH) * FUSED_BATCH);
+      const bool dl = (lane < 32) == ((lane & 31) < 13);           // (`dynl` of the refill)
+      ra0e = dl ? fa.p.r[0] : fa.p.r[2];
+      ra1e = dl ? fa.p.r[1] : fa.p.r[3];
+    }
+    const float* xN = fa.x + ((size_t)b * (fa.N + 1) + fa.N) * 12;
+    if constexpr (EARLY) {
+      const float* const xrN = REF ? rows_b + 12 * qt_ref_row(rr, fa.N) : fa.p.x_ref;      // (the terminal cost is horizon step N)
+      // the lane's entry of Qf ONCE, from an index that is valid in every lane (xj is a state index in the control columns too), and
+      // three selects (round 9).  Written as `(xj == 3 r + s) ? 2 Qf[xj] : 0` three times inside `if (!ucol)` it compiled to three
+      // exec-masked blocks, each with the same load and a wait of its own: three round trips in a row.
+      const float qfj = fa.p.qf[xj];
+      float tq[3], tx[3], tr[3];
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        tq[q] = fa.p.qf[3 * r + q];
+        tx[q] = xN[3 * r + q];
+        tr[q] = xrN[3 * r + q];
+      }
+      // (the trajectory's flag, tested behind the requests above: see `flag`)
+      if (flag != nullptr && *flag == 0) return false;
+      const float qf2 = 2.0f * qfj;
+      vA0 = (!ucol && xj == 3 * r + 0) ? qf2 : 0.0f;
+      vA1 = (!ucol && xj == 3 * r + 1) ? qf2 : 0.0f;
+      vA2 = (!ucol && xj == 3 * r + 2) ? qf2 : 0.0f;
+      vx0 = 2.0f * tq[0] * (tx[0] - tr[0]);
+      vx1 = 2.0f * tq[1] * (tx[1] - tr[1]);
+      vx2 = 2.0f * tq[2] * (tx[2] - tr[2]);
+    } else {   // (the persistent loops and MODE_FUSED_RK4 keep the order of their loads: their register allocation follows it)
+      if (!ucol) {
+        vA0 = (xj == 3 * r + 0) ? 2.0f * fa.p.qf[xj] : 0.0f;
+        vA1 = (xj == 3 * r + 1) ? 2.0f * fa.p.qf[xj] : 0.0f;
+        vA2 = (xj == 3 * r + 2) ? 2.0f * fa.p.qf[xj] : 0.0f;
+      }
+      const float* const xrN = REF ? rows_b + 12 * qt_ref_row(rr, fa.N) : fa.p.x_ref;      // (the terminal cost is horizon step N)
+      vx0 = 2.0f * fa.p.qf[3 * r + 0] * (xN[3 * r + 0] - xrN[3 * r + 0]);
+      vx1 = 2.0f * fa.p.qf[3 * r + 1] * (xN[3 * r + 1] - xrN[3 * r + 1]);
+      vx2 = 2.0f * fa.p.qf[3 * r + 2] * (xN[3 * r + 2] - xrN[3 * r + 2]);
+    }
     if constexpr (FUSED) {
       // the constants of the problem, once: the header record, and the constant image (zeros, fill_const) of every stage
       // slot — a refill runs fill_state only, which writes the same entries of a slot every time
@@ -800,28 +861,10 @@ __device__ __forceinline__ bool sweep_tile16_body(const float* __restrict__ rec,
     const int sl = lane & 31;
     const bool dynl = (lane < 32) == (sl < 13);
     const int ca = dynl ? 0 : 2;                                   // this lane's two controls: ca, ca + 1
-    const float ra0 = dynl ? fa.p.r[0] : fa.p.r[2], ra1 = dynl ? fa.p.r[1] : fa.p.r[3];
-    // (x_t, u_t) of a batch's steps, both lanes of a slot: requested a whole batch ahead (the loads of batch j - 1 fly while
-    // the steps of batch j run; waiting for them at the refill would expose an HBM round trip twice per sweep)
-    float4 xa, xb, xc, ua;
-    float4 ra, rb, rc;                                             // REF: the step's reference row, fetched with them
-    auto fetch = [&](int base) __attribute__((always_inline)) {
-      const int cnt = S - base < FUSED_BATCH ? S - base : FUSED_BATCH;
-      const int t = fa.t_start + base + (sl < cnt ? sl : 0);
-      const float4* px = reinterpret_cast<const float4*>(fa.x + ((size_t)b * (fa.N + 1) + t) * 12);
-      xa = px[0];
-      xb = px[1];
-      xc = px[2];
-      ua = *reinterpret_cast<const float4*>(fa.u + ((size_t)b * fa.N + t) * 4);
-      if constexpr (REF) {
-        const float4* pr = reinterpret_cast<const float4*>(rows_b + 12 * qt_ref_row(rr, t));
-        ra = pr[0];
-        rb = pr[1];
-        rc = pr[2];
-      }
-    };
+    // (with EARLY the weights and the first batch's (x, u) were requested at the top of the body)
+    const float ra0 = EARLY ? ra0e : (dynl ? fa.p.r[0] : fa.p.r[2]), ra1 = EARLY ? ra1e : (dynl ? fa.p.r[1] : fa.p.r[3]);
     const int top = ((S - 1) / FUSED_BATCH) * FUSED_BATCH;
-    fetch(top);
+    if constexpr (!EARLY) fetch(top);
     for (int base = top; base >= 0; base -= FUSED_BATCH) {
       const int cnt = S - base < FUSED_BATCH ? S - base : FUSED_BATCH;
       wave_sync();                                       // the previous batch's records are no longer read
