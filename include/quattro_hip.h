@@ -634,6 +634,39 @@ int quattro_track_gradient_f32(const quattro_model_params* p, const float* x, co
                                const float* cost_rows, int flags, float* grad_u_nom, float* grad_K, float* grad_x_nom,
                                float* grad_x0, float* costate, void* stream);
 
+/* CLOSED-LOOP COVARIANCE: how far a tracked run spreads under noise, to first order.  About the realised run of n_steps <= N steps of
+ * quattro_track_f32, with A_t, B_t the plant's step Jacobians at (x_t, u_t) and S = n_steps,
+ *   Acl_t = A_t + B_t K_t   (K == NULL: Acl_t = A_t, the open loop)
+ *   Sigma_0 = cov0[b] (NULL: 0),   Sigma_{t+1} = Acl_t Sigma_t Acl_t^T + W[b]   (W = noise, NULL: 0: the covariance of
+ *                       quattro_track_f32's additive disturbance d_t, which enters after the plant step)
+ *   var_u_t = diag(K_t Sigma_t K_t^T)   (t < S; K == NULL: 0)
+ *   excess  = sum_{t<S} [ sum_i q_i Sigma_t[i][i] + 1/2 sum_a l_uu,t[a][a] var_u_t[a] ] + [QUATTRO_SCORE_TERMINAL] sum_i qf_i Sigma_S[i][i]
+ * excess is the second-order estimate of E[J] - J(realised run) under quattro_score_f32's cost (the built-in models' stage Hessian is
+ * diagonal with l_ux = 0; l_uu is 2 r_a plus the barrier's second derivative at u_t; targets do not enter).  The reference has no
+ * counterpart.
+ *   x [B][n_steps+1][n], u [B][n_steps][m] : the outputs of quattro_track_f32 (the realised run; not checked)
+ *   K [B][N][m][n]    : the gains that call was given; only rows < n_steps are read.  The nominal is not an argument: nothing reads it
+ *   p                 : the cost fields (q, qf, r, barrier), and the integrator and phys the PLANT steps with (the host composes it)
+ *   plant_phys [B][8], cost_rows [B][QUATTRO_COST_ROW_FLOATS] : exactly as quattro_track_gradient_f32 takes them (the built-in
+ *                       quadrotor's weights too, as in quattro_score_f32)
+ *   cov0, noise [B][n][n] : symmetric positive semi-definite; neither is checked, and the recursion READS Sigma AS SYMMETRIC
+ *   cov [B][n_steps+1][n][n] = Sigma_t,  var [B][n_steps+1][n] = its diagonal (the same bits),  var_u [B][N][m] (rows t >= n_steps are
+ *                       written as +0.0), all fp32;  excess [B] fp64: each step's term is an fp64 sum of fp64 products of the fp32
+ *                       entries, and the terms are added in step order.  Any output may be NULL and is then not written; at least one
+ * The built-in models only: a user-model library exports the symbol and answers QUATTRO_ERR_UNSUPPORTED for its model.  Per block of
+ * four steps (csrc/track_covariance.hip): the columns of Acl_t are formed off the serial chain (the tangent of
+ * quattro_track_gradient_f32) and staged in LDS; the chain holds the two products per step -- for the quadrotor 4 + 4
+ * v_mfma_f32_16x16x4_f32 on a 16 x 16 tile with Sigma in the C/D layout, which serves as both operands without a transposition; the
+ * outputs are formed from the parked Sigma_t after the block.  The device's Sigma is symmetric to round-off only.  No atomics, nothing
+ * allocated, no workspace; the results of trajectory b are those of a call with B = 1, bit for bit, and an output does not depend on
+ * which others are asked for.
+ * Before any launch: the model check of quattro_total_cost_f32 first (QUATTRO_ERR_UNSUPPORTED for a user model); then
+ * QUATTRO_ERR_BAD_ARG for a NULL x or u, B, N or n_steps <= 0, n_steps > N, no output at all, a row array that is not 16-byte aligned,
+ * or unknown bits in flags. */
+int quattro_track_covariance_f32(const quattro_model_params* p, const float* x, const float* u, int B, int N, int n_steps,
+                                 const float* K, const float* plant_phys, const float* cost_rows, const float* cov0,
+                                 const float* noise, int flags, float* cov, float* var, float* var_u, double* excess, void* stream);
+
 /* Transformer gain predictor: weights of the reference's TransformerPredictor (quattro_ilqr_tf/transformer_model.py:85-138)
  * as DEVICE pointers, plus the DataNormalizer vectors (:15-50).  Matrices are PyTorch Linear layout [out][in];
  * the `w_*` matrices are 16-bit (raw uint16 bit patterns: bf16, or IEEE half when `precision` says so), everything else

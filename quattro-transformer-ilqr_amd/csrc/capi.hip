@@ -31,6 +31,8 @@ int quattro_launch_track_gradient(const quattro_model_params&, const float*, con
 #ifndef QT_USER_MODEL_HEADER   // (built-in models only: a user-model library answers for its model without the kernel unit)
 int quattro_launch_cost_param_gradient(const quattro_model_params&, const float*, const float*, int, int, const float*, const float*,
                                        const float*, int, const float*, double*, double*, double*, hipStream_t);
+int quattro_launch_track_covariance(const quattro_model_params&, const float*, const float*, int, int, int, const float*, const float*,
+                                    const float*, const float*, const float*, int, float*, float*, float*, double*, hipStream_t);
 #endif
 int quattro_launch_rollout(const quattro_model_params&, const float*, const float*, const float*, const float*,
                            const float*, int, int, int, float*, float*, double*, const int32_t*, hipStream_t);
@@ -301,6 +303,23 @@ int quattro_track_gradient_f32(const quattro_model_params* p, const float* x, co
   return quattro_launch_track_gradient(*p, x, u, B, N, n_steps, K != nullptr ? x_nom : nullptr, K, model_phys, x_ref_rows, ref_rows,
                                        cost_rows, (flags & QUATTRO_SCORE_TERMINAL) != 0 ? 1 : 0, grad_u_nom, grad_K, grad_x_nom,
                                        grad_x0, costate, (hipStream_t)stream);
+}
+
+int quattro_track_covariance_f32(const quattro_model_params* p, const float* x, const float* u, int B, int N, int n_steps,
+                                 const float* K, const float* plant_phys, const float* cost_rows, const float* cov0,
+                                 const float* noise, int flags, float* cov, float* var, float* var_u, double* excess, void* stream) {
+  if (!model_ok(p)) return p ? QUATTRO_ERR_UNSUPPORTED : QUATTRO_ERR_BAD_ARG;
+  if (p->model_id == QUATTRO_MODEL_USER) return QUATTRO_ERR_UNSUPPORTED;
+  if (!x || !u || B <= 0 || N <= 0 || n_steps <= 0 || n_steps > N) return QUATTRO_ERR_BAD_ARG;
+  if (!cov && !var && !var_u && !excess) return QUATTRO_ERR_BAD_ARG;
+  if ((((uintptr_t)plant_phys | (uintptr_t)cost_rows) & 15) != 0) return QUATTRO_ERR_BAD_ARG;
+  if ((flags & ~QUATTRO_SCORE_TERMINAL) != 0) return QUATTRO_ERR_BAD_ARG;
+#ifdef QT_USER_MODEL_HEADER
+  return QUATTRO_ERR_UNSUPPORTED;      // (this library holds one user model's kernels; the built-in models' are the main library's)
+#else
+  return quattro_launch_track_covariance(*p, x, u, B, N, n_steps, K, plant_phys, cost_rows, cov0, noise,
+                                         (flags & QUATTRO_SCORE_TERMINAL) != 0 ? 1 : 0, cov, var, var_u, excess, (hipStream_t)stream);
+#endif
 }
 
 int quattro_rollout_f32(const quattro_model_params* p, const float* x_nom, const float* u_nom, const float* K,

@@ -1,6 +1,7 @@
-// Device functions of the adjoint sweeps (cost_gradient.hip, track_gradient.hip): what a lane forms off the serial chain -- an entry of
-// Lf_x, the l_u of one control, a column of [A | B] with the matching entry of l_z.  Moved here unchanged from cost_gradient.hip, whose
-// kernels compile to the same instructions as before.
+// Device functions of the adjoint sweeps and the covariance recursion (cost_gradient.hip, track_gradient.hip, track_covariance.hip):
+// what a lane forms off the serial chain -- an entry of Lf_x, the l_u of one control, a column of [A | B] or of [A + B K | B] with the
+// matching entry of l_z.  Moved here unchanged from cost_gradient.hip and (track_item) from track_gradient.hip, whose kernels compile to
+// the same instructions as before.
 #pragma once
 #include "rollout_body.h"
 
@@ -115,6 +116,62 @@ __device__ __forceinline__ float grad_item(const quattro_model_params& own, cons
       ua = (NX + a == j) ? us[a] : ua;
     }
     return j >= NX ? grad_control_lu(own, ra, ua) : v;
+  }
+}
+
+// column j of [A + B K | B] at (xs, us) -> col[NX], given the lane's control seed du (state lane j: K[:, j]; control lane a: e_a),
+// and the matching staged entry: l_x[j] + du^T l_u for a state lane, l_u[a] for a control lane (returned)
+template <int MODEL, bool RK4>
+__device__ __forceinline__ float track_item(const quattro_model_params& own, const float* xs, const float* us, const int j,
+                                            const float* du, float* col) {
+  constexpr int NX = ModelDims<MODEL>::NX, NU = ModelDims<MODEL>::NU;
+#ifdef QT_USER_MODEL_HEADER
+  if constexpr (MODEL == QUATTRO_MODEL_USER) {
+    using D = qtad::Dual<float>;
+    D xd[NX], ud[NU], xn[NX];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) xd[i] = D(xs[i], i == j ? 1.0f : 0.0f);
+#pragma unroll
+    for (int a = 0; a < NU; ++a) ud[a] = D(us[a], du[a]);
+    qt_user::step<D, RK4>(own, xd, ud, xn);
+#pragma unroll
+    for (int i = 0; i < NX; ++i) col[i] = xn[i].d;
+    return qt_user::stage_cost<D>(own, xd, ud).d;
+  } else
+#endif
+  {
+    const float dt = own.dt;
+    float dx0[NX];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) dx0[i] = (i == j) ? 1.0f : 0.0f;
+    if constexpr (!RK4) {
+      float dk[NX];
+      qt_rate_jvp<MODEL>(own, xs, us, dx0, du, dk);
+#pragma unroll
+      for (int i = 0; i < NX; ++i) col[i] = fmaf(dt, dk[i], dx0[i]);
+    } else if constexpr (MODEL == QUATTRO_MODEL_QUADROTOR) {
+      QuadStage st[4];
+      quad_rk4_stages(own, own.phys, xs, us, [&](int s, const QuadStage& q) __attribute__((always_inline)) { st[s] = q; });
+      rk4_tangent<NX>(dt, dx0, col, [&](int s, const float* dxs, float* dk) __attribute__((always_inline)) {
+        quad_jvp_at(st[s], own, dxs, du, dk);
+      });
+    } else {
+      float xp[4][NX];
+      rk4_points<NX>(dt, xs, xp, [&](int, const float* xst, float* k) __attribute__((always_inline)) { qt_rate<MODEL>(own, xst, us, k); });
+      rk4_tangent<NX>(dt, dx0, col, [&](int s, const float* dxs, float* dk) __attribute__((always_inline)) {
+        qt_rate_jvp<MODEL>(own, xp[s], us, dxs, du, dk);
+      });
+    }
+    // the lane's own l_x entry (0 for a control lane), then du^T l_u: with du = e_a that is l_u[a] itself (1 * l_u[a] + 0, exact)
+    float v = 0.0f;
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+      const float g = 2.0f * own.q[i] * (xs[i] - own.x_ref[i]);
+      v = (i == j) ? g : v;
+    }
+#pragma unroll
+    for (int a = 0; a < NU; ++a) v = fmaf(du[a], grad_control_lu(own, own.r[a], us[a]), v);
+    return v;
   }
 }
 

@@ -918,6 +918,109 @@ def track_gradient(model, x, u, x_nom=None, K=None, plant=None, plant_phys=None,
     return out
 
 
+TRACK_COVARIANCE_WANTS = ("cov", "var", "var_u", "excess")
+
+
+def check_cov_rows(model, v, B, name):
+    """A covariance per trajectory: None; a diagonal (n,) or (B, n); or a matrix (n, n) or (B, n, n) -- a 2-D (n, n) is the one
+    matrix for every trajectory, also where B = n.  A torch tensor must be floating point.  ValueError otherwise, under the keyword's
+    `name`; host logic only, the values are not looked at."""
+    if v is None:
+        return
+    n = model.n
+    shape = tuple(np.shape(v))
+    if shape not in ((n,), (B, n), (n, n), (B, n, n)):
+        raise ValueError(f"{name} must be a diagonal of shape {(n,)} or {(B, n)} or a matrix of shape {(n, n)} or {(B, n, n)} "
+                         f"(got {shape})")
+    if isinstance(v, torch.Tensor) and not v.is_floating_point():
+        raise ValueError(f"{name} must be floating point (got {v.dtype})")
+
+
+def cov_rows_tensor(model, v, B, device, name="cov0"):
+    """A covariance in any form check_cov_rows takes -> the contiguous [B][n][n] float32 array on `device` that the C ABI takes,
+    expanded with torch ops on the device.  None stays None."""
+    check_cov_rows(model, v, B, name)
+    if v is None:
+        return None
+    n = model.n
+    t = torch.as_tensor(v if isinstance(v, torch.Tensor) else np.asarray(v, dtype=np.float32)).to(device=device, dtype=torch.float32)
+    if tuple(t.shape) in ((n,), (B, n)) and tuple(t.shape) != (n, n):
+        t = torch.diag_embed(t)
+    return t.expand(B, n, n).contiguous()
+
+
+def track_covariance(model, x, u, K=None, plant=None, plant_phys=None, weights=None, cov0=None, noise=None, terminal=True,
+                     want=("var", "var_u", "excess")):
+    """First-order covariance of a tracked closed-loop run on the device (quattro_track_covariance_f32): how far the run of
+    ops.track spreads under noise.  About the realised x (B, S+1, n), u (B, S, m) that ops.track returned under the gains
+    K (B, N, m, n), N >= S, with A_t, B_t the PLANT's step Jacobians at (x_t, u_t) (its integrator, its per-trajectory plant_phys row):
+        Acl_t       = A_t + B_t K_t                        (K None: Acl_t = A_t, the open loop)
+        Sigma_0     = cov0[b]                              (None: 0)
+        Sigma_{t+1} = Acl_t Sigma_t Acl_t^T + W[b]         (W = noise, None: 0: the covariance of ops.track's additive disturbance
+                                                            d_t, which enters after the plant step)
+        var_u_t     = diag(K_t Sigma_t K_t^T)              (t < S; K None: 0)
+        excess      = sum_{t<S} [ sum_i q_i Sigma_t[i][i] + 1/2 sum_a l_uu,t[a][a] var_u_t[a] ] + [terminal] sum_i qf_i Sigma_S[i][i]
+    excess is the second-order estimate of E[J] - J(realised run) under ops.score's cost: l_uu is 2 r_a plus the second derivative of
+    the control barrier at u_t, and q, qf, r are the trajectory's row of `weights` where given (as ops.score takes them, the built-in
+    quadrotor's too).  Targets do not enter: the Hessians do not depend on them.
+    -> dict of device tensors, by `want`: "cov" (B, S+1, n, n) = Sigma_t, "var" (B, S+1, n) its diagonal (the same bits), "var_u"
+    (B, N, m) (rows t >= S are +0.0; N = S with K None), all float32; "excess" (B,) float64, summed in step order.
+    cov0, noise: a diagonal (n,) or (B, n), or a matrix (n, n) or (B, n, n); a 2-D (n, n) is one matrix for every trajectory.  They
+    are expanded on the device.  That they are symmetric and positive semi-definite is the CALLER's responsibility: neither is
+    checked, and the recursion reads Sigma as symmetric (the returned "cov" is symmetric to round-off only).
+    plant / plant_phys: as ops.track takes them.  The built-in models only: NotImplementedError for a user-compiled model, before its
+    library is loaded.  ValueError for a wrong shape or dtype or an unknown or empty `want`, before anything touches the device."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    unknown = [w for w in want if w not in TRACK_COVARIANCE_WANTS]
+    if unknown or not want:
+        raise ValueError(f"want must name at least one of {list(TRACK_COVARIANCE_WANTS)} (got {list(want)})")
+    if len(np.shape(x)) != 3 or len(np.shape(u)) != 3:
+        raise ValueError(f"x must have shape (B, S + 1, n) and u (B, S, m) (got {tuple(np.shape(x))} and {tuple(np.shape(u))})")
+    Bt, S, m = (int(v) for v in u.shape)
+    n = model.n
+    if Bt < 1 or S < 1 or m != model.m or tuple(x.shape) != (Bt, S + 1, n):
+        raise ValueError(f"x must have shape (B, S + 1, {n}) and u (B, S, {model.m}) with B, S >= 1 "
+                         f"(got {tuple(x.shape)} and {tuple(u.shape)})")
+    N = S
+    if K is not None:
+        kshape = tuple(np.shape(K))
+        if len(kshape) != 4 or kshape[0] != Bt or kshape[1] < S or kshape[2:] != (m, n):
+            raise ValueError(f"K must have shape ({Bt}, N, {m}, {n}) with N >= {S} (got {kshape})")
+        N = int(kshape[1])
+    check_plant(model, plant)
+    check_phys_rows(model, plant_phys, Bt, "plant_phys")
+    check_cost_rows(model, weights, Bt, name="weights")
+    check_cov_rows(model, cov0, Bt, "cov0")
+    check_cov_rows(model, noise, Bt, "noise")
+    if model.model_id == _lib.MODEL_USER:
+        raise NotImplementedError("track_covariance runs only for the built-in models")
+    f32 = torch.float32
+    _req(x, (Bt, S + 1, n), f32, "x"); _req(u, (Bt, S, m), f32, "u")
+    if K is not None:
+        _req(K, (Bt, N, m, n), f32, "K")
+    dev = u.device
+    pphys = plant_phys_tensor(model, plant_phys, Bt, dev)
+    cost_rows = cost_rows_tensor(model, weights, Bt, dev, name="weights")
+    c0 = cov_rows_tensor(model, cov0, Bt, dev, "cov0")
+    w = cov_rows_tensor(model, noise, Bt, dev, "noise")
+    out = {}
+    if "cov" in want:
+        out["cov"] = torch.empty((Bt, S + 1, n, n), dtype=f32, device=dev)
+    if "var" in want:
+        out["var"] = torch.empty((Bt, S + 1, n), dtype=f32, device=dev)
+    if "var_u" in want:
+        out["var_u"] = torch.empty((Bt, N, m), dtype=f32, device=dev)
+    if "excess" in want:
+        out["excess"] = torch.empty((Bt,), dtype=torch.float64, device=dev)
+    # the cost fields of the model, the integrator and phys of the plant
+    p = (model if plant is None else model.with_(integrator=plant.integrator, phys=tuple(plant.phys))).c_params()
+    check(_lib.load_for(model).quattro_track_covariance_f32(
+        ctypes.byref(p), _ptr(x), _ptr(u), Bt, N, S, _ptr(K), _ptr(pphys), _ptr(cost_rows), _ptr(c0), _ptr(w),
+        _lib.SCORE_TERMINAL if terminal else 0, _ptr(out.get("cov")), _ptr(out.get("var")), _ptr(out.get("var_u")),
+        _ptr(out.get("excess")), _stream()), "quattro_track_covariance_f32")
+    return out
+
+
 def _mpc_args(model, x_cur, x_nom, u_nom, K, k, cost, tol, max_iter, n_steps, workspace, traj_x, traj_u, traj_iters, disturbance,
               alphas, reg, alpha_idx, active, iters, status):
     """-> (the arguments the three MPC entries share, in the order of quattro_mpc_run_f32 without its stream; what they point to,

@@ -421,7 +421,8 @@ class QuattroILQR:
         and weights, adds "grad_u" (B,N,m) = dJ/du and "grad_norm" (B,) = max |grad_u| per trajectory (computed on the device): a
         first-order optimality measure, which tells a stationary point from a stalled line search (alpha = -1 says only that no
         step was found).  Works in every mode, since it only reads x, u.  Without the keyword nothing new is launched and the
-        dict is what it always was; the stop test does not use the gradient."""
+        dict is what it always was; the stop test does not use the gradient.
+        QuattroILQR.tube(cov0=, noise=) after a solve: the first-order covariance tube around the returned plan."""
         n, m, N, dev = self.model.n, self.model.m, self.horizon, self.device
         if not isinstance(x0, torch.Tensor):
             x0 = np.asarray(x0)
@@ -486,7 +487,26 @@ class QuattroILQR:
         if want_grad:
             out["grad_u"] = ops.cost_gradient(self.model, self.x, self.u, want_x0=False, **rows)["grad_u"]
             out["grad_norm"] = out["grad_u"].abs().amax(dim=(1, 2))
+        self._solved_rows = rows                        # (what tube() reads the plan under)
         return out
+
+    def tube(self, cov0=None, noise=None):
+        """The first-order covariance tube around the plan of the LAST solve when that plan is tracked with its own gains: one
+        ops.track_covariance launch on the solve's x, u, K under that call's model_phys (as the plant's rows) and weights, from a
+        start of covariance cov0 under a disturbance of covariance noise (the forms ops.track_covariance takes; None: zero).
+        -> dict of device tensors "var" (B,N+1,n), "var_u" (B,N,m), "excess" (B,) fp64.  A method of its own rather than a keyword of
+        solve(), whose argument list stays what it was: a solve launches nothing new and returns the keys it always did.  The
+        built-in models, every mode.  NotImplementedError for a user-compiled model, RuntimeError before the first solve, ValueError
+        for a wrong shape, all before anything touches the device."""
+        if self.model.model_id == _lib.MODEL_USER:
+            raise NotImplementedError("tube: ops.track_covariance runs only for the built-in models")
+        rows = getattr(self, "_solved_rows", None)
+        if rows is None or self._B is None:
+            raise RuntimeError("tube() reads the plan of the last solve: call solve() first")
+        ops.check_cov_rows(self.model, cov0, self._B, "cov0")
+        ops.check_cov_rows(self.model, noise, self._B, "noise")
+        return ops.track_covariance(self.model, self.x, self.u, K=self.K, plant_phys=rows["model_phys"], weights=rows["weights"],
+                                    cov0=cov0, noise=noise)
 
 
 # ================================================================================================ iLQR_TF drop-in
