@@ -667,6 +667,44 @@ int quattro_track_covariance_f32(const quattro_model_params* p, const float* x, 
                                  const float* K, const float* plant_phys, const float* cost_rows, const float* cov0,
                                  const float* noise, int flags, float* cov, float* var, float* var_u, double* excess, void* stream);
 
+/* OUTPUT FEEDBACK: n_steps <= N steps of quattro_track_f32's gain law acting on the ESTIMATE of an extended Kalman filter that runs in
+ * the same launch, behind a sensor that measures p_y of the n states.  Per trajectory b, f_plant the plant's step (the integrator and
+ * phys of `plant`, or row b of plant_phys), f_model the estimator's (the integrator and phys of p, or row b of model_phys), obs the
+ * observed indices:
+ *   x_0 = x0[b],  xh = xhat0[b] (NULL: x0[b]),  P = cov0[b] (NULL: 0);  for t = 0 .. n_steps - 1:
+ *   measure   y_i = x_t[obs_i] + v_t[b][i]                                   (meas_noise NULL: v = 0)
+ *   update    for i = 0 .. p_y - 1 in order, j = obs_i:  g = P[:, j],  s = P[j][j] + R[b][i],  e = y_i - xh[j],
+ *             nis_t += e^2 / s,  xh += g e / s,  P -= g g^T / s
+ *   control   u_t = u_nom_t + K_t (xh - x_nom_t)                             (xh AFTER the update)
+ *   plant     x_{t+1} = f_plant(x_t, u_t) + d_t[b]                           (disturbance NULL: 0)
+ *   predict   A = df_model/dx at (xh, u_t),  xh <- f_model(xh, u_t),  P <- A P A^T + W[b]      (noise NULL: W = 0)
+ * The sensor is a selection of state components with independent noise (R diagonal, > 0), for which the scalar updates in sequence
+ * are exactly the batch Kalman update.  The reference has no counterpart.
+ *   x0 [B][n], x_nom [B][N+1][n], u_nom [B][N][m], K [B][N][m][n] : as quattro_track_f32 takes them
+ *   observed [p_y]     : HOST array of state indices, ascending and distinct, 1 <= p_y <= n, shared by the batch
+ *   meas_var           : R, device array [p_y] (meas_var_rows == 0) or [B][p_y] (meas_var_rows == 1); > 0 is the caller's business
+ *   xhat0 [B][n], cov0 [B][n][n], noise [B][n][n] : optional; P IS READ AS SYMMETRIC, positive semi-definite is not checked
+ *   meas_noise [n_steps][B][p_y], disturbance [n_steps][B][n] : optional realised noises
+ *   plant (NULL: p), plant_phys [B][8], model_phys [B][8] : as quattro_track_f32 and quattro_track_gradient_f32 take them
+ *   x [B][n_steps+1][n], u [B][n_steps][m] : required.  Optional, NULL is not written: xhat [B][n_steps+1][n] (row t < n_steps the
+ *                        updated estimate the control of step t used, row n_steps the last prediction), var [B][n_steps+1][n] the
+ *                        diagonal of the same P (the same bits as cov's), cov [B][n_steps+1][n][n], nis [B][n_steps] the normalised
+ *                        innovation squared.  All fp32; cov is symmetric to round-off only
+ * One kernel (csrc/track_estimate.hip): the lane mapping of quattro_track_covariance_f32 with the Jacobian on the serial chain.  The
+ * plant's step and the estimator's base step are one statement of the dynamics: with xhat0 NULL, no meas_noise and the plant equal to
+ * the model, xhat equals x bit for bit and nis is +0.0.  No atomics, nothing allocated, no workspace; the results of trajectory b are
+ * those of a call with B = 1, bit for bit, and an output does not depend on which others are asked for.
+ * The built-in models only: a user-model library exports the symbol and answers QUATTRO_ERR_UNSUPPORTED for its model.
+ * Before any launch: the model check of quattro_total_cost_f32 first (QUATTRO_ERR_UNSUPPORTED for a user model); then
+ * QUATTRO_ERR_BAD_ARG for a NULL x0, x_nom, u_nom, K, observed, meas_var, x or u, B, N or n_steps <= 0, n_steps > N, p_y outside 1 .. n,
+ * meas_var_rows other than 0 or 1, an index out of range, repeated or not ascending, a row array (plant_phys, model_phys) that is not
+ * 16-byte aligned, or a plant that is not the same problem (quattro_track_f32's check). */
+int quattro_track_estimate_f32(const quattro_model_params* p, const quattro_model_params* plant, const float* x0, const float* x_nom,
+                               const float* u_nom, const float* K, int B, int N, int n_steps, const int32_t* observed, int p_y,
+                               const float* meas_var, int meas_var_rows, const float* xhat0, const float* cov0, const float* noise,
+                               const float* meas_noise, const float* disturbance, const float* plant_phys, const float* model_phys,
+                               float* x, float* u, float* xhat, float* var, float* cov, float* nis, void* stream);
+
 /* Transformer gain predictor: weights of the reference's TransformerPredictor (quattro_ilqr_tf/transformer_model.py:85-138)
  * as DEVICE pointers, plus the DataNormalizer vectors (:15-50).  Matrices are PyTorch Linear layout [out][in];
  * the `w_*` matrices are 16-bit (raw uint16 bit patterns: bf16, or IEEE half when `precision` says so), everything else

@@ -33,6 +33,10 @@ int quattro_launch_cost_param_gradient(const quattro_model_params&, const float*
                                        const float*, int, const float*, double*, double*, double*, hipStream_t);
 int quattro_launch_track_covariance(const quattro_model_params&, const float*, const float*, int, int, int, const float*, const float*,
                                     const float*, const float*, const float*, int, float*, float*, float*, double*, hipStream_t);
+int quattro_launch_track_estimate(const quattro_model_params&, const PlantSpec&, const float*, const float*, const float*, const float*,
+                                  int, int, int, const int32_t*, int, const float*, int, const float*, const float*, const float*,
+                                  const float*, const float*, const float*, const float*, float*, float*, float*, float*, float*,
+                                  float*, hipStream_t);
 #endif
 int quattro_launch_rollout(const quattro_model_params&, const float*, const float*, const float*, const float*,
                            const float*, int, int, int, float*, float*, double*, const int32_t*, hipStream_t);
@@ -319,6 +323,32 @@ int quattro_track_covariance_f32(const quattro_model_params* p, const float* x, 
 #else
   return quattro_launch_track_covariance(*p, x, u, B, N, n_steps, K, plant_phys, cost_rows, cov0, noise,
                                          (flags & QUATTRO_SCORE_TERMINAL) != 0 ? 1 : 0, cov, var, var_u, excess, (hipStream_t)stream);
+#endif
+}
+
+int quattro_track_estimate_f32(const quattro_model_params* p, const quattro_model_params* plant, const float* x0, const float* x_nom,
+                               const float* u_nom, const float* K, int B, int N, int n_steps, const int32_t* observed, int p_y,
+                               const float* meas_var, int meas_var_rows, const float* xhat0, const float* cov0, const float* noise,
+                               const float* meas_noise, const float* disturbance, const float* plant_phys, const float* model_phys,
+                               float* x, float* u, float* xhat, float* var, float* cov, float* nis, void* stream) {
+  if (!model_ok(p)) return p ? QUATTRO_ERR_UNSUPPORTED : QUATTRO_ERR_BAD_ARG;
+  if (p->model_id == QUATTRO_MODEL_USER) return QUATTRO_ERR_UNSUPPORTED;
+  if (!x0 || !x_nom || !u_nom || !K || !observed || !meas_var || !x || !u) return QUATTRO_ERR_BAD_ARG;
+  if (B <= 0 || N <= 0 || n_steps <= 0 || n_steps > N) return QUATTRO_ERR_BAD_ARG;
+  if (p_y < 1 || p_y > p->n || (meas_var_rows != 0 && meas_var_rows != 1)) return QUATTRO_ERR_BAD_ARG;
+  for (int i = 0; i < p_y; ++i) {                    // in range, ascending, distinct (a HOST array)
+    if (observed[i] < 0 || observed[i] >= p->n || (i > 0 && observed[i] <= observed[i - 1])) return QUATTRO_ERR_BAD_ARG;
+  }
+  if ((((uintptr_t)plant_phys | (uintptr_t)model_phys) & 15) != 0) return QUATTRO_ERR_BAD_ARG;
+  PlantSpec ps;
+  const int st = plant_spec(p, plant, &ps);
+  if (st != QUATTRO_OK) return st;
+#ifdef QT_USER_MODEL_HEADER
+  return QUATTRO_ERR_UNSUPPORTED;      // (this library holds one user model's kernels; the built-in models' are the main library's)
+#else
+  return quattro_launch_track_estimate(*p, ps, x0, x_nom, u_nom, K, B, N, n_steps, observed, p_y, meas_var, meas_var_rows, xhat0, cov0,
+                                       noise, meas_noise, disturbance, plant_phys, model_phys, x, u, xhat, var, cov, nis,
+                                       (hipStream_t)stream);
 #endif
 }
 

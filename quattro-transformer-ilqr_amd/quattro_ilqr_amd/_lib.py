@@ -108,6 +108,9 @@ SIGNATURES = {
                                            _P, _P, _P, _P, _P, _P]),
     "quattro_track_covariance_f32": (c_int, [POINTER(ModelParams), _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_int,
                                              _P, _P, _P, _P, _P]),
+    "quattro_track_estimate_f32": (c_int, [POINTER(ModelParams), POINTER(ModelParams), _P, _P, _P, _P, c_int, c_int, c_int,
+                                           POINTER(ctypes.c_int32), c_int, _P, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                           _P, _P]),
     "quattro_rollout_f32": (c_int, [POINTER(ModelParams), _P, _P, _P, _P, POINTER(c_float), c_int, c_int, c_int, _P,
                                     _P, _P, _P, _P]),
     "quattro_linesearch_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),

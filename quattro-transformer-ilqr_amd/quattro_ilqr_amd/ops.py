@@ -1021,6 +1021,138 @@ def track_covariance(model, x, u, K=None, plant=None, plant_phys=None, weights=N
     return out
 
 
+TRACK_ESTIMATE_WANTS = ("xhat", "var", "cov", "nis")
+
+
+def check_observed(model, observed):
+    """The observed state indices of a selection sensor -> a tuple of ints: 1 <= p_y <= n of them, in 0 .. n - 1, ascending and
+    distinct.  ValueError otherwise; host logic only."""
+    try:
+        arr = np.asarray(observed)
+        ok = arr.ndim == 1 and 1 <= arr.size <= model.n and np.issubdtype(arr.dtype, np.integer)
+    except Exception:
+        ok = False
+    if not ok:
+        raise ValueError(f"observed must be 1..{model.n} integer state indices (got {observed!r})")
+    obs = tuple(int(v) for v in arr)
+    if obs[0] < 0 or obs[-1] >= model.n or any(b <= a for a, b in zip(obs, obs[1:])):
+        raise ValueError(f"observed must be ascending, distinct indices in 0..{model.n - 1} (got {obs})")
+    return obs
+
+
+def check_meas_var(meas_var, B, p_y):
+    """The measurement variances of a selection sensor, (p_y,) for every trajectory or (B, p_y) -- a 2-D (B, p_y) is per trajectory,
+    also where B = 1 -- every one of them finite and > 0 (the VALUES are looked at, on the host).  -> float32 numpy array.
+    ValueError otherwise."""
+    if isinstance(meas_var, torch.Tensor):
+        if not meas_var.is_floating_point():
+            raise ValueError(f"meas_var must be floating point (got {meas_var.dtype})")
+        meas_var = meas_var.detach().cpu().numpy()
+    try:
+        arr = np.asarray(meas_var, dtype=np.float64)
+    except Exception:
+        raise ValueError(f"meas_var must be numbers of shape {(p_y,)} or {(B, p_y)}") from None
+    if arr.shape not in ((p_y,), (B, p_y)):
+        raise ValueError(f"meas_var must have shape {(p_y,)} or {(B, p_y)} (got {arr.shape})")
+    with np.errstate(over="ignore", under="ignore"):
+        a32 = arr.astype(np.float32)
+    if not (np.all(np.isfinite(arr)) and np.all(arr > 0.0) and np.all(a32 > 0.0) and np.all(np.isfinite(a32))):
+        raise ValueError("meas_var must be finite and > 0 (in float32 too): a noiseless sensor makes the innovation variance singular")
+    return np.ascontiguousarray(arr, dtype=np.float32)
+
+
+def track_estimate(model, x0, x_nom, u_nom, K, steps, observed, meas_var, xhat0=None, cov0=None, noise=None, meas_noise=None,
+                   disturbance=None, plant=None, plant_phys=None, model_phys=None, want=("xhat", "var", "nis")):
+    """Output feedback on the device (quattro_track_estimate_f32): `steps` <= N steps of ops.track's gain law acting on the ESTIMATE
+    of an extended Kalman filter that runs inside the same launch, behind a sensor that measures the states `observed`.  Per
+    trajectory b, with f_plant the plant's step (plant / plant_phys as ops.track takes them) and f_model the estimator's (the model's
+    integrator and phys, or row b of model_phys):
+        x_0 = x0[b],  xh = xhat0[b] (None: x0[b]),  P = cov0[b] (None: 0);  for t = 0 .. steps - 1:
+        measure   y_i = x_t[observed[i]] + meas_noise[t, b, i]                  (None: 0)
+        update    for i in order, j = observed[i]:  g = P[:, j],  s = P[j][j] + meas_var[b][i],  e = y_i - xh[j],
+                  nis_t += e^2 / s,  xh += g e / s,  P -= g g^T / s
+        control   u_t = u_nom_t + K_t (xh - x_nom_t)                            (xh AFTER the update)
+        plant     x_{t+1} = f_plant(x_t, u_t) + disturbance[t, b]               (None: 0)
+        predict   A = df_model/dx at (xh, u_t),  xh <- f_model(xh, u_t),  P <- A P A^T + noise[b]      (None: 0)
+    A selection sensor with independent noise: the scalar updates in sequence are exactly the batch Kalman update.
+    x0 (B, n), x_nom (B, N+1, n), u_nom (B, N, m), K (B, N, m, n): float32 device tensors, as ops.track takes them.  observed: 1..n
+    state indices, ascending and distinct, shared by the batch.  meas_var: (p_y,) or (B, p_y), finite and > 0 (checked on the host).
+    xhat0 (B, n) float32 device tensor.  cov0, noise: the forms ops.track_covariance takes (check_cov_rows); symmetric positive
+    semi-definite is the CALLER's responsibility, and P is read as symmetric.  meas_noise (steps, B, p_y), disturbance (steps, B, n):
+    float32 device tensors, the realised noises.
+    -> dict of float32 device tensors: "x" (B, steps+1, n) and "u" (B, steps, m) always, and by `want`: "xhat" (B, steps+1, n) (row
+    t < steps the updated estimate the control of step t used, row `steps` the last prediction), "var" (B, steps+1, n) the diagonal
+    of the same P (the same bits as "cov"), "cov" (B, steps+1, n, n) (symmetric to round-off only), "nis" (B, steps) the normalised
+    innovation squared, whose mean sits near p_y for a consistent filter.
+    The plant's step and the estimator's are one statement of the dynamics: a perfectly informed estimator (xhat0 None, no
+    meas_noise, the plant equal to the model) returns xhat[:, :steps] == x[:, :steps] bit for bit and nis of +0.0.
+    The built-in models only: NotImplementedError for a user-compiled model, before its library is loaded.  ValueError for a wrong
+    shape, dtype or value, or an unknown entry of `want`, before anything touches the device."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    unknown = [w for w in want if w not in TRACK_ESTIMATE_WANTS]
+    if unknown:
+        raise ValueError(f"want may name {list(TRACK_ESTIMATE_WANTS)} (got {list(want)})")
+    if len(np.shape(u_nom)) != 3:
+        raise ValueError(f"u_nom must have shape (B, N, m) (got {tuple(np.shape(u_nom))})")
+    Bt, N, m = (int(v) for v in u_nom.shape)
+    n = model.n
+    if Bt < 1 or N < 1 or m != model.m:
+        raise ValueError(f"u_nom must have shape (B, N, {model.m}) with B, N >= 1 (got {tuple(u_nom.shape)})")
+    steps = int(steps)
+    if not 1 <= steps <= N:
+        raise ValueError("steps must be in 1..N")
+    for name, t, shape in (("x0", x0, (Bt, n)), ("x_nom", x_nom, (Bt, N + 1, n)), ("K", K, (Bt, N, m, n))):
+        if tuple(np.shape(t)) != shape:
+            raise ValueError(f"{name} must have shape {shape} (got {tuple(np.shape(t))})")
+    obs = check_observed(model, observed)
+    p_y = len(obs)
+    mv = check_meas_var(meas_var, Bt, p_y)
+    for name, t, shape in (("xhat0", xhat0, (Bt, n)), ("meas_noise", meas_noise, (steps, Bt, p_y)),
+                           ("disturbance", disturbance, (steps, Bt, n))):
+        if t is not None and tuple(np.shape(t)) != shape:
+            raise ValueError(f"{name} must have shape {shape} (got {tuple(np.shape(t))})")
+    check_cov_rows(model, cov0, Bt, "cov0")
+    check_cov_rows(model, noise, Bt, "noise")
+    check_plant(model, plant)
+    check_phys_rows(model, plant_phys, Bt, "plant_phys")
+    check_phys_rows(model, model_phys, Bt, "model_phys")
+    if model.model_id == _lib.MODEL_USER:
+        raise NotImplementedError("track_estimate runs only for the built-in models")
+    f32 = torch.float32
+    _req(x0, (Bt, n), f32, "x0"); _req(x_nom, (Bt, N + 1, n), f32, "x_nom"); _req(u_nom, (Bt, N, m), f32, "u_nom")
+    _req(K, (Bt, N, m, n), f32, "K")
+    if xhat0 is not None:
+        _req(xhat0, (Bt, n), f32, "xhat0")
+    if meas_noise is not None:
+        _req(meas_noise, (steps, Bt, p_y), f32, "meas_noise")
+    if disturbance is not None:
+        _req(disturbance, (steps, Bt, n), f32, "disturbance")
+    dev = u_nom.device
+    pphys = plant_phys_tensor(model, plant_phys, Bt, dev)
+    mphys = model_phys_tensor(model, model_phys, Bt, dev)
+    c0 = cov_rows_tensor(model, cov0, Bt, dev, "cov0")
+    w = cov_rows_tensor(model, noise, Bt, dev, "noise")
+    mvt = torch.as_tensor(mv, device=dev)
+    out = {"x": torch.empty((Bt, steps + 1, n), dtype=f32, device=dev), "u": torch.empty((Bt, steps, m), dtype=f32, device=dev)}
+    if "xhat" in want:
+        out["xhat"] = torch.empty((Bt, steps + 1, n), dtype=f32, device=dev)
+    if "var" in want:
+        out["var"] = torch.empty((Bt, steps + 1, n), dtype=f32, device=dev)
+    if "cov" in want:
+        out["cov"] = torch.empty((Bt, steps + 1, n, n), dtype=f32, device=dev)
+    if "nis" in want:
+        out["nis"] = torch.empty((Bt, steps), dtype=f32, device=dev)
+    p = model.c_params()
+    pp = None if plant is None else plant.c_params()
+    obs_c = (ctypes.c_int32 * p_y)(*obs)
+    check(_lib.load_for(model).quattro_track_estimate_f32(
+        ctypes.byref(p), None if pp is None else ctypes.byref(pp), _ptr(x0), _ptr(x_nom), _ptr(u_nom), _ptr(K), Bt, N, steps, obs_c,
+        p_y, _ptr(mvt), 1 if mv.ndim == 2 else 0, _ptr(xhat0), _ptr(c0), _ptr(w), _ptr(meas_noise), _ptr(disturbance), _ptr(pphys),
+        _ptr(mphys), _ptr(out["x"]), _ptr(out["u"]), _ptr(out.get("xhat")), _ptr(out.get("var")), _ptr(out.get("cov")),
+        _ptr(out.get("nis")), _stream()), "quattro_track_estimate_f32")
+    return out
+
+
 def _mpc_args(model, x_cur, x_nom, u_nom, K, k, cost, tol, max_iter, n_steps, workspace, traj_x, traj_u, traj_iters, disturbance,
               alphas, reg, alpha_idx, active, iters, status):
     """-> (the arguments the three MPC entries share, in the order of quattro_mpc_run_f32 without its stream; what they point to,

@@ -422,7 +422,8 @@ class QuattroILQR:
         first-order optimality measure, which tells a stationary point from a stalled line search (alpha = -1 says only that no
         step was found).  Works in every mode, since it only reads x, u.  Without the keyword nothing new is launched and the
         dict is what it always was; the stop test does not use the gradient.
-        QuattroILQR.tube(cov0=, noise=) after a solve: the first-order covariance tube around the returned plan."""
+        QuattroILQR.tube(cov0=, noise=) after a solve: the first-order covariance tube around the returned plan.
+        QuattroILQR.fly(observed=, meas_var=) after a solve: the returned plan and gains flown behind a sensor and an estimator."""
         n, m, N, dev = self.model.n, self.model.m, self.horizon, self.device
         if not isinstance(x0, torch.Tensor):
             x0 = np.asarray(x0)
@@ -507,6 +508,39 @@ class QuattroILQR:
         ops.check_cov_rows(self.model, noise, self._B, "noise")
         return ops.track_covariance(self.model, self.x, self.u, K=self.K, plant_phys=rows["model_phys"], weights=rows["weights"],
                                     cov0=cov0, noise=noise)
+
+    def fly(self, observed, meas_var, steps=None, xhat0=None, cov0=None, noise=None, meas_noise=None, disturbance=None, plant=None,
+            plant_phys=None, want=("xhat", "var", "nis")):
+        """The plan of the LAST solve flown behind a sensor: one ops.track_estimate launch from the solve's start x[:, 0] along its
+        x, u with its gains K, the control acting on the estimate of an extended Kalman filter that measures the states `observed`
+        with variances meas_var.  That call's model_phys rows are the estimator's rows and, unless plant_phys is given, the plant's
+        too (as tube() takes them for the covariance).  steps: None = the horizon.  Everything else as ops.track_estimate takes it.
+        -> its dict: "x", "u" and what `want` names.  A method of its own rather than a keyword of solve(), whose argument list and
+        results stay what they were.  The built-in models.  NotImplementedError for a user-compiled model, RuntimeError before the
+        first solve, ValueError for a wrong shape or value, all before anything touches the device."""
+        if self.model.model_id == _lib.MODEL_USER:
+            raise NotImplementedError("fly: ops.track_estimate runs only for the built-in models")
+        rows = getattr(self, "_solved_rows", None)
+        if rows is None or self._B is None:
+            raise RuntimeError("fly() reads the plan of the last solve: call solve() first")
+        obs = ops.check_observed(self.model, observed)
+        ops.check_meas_var(meas_var, self._B, len(obs))
+        ops.check_cov_rows(self.model, cov0, self._B, "cov0")
+        ops.check_cov_rows(self.model, noise, self._B, "noise")
+        ops.check_plant(self.model, plant)
+        ops.check_phys_rows(self.model, plant_phys, self._B, "plant_phys")
+        S, n = self.horizon if steps is None else int(steps), self.model.n
+        if not 1 <= S <= self.horizon:
+            raise ValueError("steps must be in 1..N")
+        for name, t, shape in (("xhat0", xhat0, (self._B, n)), ("meas_noise", meas_noise, (S, self._B, len(obs))),
+                               ("disturbance", disturbance, (S, self._B, n))):
+            if t is not None and tuple(np.shape(t)) != shape:
+                raise ValueError(f"{name} must have shape {shape} (got {tuple(np.shape(t))})")
+        return ops.track_estimate(self.model, self.x[:, 0].contiguous(), self.x, self.u, self.K,
+                                  S, obs, meas_var, xhat0=xhat0, cov0=cov0, noise=noise,
+                                  meas_noise=meas_noise, disturbance=disturbance, plant=plant,
+                                  plant_phys=rows["model_phys"] if plant_phys is None else plant_phys, model_phys=rows["model_phys"],
+                                  want=want)
 
 
 # ================================================================================================ iLQR_TF drop-in
