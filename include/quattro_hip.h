@@ -705,6 +705,52 @@ int quattro_track_estimate_f32(const quattro_model_params* p, const quattro_mode
                                const float* meas_noise, const float* disturbance, const float* plant_phys, const float* model_phys,
                                float* x, float* u, float* xhat, float* var, float* cov, float* nis, void* stream);
 
+/* A LOGGED RUN filtered and smoothed: the extended Kalman filter of quattro_track_estimate_f32 over sensor readings and controls that
+ * are INPUTS (nothing here steps a plant or forms a control), its log-likelihood, and the fixed-interval smoother.  Per trajectory b,
+ * f the model's step (the integrator and phys of p, or row b of model_phys), obs the observed indices, S = n_steps the number of
+ * logged controls; a NaN in y is "no reading of that sensor at that step":
+ *   filter    xh = xhat0[b],  P = cov0[b] (NULL: 0);  for t = 0 .. S:
+ *     update  for i = 0 .. p_y - 1 in order, j = obs_i, only where y_t[i] is not NaN:  g = P[:, j],  s = P[j][j] + R[b][i],
+ *             e = y_t[i] - xh[j],  innov[t][i] = e,  innov_var[t][i] = s,  nis_t += e^2 / s,  xh += g e / s,  P -= g g^T / s
+ *             (a missing reading: innov = innov_var = NaN, xh and P untouched bit for bit, nothing added to nis_t)
+ *     record  xhat[t] = xh,  cov[t] = P,  var[t] = diag P                     (the posterior of step t)
+ *     predict (t < S)  A_t = df/dx at (xh, u_t),  xh <- f(xh, u_t),  P <- A_t P A_t^T + W[b]      (noise NULL: W = 0)
+ *   loglik[b] = -1/2 sum_t sum_i (ln(2 pi s) + e^2 / s) over the readings that exist: an fp64 sum, in step order and then sensor order,
+ *             of fp64 terms formed from the fp32 e and s that are returned
+ *   smoother  modified Bryson-Frazier in the posterior form, r [n] and Lambda [n][n] zero after the last step;  for t = S .. 0:
+ *     xs[t] = xhat[t] + cov[t] r,   cov_s[t] = cov[t] - cov[t] Lambda cov[t],   var_s[t] = its diagonal (the same bits)
+ *     for i = p_y - 1 .. 0 (REVERSE order), the readings that exist, with that update's g, s, e and k = g / s:
+ *             q = Lambda k,  c = k^T q,  rj = r[j] + e / s - k^T r,  Lambda[j][:] -= q^T,  Lambda[:, j] -= q,  Lambda[j][j] += c + 1 / s,
+ *             r[j] = rj
+ *     (t > 0) r <- A_{t-1}^T r,  Lambda <- A_{t-1}^T Lambda A_{t-1}
+ * In exact arithmetic the smoother is the extended Rauch-Tung-Striebel smoother about the filter's own linearisation points; it needs
+ * no matrix inverse.  The update's statements and their order are quattro_track_estimate_f32's.  The reference has no counterpart.
+ *   y                  : the readings, [n_steps+1][p_y] for one log shared by the batch (y_rows == 0) or [B][n_steps+1][p_y] (y_rows == 1)
+ *   u                  : the applied controls, [n_steps][m] (u_rows == 0) or [B][n_steps][m] (u_rows == 1)
+ *   observed, p_y, meas_var, meas_var_rows, cov0, noise, model_phys : as quattro_track_estimate_f32 takes them; P IS READ AS SYMMETRIC
+ *   xhat0 [B][n]       : required (a log has no true state to default to)
+ *   workspace          : device memory, 16-byte aligned, at least quattro_estimate_log_workspace_bytes(p, B, n_steps, p_y, smooth) bytes,
+ *                        smooth != 0 where any of xs, var_s, cov_s is asked for; nothing beyond that many bytes is touched
+ *   Outputs, all optional (NULL is not written), at least one: xhat, var [B][n_steps+1][n], cov [B][n_steps+1][n][n], innov,
+ *                        innov_var [B][n_steps+1][p_y], nis [B][n_steps+1], xs, var_s [B][n_steps+1][n], cov_s [B][n_steps+1][n][n],
+ *                        all fp32; loglik [B] fp64.  The covariances are symmetric to round-off only
+ * Two kernels on the one stream (csrc/estimate_log.hip): the forward pass is quattro_track_estimate_f32's chain without the plant,
+ * leaving per update k, e / s and 1 / s in the workspace; the backward pass, launched only where xs, var_s or cov_s is asked for,
+ * recomputes the A_t in blocks off its serial chain.  No atomics, nothing allocated; the results of trajectory b are those of a call
+ * with B = 1, bit for bit, an output does not depend on which others are asked for, and the filter's do not depend on the smoother.
+ * The built-in models only: a user-model library exports both symbols and answers QUATTRO_ERR_UNSUPPORTED (the query: 0) for its model.
+ * Before any launch: the model check of quattro_total_cost_f32 first (QUATTRO_ERR_UNSUPPORTED for a user model); then
+ * QUATTRO_ERR_BAD_ARG for a NULL y, u, observed, meas_var or xhat0, B or n_steps <= 0, p_y outside 1 .. n, y_rows, u_rows or
+ * meas_var_rows other than 0 or 1, an index out of range, repeated or not ascending, no output at all, model_phys -- or, with the
+ * smoother, u or xhat -- not 16-byte aligned; then QUATTRO_ERR_WORKSPACE for a NULL, misaligned or short workspace.  The query answers
+ * 0 for what the entry would refuse. */
+size_t quattro_estimate_log_workspace_bytes(const quattro_model_params* p, int B, int n_steps, int p_y, int smooth);
+int quattro_estimate_log_f32(const quattro_model_params* p, const float* y, int y_rows, const float* u, int u_rows, int B, int n_steps,
+                             const int32_t* observed, int p_y, const float* meas_var, int meas_var_rows, const float* xhat0,
+                             const float* cov0, const float* noise, const float* model_phys, void* workspace, size_t workspace_bytes,
+                             float* xhat, float* var, float* cov, float* innov, float* innov_var, float* nis, double* loglik,
+                             float* xs, float* var_s, float* cov_s, void* stream);
+
 /* Transformer gain predictor: weights of the reference's TransformerPredictor (quattro_ilqr_tf/transformer_model.py:85-138)
  * as DEVICE pointers, plus the DataNormalizer vectors (:15-50).  Matrices are PyTorch Linear layout [out][in];
  * the `w_*` matrices are 16-bit (raw uint16 bit patterns: bf16, or IEEE half when `precision` says so), everything else

@@ -37,6 +37,9 @@ int quattro_launch_track_estimate(const quattro_model_params&, const PlantSpec&,
                                   int, int, int, const int32_t*, int, const float*, int, const float*, const float*, const float*,
                                   const float*, const float*, const float*, const float*, float*, float*, float*, float*, float*,
                                   float*, hipStream_t);
+int quattro_launch_estimate_log(const quattro_model_params&, const float*, int, const float*, int, int, int, const int32_t*, int,
+                                const float*, int, const float*, const float*, const float*, const float*, float* const[4], float*,
+                                float*, float*, float*, float*, float*, double*, float*, float*, float*, hipStream_t);
 #endif
 int quattro_launch_rollout(const quattro_model_params&, const float*, const float*, const float*, const float*,
                            const float*, int, int, int, float*, float*, double*, const int32_t*, hipStream_t);
@@ -89,6 +92,26 @@ int plant_spec(const quattro_model_params* p, const quattro_model_params* plant,
   out->integrator = plant->integrator;
   for (int i = 0; i < 8; ++i) out->phys[i] = plant->phys[i];
   return QUATTRO_OK;
+}
+
+// The workspace of quattro_estimate_log_f32 in floats, four regions of whole 16-byte units: the smoother's records (a reading:
+// k padded to 16 or 4, e / s, 1 / s, two floats unused), e and s of every reading, the posterior xhat and the posterior cov.  The
+// filter alone keeps only the second.
+struct LogWorkspace {
+  size_t off[4], floats;
+};
+LogWorkspace log_workspace(int n, int B, int S, int p_y, bool smooth) {
+  const size_t np = n > 4 ? 16 : 4, rows = (size_t)B * ((size_t)S + 1), readings = rows * (size_t)p_y;
+  auto whole = [](size_t v) { return (v + 3) / 4 * 4; };
+  const size_t size[4] = {smooth ? readings * (np + 4) : 0, whole(2 * readings), smooth ? whole(rows * (size_t)n) : 0,
+                          smooth ? whole(rows * (size_t)n * (size_t)n) : 0};
+  LogWorkspace w;
+  w.floats = 0;
+  for (int i = 0; i < 4; ++i) {
+    w.off[i] = w.floats;
+    w.floats += size[i];
+  }
+  return w;
 }
 }  // namespace
 
@@ -349,6 +372,44 @@ int quattro_track_estimate_f32(const quattro_model_params* p, const quattro_mode
   return quattro_launch_track_estimate(*p, ps, x0, x_nom, u_nom, K, B, N, n_steps, observed, p_y, meas_var, meas_var_rows, xhat0, cov0,
                                        noise, meas_noise, disturbance, plant_phys, model_phys, x, u, xhat, var, cov, nis,
                                        (hipStream_t)stream);
+#endif
+}
+
+size_t quattro_estimate_log_workspace_bytes(const quattro_model_params* p, int B, int S, int p_y, int smooth) {
+  if (!model_ok(p) || p->model_id == QUATTRO_MODEL_USER || B <= 0 || S <= 0 || p_y < 1 || p_y > p->n) return 0;
+  return log_workspace(p->n, B, S, p_y, smooth != 0).floats * sizeof(float);
+}
+
+int quattro_estimate_log_f32(const quattro_model_params* p, const float* y, int y_rows, const float* u, int u_rows, int B, int S,
+                             const int32_t* observed, int p_y, const float* meas_var, int meas_var_rows, const float* xhat0,
+                             const float* cov0, const float* noise, const float* model_phys, void* workspace, size_t workspace_bytes,
+                             float* xhat, float* var, float* cov, float* innov, float* innov_var, float* nis, double* loglik,
+                             float* xs, float* var_s, float* cov_s, void* stream) {
+  if (!model_ok(p)) return p ? QUATTRO_ERR_UNSUPPORTED : QUATTRO_ERR_BAD_ARG;
+  if (p->model_id == QUATTRO_MODEL_USER) return QUATTRO_ERR_UNSUPPORTED;
+  if (!y || !u || !observed || !meas_var || !xhat0 || B <= 0 || S <= 0) return QUATTRO_ERR_BAD_ARG;
+  if (p_y < 1 || p_y > p->n || (meas_var_rows != 0 && meas_var_rows != 1) || (y_rows != 0 && y_rows != 1) ||
+      (u_rows != 0 && u_rows != 1))
+    return QUATTRO_ERR_BAD_ARG;
+  for (int i = 0; i < p_y; ++i) {                    // in range, ascending, distinct (a HOST array)
+    if (observed[i] < 0 || observed[i] >= p->n || (i > 0 && observed[i] <= observed[i - 1])) return QUATTRO_ERR_BAD_ARG;
+  }
+  if (!xhat && !var && !cov && !innov && !innov_var && !nis && !loglik && !xs && !var_s && !cov_s) return QUATTRO_ERR_BAD_ARG;
+  const bool smooth = xs != nullptr || var_s != nullptr || cov_s != nullptr;
+  // the backward pass reads u and xhat a step at a time in 16-byte units
+  if ((((uintptr_t)model_phys | (smooth ? (uintptr_t)u | (uintptr_t)xhat : (uintptr_t)0)) & 15) != 0) return QUATTRO_ERR_BAD_ARG;
+  if (p->integrator != QUATTRO_INTEGRATOR_EULER && p->integrator != QUATTRO_INTEGRATOR_RK4) return QUATTRO_ERR_UNSUPPORTED;
+  const LogWorkspace w = log_workspace(p->n, B, S, p_y, smooth);
+  if (workspace == nullptr || ((uintptr_t)workspace & 15) != 0 || workspace_bytes < w.floats * sizeof(float))
+    return QUATTRO_ERR_WORKSPACE;
+#ifdef QT_USER_MODEL_HEADER
+  return QUATTRO_ERR_UNSUPPORTED;      // (this library holds one user model's kernels; the built-in models' are the main library's)
+#else
+  float* const base = static_cast<float*>(workspace);
+  float* const ws[4] = {base + w.off[0], base + w.off[1], base + w.off[2], base + w.off[3]};
+  return quattro_launch_estimate_log(*p, y, y_rows, u, u_rows, B, S, observed, p_y, meas_var, meas_var_rows, xhat0, cov0, noise,
+                                     model_phys, ws, xhat, var, cov, innov, innov_var, nis, loglik, xs, var_s, cov_s,
+                                     (hipStream_t)stream);
 #endif
 }
 

@@ -111,6 +111,9 @@ SIGNATURES = {
     "quattro_track_estimate_f32": (c_int, [POINTER(ModelParams), POINTER(ModelParams), _P, _P, _P, _P, c_int, c_int, c_int,
                                            POINTER(ctypes.c_int32), c_int, _P, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                            _P, _P]),
+    "quattro_estimate_log_workspace_bytes": (c_size_t, [POINTER(ModelParams), c_int, c_int, c_int, c_int]),
+    "quattro_estimate_log_f32": (c_int, [POINTER(ModelParams), _P, c_int, _P, c_int, c_int, c_int, POINTER(ctypes.c_int32), c_int,
+                                         _P, c_int, _P, _P, _P, _P, _P, c_size_t, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "quattro_rollout_f32": (c_int, [POINTER(ModelParams), _P, _P, _P, _P, POINTER(c_float), c_int, c_int, c_int, _P,
                                     _P, _P, _P, _P]),
     "quattro_linesearch_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),

@@ -1153,6 +1153,101 @@ def track_estimate(model, x0, x_nom, u_nom, K, steps, observed, meas_var, xhat0=
     return out
 
 
+ESTIMATE_LOG_FILTER_WANTS = ("xhat", "var", "cov", "innov", "innov_var", "nis", "loglik")
+ESTIMATE_LOG_SMOOTH_WANTS = ("xs", "var_s", "cov_s")
+
+
+def estimate_log(model, y, u, observed, meas_var, xhat0, cov0=None, noise=None, model_phys=None, smooth=False,
+                 want=("xhat", "var", "nis", "loglik")):
+    """A LOGGED run filtered and smoothed on the device (quattro_estimate_log_f32): ops.track_estimate's extended Kalman filter over
+    sensor readings and controls that are inputs, its log-likelihood, and the fixed-interval smoother.  Nothing here steps a plant or
+    forms a control.  Per trajectory b, f the model's step (its integrator and phys, or row b of model_phys), S the number of logged
+    controls; a NaN in y is "no reading of that sensor at that step" (dropouts, slow sensors, a log without a final reading):
+        xh = xhat0[b],  P = cov0[b] (None: 0);  for t = 0 .. S:
+        update    for i in order, j = observed[i], only where y_t[i] is not NaN:  g = P[:, j],  s = P[j][j] + meas_var[b][i],
+                  e = y_t[i] - xh[j],  innov[t][i] = e,  innov_var[t][i] = s,  nis_t += e^2 / s,  xh += g e / s,  P -= g g^T / s
+                  (a missing reading: innov = innov_var = NaN, xh and P untouched bit for bit, nothing added to nis_t)
+        record    xhat[t] = xh,  cov[t] = P,  var[t] = diag P                   (the posterior of step t)
+        predict   (t < S)  A_t = df/dx at (xh, u_t),  xh <- f(xh, u_t),  P <- A_t P A_t^T + noise[b]      (None: 0)
+        loglik[b] = -1/2 sum_t sum_i (ln(2 pi s) + e^2 / s) over the readings that exist, summed in fp64 in step and sensor order
+    smooth=True adds the modified Bryson-Frazier smoother (in exact arithmetic the extended Rauch-Tung-Striebel smoother about the
+    filter's linearisation points), r and Lambda zero after the last step, for t = S .. 0:
+        xs[t] = xhat[t] + cov[t] r,   cov_s[t] = cov[t] - cov[t] Lambda cov[t],   var_s[t] = its diagonal
+        for i in REVERSE order, the readings that exist, k = g / s of that update:  q = Lambda k,  c = k^T q,
+                  rj = r[j] + e / s - k^T r,  Lambda[j][:] -= q^T,  Lambda[:, j] -= q,  Lambda[j][j] += c + 1 / s,  r[j] = rj
+        (t > 0)   r <- A_{t-1}^T r,  Lambda <- A_{t-1}^T Lambda A_{t-1}
+    y: (S+1, p_y) for one log shared by every hypothesis, or (B, S+1, p_y); u: (S, m) or (B, S, m); float32 device tensors.  B comes
+    from whichever is 3-D, else from xhat0 (B, n), which is required: a log has no true state to default to.  observed, meas_var: as
+    ops.track_estimate takes them (check_observed, check_meas_var).  cov0, noise: check_cov_rows' forms; symmetric positive
+    semi-definite is the CALLER's responsibility, and P is read as symmetric.  model_phys: rows as ops.track_estimate takes them.
+    -> dict of device tensors, by `want`: "xhat", "var" (B, S+1, n), "cov" (B, S+1, n, n), "innov", "innov_var" (B, S+1, p_y), "nis"
+    (B, S+1) float32; "loglik" (B,) float64; with smooth=True also "xs", "var_s" (B, S+1, n), "cov_s" (B, S+1, n, n), of which "xs"
+    and "var_s" are added to the default `want`.  var / var_s are the diagonals of cov / cov_s (the same bits); the filter's outputs do
+    not depend on whether the smoother runs.  The workspace is a torch allocation sized by quattro_estimate_log_workspace_bytes.
+    The built-in models only: NotImplementedError for a user-compiled model, before its library is loaded.  ValueError for a wrong
+    shape, dtype or value, an unknown or empty `want`, or a smoothed entry of `want` without smooth=True, before anything touches the
+    device."""
+    smooth = bool(smooth)
+    default = want is estimate_log.__defaults__[-1]
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if default and smooth:
+        want = want + ("xs", "var_s")
+    known = ESTIMATE_LOG_FILTER_WANTS + ESTIMATE_LOG_SMOOTH_WANTS
+    unknown = [w for w in want if w not in known]
+    if unknown or not want:
+        raise ValueError(f"want must name at least one of {list(known)} (got {list(want)})")
+    if not smooth and any(w in ESTIMATE_LOG_SMOOTH_WANTS for w in want):
+        raise ValueError(f"want names {[w for w in want if w in ESTIMATE_LOG_SMOOTH_WANTS]}, which need smooth=True")
+    n, m = model.n, model.m
+    obs = check_observed(model, observed)
+    p_y = len(obs)
+    yshape, ushape, hshape = tuple(np.shape(y)), tuple(np.shape(u)), tuple(np.shape(xhat0))
+    if len(ushape) not in (2, 3) or ushape[-1] != m or ushape[-2] < 1:
+        raise ValueError(f"u must have shape (S, {m}) or (B, S, {m}) with S >= 1 (got {ushape})")
+    S = int(ushape[-2])
+    if len(yshape) not in (2, 3) or yshape[-2:] != (S + 1, p_y):
+        raise ValueError(f"y must have shape ({S + 1}, {p_y}) or (B, {S + 1}, {p_y}) (got {yshape})")
+    if len(hshape) != 2 or hshape[1] != n or hshape[0] < 1:
+        raise ValueError(f"xhat0 must have shape (B, {n}) with B >= 1 (got {hshape})")
+    Bt = int(hshape[0])
+    for name, shape in (("y", yshape), ("u", ushape)):
+        if len(shape) == 3 and shape[0] != Bt:
+            raise ValueError(f"{name} must have {Bt} trajectories, as xhat0 has (got {shape})")
+    mv = check_meas_var(meas_var, Bt, p_y)
+    check_cov_rows(model, cov0, Bt, "cov0")
+    check_cov_rows(model, noise, Bt, "noise")
+    check_phys_rows(model, model_phys, Bt, "model_phys")
+    if model.model_id == _lib.MODEL_USER:
+        raise NotImplementedError("estimate_log runs only for the built-in models")
+    f32 = torch.float32
+    for name, t in (("y", y), ("u", u), ("xhat0", xhat0)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name} must be a float32 device tensor (got {type(t).__name__})")
+    _req(y, yshape, f32, "y"); _req(u, ushape, f32, "u"); _req(xhat0, (Bt, n), f32, "xhat0")
+    dev = xhat0.device
+    mphys = model_phys_tensor(model, model_phys, Bt, dev)
+    c0 = cov_rows_tensor(model, cov0, Bt, dev, "cov0")
+    w = cov_rows_tensor(model, noise, Bt, dev, "noise")
+    mvt = torch.as_tensor(mv, device=dev)
+    shapes = dict(xhat=(Bt, S + 1, n), var=(Bt, S + 1, n), cov=(Bt, S + 1, n, n), innov=(Bt, S + 1, p_y), innov_var=(Bt, S + 1, p_y),
+                  nis=(Bt, S + 1), xs=(Bt, S + 1, n), var_s=(Bt, S + 1, n), cov_s=(Bt, S + 1, n, n))
+    out = {k: torch.empty(shapes[k], dtype=f32, device=dev) for k in known if k in want and k != "loglik"}
+    if "loglik" in want:
+        out["loglik"] = torch.empty((Bt,), dtype=torch.float64, device=dev)
+    p = model.c_params()
+    lib = _lib.load_for(model)
+    ws_bytes = int(lib.quattro_estimate_log_workspace_bytes(ctypes.byref(p), Bt, S, p_y, int(smooth)))
+    ws = torch.empty(((ws_bytes + 15) // 16 * 4,), dtype=f32, device=dev)
+    obs_c = (ctypes.c_int32 * p_y)(*obs)
+    check(lib.quattro_estimate_log_f32(
+        ctypes.byref(p), _ptr(y), 1 if len(yshape) == 3 else 0, _ptr(u), 1 if len(ushape) == 3 else 0, Bt, S, obs_c, p_y, _ptr(mvt),
+        1 if mv.ndim == 2 else 0, _ptr(xhat0), _ptr(c0), _ptr(w), _ptr(mphys), _ptr(ws), ws_bytes, _ptr(out.get("xhat")),
+        _ptr(out.get("var")), _ptr(out.get("cov")), _ptr(out.get("innov")), _ptr(out.get("innov_var")), _ptr(out.get("nis")),
+        _ptr(out.get("loglik")), _ptr(out.get("xs")), _ptr(out.get("var_s")), _ptr(out.get("cov_s")), _stream()),
+        "quattro_estimate_log_f32")
+    return out
+
+
 def _mpc_args(model, x_cur, x_nom, u_nom, K, k, cost, tol, max_iter, n_steps, workspace, traj_x, traj_u, traj_iters, disturbance,
               alphas, reg, alpha_idx, active, iters, status):
     """-> (the arguments the three MPC entries share, in the order of quattro_mpc_run_f32 without its stream; what they point to,
