@@ -132,10 +132,11 @@ def worst(errs):
 
 
 # ---------------------------------------------------------------------------------------------------------------- cases
-def case(model, set_name="skew", integ="rk4", N=7, S=None, terminal=True, plant_integ=None, hetero=(), cov="dense", open=False):
+def case(model, set_name="skew", integ="rk4", N=7, S=None, terminal=True, plant_integ=None, hetero=(), cov="dense", open=False,
+         B=pol.B_CASE):
     """policy_cases.case plus cov0, noise (None or (B, n, n)), Kc (the gains the entry is given: K, or None with open=True) and
     ref = propagate() in fp64."""
-    c = pol.case(model, set_name, integ, N, S, terminal=terminal, plant_integ=plant_integ, hetero=hetero)
+    c = pol.case(model, set_name, integ, N, S, B=B, terminal=terminal, plant_integ=plant_integ, hetero=hetero)
     cov0, noise = cov_inputs(model, c["x"].shape[0], cov)
     Kc = None if open else c["K"]
     Nv = c["S"] if open else N                                  # var_u has the gains' rows; without gains, the run's
@@ -157,7 +158,8 @@ def mutant_errors(c, name):
 
 
 # The cases the restatement is measured on and the GPU parity test runs: both models, both integrators, the skew set, policy_cases.STEPS
-# (the remainders of a four-step pass and of a multi-pass run), rows per trajectory, a plant with the other integrator, the terminal
+# (S = 7, 5, 1, 26: the remainders 3, 1, 1, 2 of a four-step pass, one pass and several; NOT remainder 0, the one length at which the
+# terminal slot goes into a second output pass -- tests/step_grid_cases.py has those lengths), rows per trajectory, a plant with the other integrator, the terminal
 # flag off, the zero start and the open loop.
 def parity_cases(model):
     out = []
